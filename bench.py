@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- SAM-Decoding draft+verify hot path on MI355X, BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: launched by torch.distributed.run, one rank/GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                                  (N > 1: launched by torch.distributed.run, one rank/GPU)
 
 Workload (config.workload): BASELINE.json configs[1] -- samd_sam_only on a Vicuna-7B-shaped fp16 Llama, bs=1,
 max_predicts 60 / alpha 4 / len_bias 0 (scripts/inference_samd_sam_only.sh:17-19 of the reference).  There are no
@@ -17,7 +18,13 @@ exactly K steps (request turnover -- reset, prefill, prompt ingestion -- include
 barrier + synchronize; value = accepted tokens of all ranks / max-over-ranks time.  Requests are independent, so N GPUs
 = N replicas on disjoint request shards with no data-path collective ("scaling": "weak").
 
-Extra objects in the JSON line: `roofline` = the SAM traversal kernel (k_static_walk) in batched-streams form, HIP
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step (`--dump-outputs DIR`) and
+prints the headline line.  Everything else it can measure runs only with `--full`, after the timed region.
+
+`--dump-outputs DIR`: what the timed path computed, as .npy files (see dump_outputs).  Every input is seeded, so two
+builds run with the same arguments can be compared file by file.
+
+Extra objects in the JSON line of a `--full` run: `roofline` = the SAM traversal kernel (k_static_walk) in batched-streams form, HIP
 events around the launches, algorithmic bytes = 16 B x visited states; `cpu_baseline` = the C
 oracle (oracle/, a port of the reference's Python SAM path) on this box's host cores over a bounded sample of the same
 request streams; plus the autoregressive baseline, step-time breakdown and verify-forward bandwidth of the same run.
@@ -850,6 +857,27 @@ def launch_selftest(args):
         dist.destroy_process_group()
 
 
+DUMP_TOKENS_MAX = 1 << 22       # --dump-outputs keeps the last 4 M tokens / step lengths of the timed region (16 MB each as float32)
+
+
+def dump_outputs(directory, last_ids, verify_logits, timed_tokens, timed_accepts):
+    """--dump-outputs DIR: what the timed path computed, written after the timed region.
+    last_step_tokens        the accepted tokens of the last timed step (what SamdModel._run yields its caller)
+    last_step_verify_logits the verify forward's logits of that step's draft nodes, [n, vocab] (the LM's output before the
+                            scripted arg-max replaces its choice)
+    timed_tokens            every token the timed steps accepted, in order (the last DUMP_TOKENS_MAX)
+    timed_accept_lengths    tokens accepted per timed step (the last DUMP_TOKENS_MAX)
+    Token ids are stored as float32, which holds every id below 2^24 exactly (both vocabularies here are smaller)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"last_step_tokens": np.asarray(last_ids, dtype=np.float32),
+              "last_step_verify_logits": verify_logits.float().cpu().numpy(),
+              "timed_tokens": np.asarray(timed_tokens, dtype=np.float32),
+              "timed_accept_lengths": np.asarray(timed_accepts, dtype=np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -876,10 +904,15 @@ def main():
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--workload", choices=["headline", "summarization"], default="headline",
                     help="the timed region and `value` are ALWAYS the headline (configs[1]); 'summarization' runs the `summarization` object's leg "
-                         "(long prompts, prompt-copy continuations, AR incl. prefill) over 24 requests per profile instead of the default 6")
-    ap.add_argument("--summ-requests", type=int, default=None, help="requests per profile of the summarization leg (0 = skip it)")
+                         "(long prompts, prompt-copy continuations, AR incl. prefill, --full only) over 24 requests per profile instead of the default 6")
+    ap.add_argument("--summ-requests", type=int, default=None, help="requests per profile of the summarization leg of a --full run (0 = skip it)")
     ap.add_argument("--launch-selftest", action="store_true", help="CPU check of the N-rank plumbing (gloo): spawn, rendezvous, reduce, relay; no GPU work")
     ap.add_argument("--dry-launch", action="store_true", help="with --gpus N > 1 outside a launcher: print the child command as JSON and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure the context of the line: long run, per-bucket step breakdown, autoregressive "
+                         "baseline, summarization leg, roofline figures (live counters included), CPU baseline; a plain run prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
 
     # --gpus N > 1 outside torch.distributed.run: start the N ranks as a CHILD process (never exec: this process may not be
@@ -924,7 +957,9 @@ def main():
     # the part of it that is NOT moving the image: re-deriving the walk tables on this rank.  world > 1: clocked inside
     # broadcast_static around the adopt; world 1: the walk tables derived once more, clocked (the upload made them once already)
     dist_split = getattr(auto, "distribution", None)
-    if dist_split is None:
+    if dist_split is None and not args.full:
+        dist_split = {"broadcast_ms": None, "derive_ms": None}     # a plain run does not clock the re-derivation
+    elif dist_split is None:
         t_rd = time.perf_counter()
         auto.set_bigram_slots(0)
         torch.cuda.synchronize()
@@ -988,12 +1023,24 @@ def main():
             yield prompt, target
 
     req_log = []
+    last_step = {"ids": [], "n_next": 0}              # --dump-outputs: the last step's tokens and the draft size it verified
+    dump = None
+    if args.dump_outputs:
+        from collections import deque
+        dump = {"tokens": deque(maxlen=DUMP_TOKENS_MAX), "accepts": deque(maxlen=DUMP_TOKENS_MAX)}
+        _engine_step = model.engine.step
+
+        def _recorded_step(n_next, *a, **kw):
+            last_step["n_next"] = n_next
+            return _engine_step(n_next, *a, **kw)
+        model.engine.step = _recorded_step
 
     def steps_forever():
         for prompt, target in requests():
             req_log.append((prompt, target))
             ids = torch.tensor([prompt], dtype=torch.long, device="cuda")
             for new_ids, rep in model._run(ids, gcfg, gcfg.max_new_tokens):
+                last_step["ids"] = new_ids
                 yield len(new_ids)
 
     # request turnover (reset + prefill + prompt ingest + the first draft = engine.start, synchronous) is part of the timed region when
@@ -1058,12 +1105,22 @@ def main():
         if step_times is not None:
             ts = time.perf_counter()
         tokens += next(it)
+        if dump is not None:
+            dump["tokens"].extend(last_step["ids"])
+            dump["accepts"].append(len(last_step["ids"]))
         if step_times is not None:
             step_times.append(round((time.perf_counter() - ts) * 1e3, 3))
     fence()
     dt = time.perf_counter() - t0
     turnover_timed = dict(turnover)
     model.engine.start = _engine_start
+    dumped = None
+    if dump is not None:
+        model.engine.step = _engine_step
+        if rank == 0 and args.steps > 0:
+            n = last_step["n_next"]
+            logits = runner._buffers(lm.bucket(n))["logits"][:n]          # the verify buffers of the last step's row bucket
+            dumped = dump_outputs(args.dump_outputs, last_step["ids"], logits, dump["tokens"], dump["accepts"])
     if step_times is not None:
         print("step wall times (ms):", step_times, file=sys.stderr, flush=True)
     stats = {k: list(v) for k, v in model.lookup_stats.items()}
@@ -1077,8 +1134,46 @@ def main():
             ("eval_posterior_us", "dyn_update_us", "static_transfer_us", "lookup_draft_buffers_us"))})
 
     # SUM of tokens, MAX of time over ranks; every rank's own wait for the static automaton (broadcast + adopt) travels along
-    tokens_total, dt_max, per_rank = parallel.reduce_throughput(tokens, dt, extra={"static_sam_distribution_ms": broadcast_ms,
-                                                                                   "static_sam_derive_ms": dist_split["derive_ms"]})
+    rank_extra = {"static_sam_distribution_ms": broadcast_ms}
+    if dist_split["derive_ms"] is not None:                    # None: a plain run at world 1 did not clock it
+        rank_extra["static_sam_derive_ms"] = dist_split["derive_ms"]
+    tokens_total, dt_max, per_rank = parallel.reduce_throughput(tokens, dt, extra=rank_extra)
+
+    def headline():
+        """the keys of the line that this run's timed region alone gives; a --full run adds the context after them"""
+        n_steps = sum(v[0] for v in stats.values())
+        n_tok = sum(v[1] for v in stats.values())
+        value = tokens_total / dt_max
+        return {
+            "metric": "tokens/sec (+ mean accepted tokens), Vicuna-7B bs=1, samd_sam_only draft+verify",
+            "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt_max / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f16" if dtype == torch.float16 else "bf16", "data": "synthetic: random-init Vicuna-7B-shaped weights (seed 0), seeded Markov corpus + request streams; "
+                                    + ("LM arg-max replaced after the full forward by each request's continuation stream"
+                                       if args.acceptance == "scripted" else "the random-init model's own arg-max"),
+            "config": {"workload": "BASELINE.json configs[1]: samd_sam_only, Vicuna-7B-v1.3 shape fp16, bs=1, max_predicts 60, alpha 4, "
+                                   f"len_bias 0, K 8; prompts 512 tokens, max_new_tokens 512, max_cache_len {max_len}",
+                       "model_shape": args.model, "layers": mcfg["num_hidden_layers"], "corpus_tokens": int(args.corpus_tokens),
+                       "static_sam_states": int(sam_info["n_states"]), "static_sam_bytes": int(sam_info["device_bytes"]),
+                       "static_sam_derived_bytes": derived_decode,
+                       "acceptance": args.acceptance, "variant": args.variant, "parallelism": f"request-parallel x{world} (replicas, no data-path collective)",
+                       "hipgraphs": not args.no_graphs, "v_cache_layout": "transposed" if getattr(runner, "v_transposed", False) else "rows"},
+            "mean_accepted_tokens": round(n_tok / max(n_steps, 1), 3),
+            "draft_steps": {k: {"steps": v[0], "mean_accept": round(v[1] / max(v[0], 1), 3)} for k, v in stats.items()},
+            "per_rank": [dict(r, ms_per_step=round(r["seconds"] / args.steps * 1e3, 4)) for r in per_rank], "bucket_histogram": bucket_hist,
+            # size of the all_gather that produced `value` (parallel.reduce_throughput): a SCALE record is checkable mechanically -- it must equal n_gpus
+            "rccl_ranks_seen": len(per_rank),
+            "timed_tokens": int(tokens_total), "session_kernel_phases": session_phases,
+            "full": bool(args.full), "dumped_outputs": dumped,
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # context, outside the timed region: a short timed window (the driver's 20 steps = ~46 tokens inside one request) samples the
     # accepted-token process with +-20 % noise; the same request stream continued for LONG_RUN_STEPS more steps gives the rate the
@@ -1157,28 +1252,9 @@ def main():
         auto.set_bigram_slots(0)
         cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(flat, off, docs, cfg, toks_walk)    # rank 0 at N = 1 only
 
-        n_steps = sum(v[0] for v in stats.values())
-        n_tok = sum(v[1] for v in stats.values())
         value = tokens_total / dt_max
-        out = {
-            "metric": "tokens/sec (+ mean accepted tokens), Vicuna-7B bs=1, samd_sam_only draft+verify",
-            "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt_max / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f16" if dtype == torch.float16 else "bf16", "data": "synthetic: random-init Vicuna-7B-shaped weights (seed 0), seeded Markov corpus + request streams; "
-                                    + ("LM arg-max replaced after the full forward by each request's continuation stream"
-                                       if args.acceptance == "scripted" else "the random-init model's own arg-max"),
-            "config": {"workload": "BASELINE.json configs[1]: samd_sam_only, Vicuna-7B-v1.3 shape fp16, bs=1, max_predicts 60, alpha 4, "
-                                   f"len_bias 0, K 8; prompts 512 tokens, max_new_tokens 512, max_cache_len {max_len}",
-                       "model_shape": args.model, "layers": mcfg["num_hidden_layers"], "corpus_tokens": int(args.corpus_tokens),
-                       "static_sam_states": int(sam_info["n_states"]), "static_sam_bytes": int(sam_info["device_bytes"]),
-                       "static_sam_derived_bytes": derived_decode,
-                       "acceptance": args.acceptance, "variant": args.variant, "parallelism": f"request-parallel x{world} (replicas, no data-path collective)",
-                       "hipgraphs": not args.no_graphs, "v_cache_layout": "transposed" if getattr(runner, "v_transposed", False) else "rows"},
-            "mean_accepted_tokens": round(n_tok / max(n_steps, 1), 3),
-            "draft_steps": {k: {"steps": v[0], "mean_accept": round(v[1] / max(v[0], 1), 3)} for k, v in stats.items()},
-            "per_rank": [dict(r, ms_per_step=round(r["seconds"] / args.steps * 1e3, 4)) for r in per_rank], "bucket_histogram": bucket_hist,
-            # size of the all_gather that produced `value` (parallel.reduce_throughput): a SCALE record is checkable mechanically -- it must equal n_gpus
-            "rccl_ranks_seen": len(per_rank),
+        out = headline()
+        out.update({
             # rank 0's timed region taken apart: request turnovers that fell into it (engine.start, clocked on the host), the decode steps
             # without them, and what the same steps cost as back-to-back graph replays of their row buckets (step_breakdown_by_rows) --
             # the difference is what the host adds between replays (report wait, bucket choice, launch)
@@ -1208,7 +1284,7 @@ def main():
                                % (TR_HOT_VOCAB, list(TR_RANK_P))) + ("; draft head planted with exactly that distribution (plant_order1_head)" if planted else "")
                               if order1 else None,
             "projected_speedup_of_this_variant": variant_projection(args.variant, ar_tps, dt_max / args.steps * 1e3),
-            "long_run": long_run, "timed_tokens": int(tokens_total), "session_kernel_phases": session_phases,
+            "long_run": long_run,
             # the category the north star's target is quoted on, as a workload (outside the timed region; see summarization_leg)
             "summarization": summ,
             "ar_tokens_per_s": round(ar_tps, 2), "speedup_vs_ar": round(value / world / ar_tps, 3),
@@ -1230,7 +1306,7 @@ def main():
                                "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(runner.weight_bytes() / (breakdown["8"]["step_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
                                "alg_bytes_per_step": int(runner.weight_bytes()), "step_ms": breakdown["8"]["step_ms"]} if "8" in breakdown else None),
             "setup": {"static_build_s": round(build_s, 2), "host": f"{os.cpu_count()} cores"},
-        }
+        })
         # LAST, so that the driver's stored tail keeps it: the claims of the line in one compact object
         def _sweep_frac(dist, tokens, slots):
             rows = (roof.get("corpus_sweep") or {}).get("rows") or []

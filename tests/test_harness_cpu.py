@@ -145,11 +145,14 @@ class _WordTokenizer:
         return R
 
 
-def test_chat_loop_commands(tmp_path):
+def test_chat_loop_commands(tmp_path, monkeypatch):
     from evaluation.chat import ChatSession, chat_loop, stream_answer
     model, tok = _EchoModel(), _WordTokenizer()
     out = []
-    save = str(tmp_path / "conv")
+    # a bare name in the working directory: `!!save` appends ".json" only to a name without a dot, and a dot anywhere in an
+    # absolute temporary path (a hidden parent directory) would count
+    monkeypatch.chdir(tmp_path)
+    save = "conv"
     script = iter(["hello there", "second question", "!!regen", "!!save " + save, "!!remove", "!!remove", "!!remove",
                    "!!load " + save, "!!load nowhere", "!!save", "!!reset", "after reset", "!!exit"])
     session = ChatSession("vicuna")
