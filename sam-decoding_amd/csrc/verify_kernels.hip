@@ -1234,7 +1234,8 @@ int samd_tree_attention(const void *d_q, const void *d_k_cache, const void *d_v_
 }
 
 static int att_direct_rows() {                 // SAMD_ATT_DIRECT_ROWS: the widest row bucket that takes the one-wave kernel over a transposed-V cache (0: none; A/B switch)
-    static const int rows = [] { const char *e = getenv("SAMD_ATT_DIRECT_ROWS"); return e ? atoi(e) : 16; }();
+    // clamped to [0, 64]: k_tree_attention_direct reads only the low mask word of a row, so a draft of 65..128 nodes must take the tiled kernel
+    static const int rows = [] { const char *e = getenv("SAMD_ATT_DIRECT_ROWS"); const int r = e ? atoi(e) : 16; return r < 0 ? 0 : (r > 64 ? 64 : r); }();
     return rows;
 }
 
