@@ -109,14 +109,16 @@ int samd_static_info(const samd_static_t *sam, int64_t out[8]);
  * (a power of two, >= 4 x the number of root-child edges by default: SAMD_BIGRAM_SLOTS_PER_PAIR / samd_static_set_bigram_slots); zeros for
  * what was not derived; out[4] = bytes, out[5] = slots of the EDGE TABLE of the branching states (round 5: one probe per transition out of a
  * state of degree >= 2, csrc/samd_common.h; sized like the bigram table).  These bytes are resident per GPU replica NEXT to
- * samd_static_info's device bytes (the image). */
+ * samd_static_info's device bytes (the image).  A handle has either edge blocks with the bigram table and no edge table, or no edge blocks
+ * with the edge table and the bigram table each present or not, or (after a failed derivation) none of these. */
 int samd_static_derived_info(const samd_static_t *sam, int64_t out[6]);
 /* round 6: the EDGE BLOCKS and HOT WORDS that replace the edge table when they fit (csrc/samd_common.h: per-state blocks of 16-byte slots
  * whose every slot carries the owning state's fail header -- a probe, hit or miss, is one request that also says where transfer_state's climb
  * (static_sam.py:99-101) goes next -- and one 16-byte hot word per state in place of node word 0): out[0] = bytes of the hot words, out[1] =
  * bytes of the blocks, out[2] = their slots, out[3] = states that own a block; zeros when the handle walks through the edge table instead
  * (SAMD_EDGE_BLOCKS=0, or something did not fit: samd_static_derived_info's out[4] / out[5] are then non-zero).  Resident per GPU replica
- * next to the image, like everything samd_static_derived_info reports. */
+ * next to the image, like everything samd_static_derived_info reports.  Blocks come only with the bigram table and never with the edge table;
+ * a failed derivation leaves none of the three. */
 int samd_static_edge_blocks_info(const samd_static_t *sam, int64_t out[4]);
 /* re-size the bigram table of an uploaded automaton: slots_per_pair in 2 .. 64 (0 = the default, 4).  A tuning entry with no reference
  * counterpart: a sparser table only helps the BATCHED walk (samd_static_walk* / samd_static_lookup_batch: 64 cursors in lock-step pay a

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <functional>
 #include <vector>
 #include <hipcub/hipcub.hpp>
 #include "sam_device.h"
@@ -22,7 +23,8 @@ static inline StaticDev static_view(const samd_static_t *s) {
     v.rc_bits = (const uint32_t *)s->d_rc_bits;
     v.ehash = (const uint4 *)s->d_ehash; v.edge_mask = s->n_ehash > 0 ? (uint32_t)(s->n_ehash - 1) : 0u;
     v.topk_cnt = (const int32_t *)s->d_topk_cnt;
-    v.hot = (const uint4 *)s->d_hot; v.blocks = s->d_hot ? (const uint4 *)s->d_blocks : nullptr; v.eb_tok_bits = samd_eb_tok_bits(s->vocab);
+    // the block path needs the bigram table (derive_walk_tables): without one the device sees no blocks
+    v.hot = s->d_d1hash ? (const uint4 *)s->d_hot : nullptr; v.blocks = s->d_d1hash ? (const uint4 *)s->d_blocks : nullptr; v.eb_tok_bits = samd_eb_tok_bits(s->vocab);
     return v;
 }
 
@@ -77,64 +79,7 @@ __global__ __launch_bounds__(256, 8) void k_static_walk(StaticDev S, const int32
     }
 }
 
-// ================================================================================================
-// the same walk with DECOUPLED LANES (sam_device.h, "Round 6, last"): every lane keeps its own token index; one trip of the loop = one
-// dependent round for the whole wave.  The lanes' tokens sit in LDS, 16 per lane at a time ([k][lane]: a lane reads only what it wrote, and the
-// bank follows the lane, so the per-lane index costs no conflict), next to the child bitmap.
-// ================================================================================================
-#define WALK_TCHUNK 16
-template <int W>
-__global__ __launch_bounds__(256, 8) void k_static_walk_async(StaticDev S, const int32_t *cursors, int32_t *cursors_out,
-                                                           const int32_t *__restrict__ tokens, int B, int T,
-                                                           int32_t *__restrict__ trace, unsigned long long *__restrict__ visited_total, int lds_words) {
-    extern __shared__ uint32_t walk_bits[];
-    const int tid = threadIdx.x, b = blockIdx.x * blockDim.x + tid;
-    const uint32_t *bits = S.rc_bits;
-    if (lds_words > 0) {
-        for (int k = tid; k < lds_words; k += blockDim.x) walk_bits[k] = S.rc_bits[k];
-        __syncthreads();
-        bits = walk_bits;
-    }
-    int32_t *tokbuf = reinterpret_cast<int32_t *>(walk_bits + lds_words);       // [WALK_TCHUNK][256]
-    const bool live = b < B;
-    WalkLane L;
-    L.idx = 0; L.len = 0; L.tok = 0; L.mode = WM_READY; L.a = 0; L.vtok = 0; L.ref = L.pos = L.probes = 0u; L.set_len = false;
-    L.cw = chain_none();
-    if (live) { const int2 c = reinterpret_cast<const int2 *>(cursors)[b]; L.idx = c.x; L.len = c.y; }
-    unsigned long long visited = 0;
-    for (int t0 = 0; t0 < T; t0 += WALK_TCHUNK) {
-        const int tn = live ? (T - t0 < WALK_TCHUNK ? T - t0 : WALK_TCHUNK) : 0;
-#pragma unroll
-        for (int k = 0; k < WALK_TCHUNK; k++) if (k < tn) tokbuf[k * 256 + tid] = tokens[(size_t)(t0 + k) * B + b];
-        int t = 0;
-        uint4 e = make_uint4(0u, 0u, 0u, 0u);
-        for (;;) {
-            bool done = false;
-            if (L.mode != WM_READY) done = wl_step<W>(S, bits, L, e);             // the pending load has landed
-            if (done) {
-                visited += (unsigned)L.vtok; L.cw.ptok = L.tok; L.mode = WM_READY;
-                if (trace) reinterpret_cast<int2 *>(trace)[(size_t)(t0 + t) * B + b] = make_int2(st_resolve(S, L.idx), L.len);
-                t++;
-            }
-            if (L.mode == WM_READY && t < tn) {                                   // a free lane starts its next token
-                L.tok = tokbuf[t * 256 + tid];
-                if (wl_start<W>(S, bits, L)) {
-                    visited += (unsigned)L.vtok; L.cw.ptok = L.tok;
-                    if (trace) reinterpret_cast<int2 *>(trace)[(size_t)(t0 + t) * B + b] = make_int2(st_resolve(S, L.idx), L.len);
-                    t++;
-                }
-            }
-            const bool pending = L.mode != WM_READY;
-            if (pending) e = *wl_addr(S, L);                                       // ONE load instruction per trip for the whole wave
-            if (!__any(pending || t < tn)) break;
-        }
-    }
-    if (live && cursors_out) reinterpret_cast<int2 *>(cursors_out)[b] = make_int2(st_resolve(S, L.idx), L.len);
-    if (visited_total) {
-        for (int o = 32; o > 0; o >>= 1) visited += __shfl_xor(visited, o);
-        if ((threadIdx.x & 63) == 0 && visited) atomicAdd(visited_total, visited);
-    }
-}
+// The same walk with decoupled lanes (k_static_walk_async) was built, measured slower and removed: profiles/r06_walk.md section 4b.
 
 // chain words from the node image: one thread per state (samd_common.h, CHAIN WORDS)
 template <int W>
@@ -482,31 +427,21 @@ int samd_device_info(int64_t out[4]) {
     return SAMD_OK;
 }
 
-// SAMD_WALK_CHAIN=0 (read once) keeps every transition on the nodes: the A/B switch of profiles/r02_walk_pmc.md
 static void launch_walk(const samd_static_t *sam, int blocks, int threads, hipStream_t st, const int32_t *d_cursors, int32_t *d_out, const int32_t *d_tokens, int B, int T,
                         int32_t *d_trace, unsigned long long *d_visited) {
-    static const bool use_chain = [] { const char *e = getenv("SAMD_WALK_CHAIN"); return !(e && e[0] == '0'); }();
-    // the decoupled-lane form (k_static_walk_async) is an experiment, OFF by default: -39 % load instructions, +39 % vector instructions, 0.335 vs
-    // 0.301 ms on the Zipfian corpus, 0.171 vs 0.151 on the headline one (profiles/r06_walk.md section 4b).  Read per launch: tests run both forms.
-    const char *env_async = getenv("SAMD_WALK_ASYNC");
-    const bool use_async = env_async && env_async[0] == '1';
     const StaticDev v = static_view(sam);
-    // the child bitmap rides in LDS when it is small enough to leave the occupancy alone (8 workgroups of 256 per CU: 160 KiB / 8)
+    // PATH (k_static_walk): no chain words = the nodes only; edge blocks (which static_view shows only with the bigram table) = their path
+    const int path = !v.chain ? 0 : (v.blocks ? 2 : 1);
+    // the child bitmap rides in LDS when it is small enough to leave the occupancy alone (8 workgroups of 256 per CU: 160 KiB / 8); the
+    // node-only walk reads none
     const int bit_words = v.rc_bits ? (int)((v.vocab + 31) / 32) : 0;
-    const int lds_words = bit_words * 4 <= 20480 ? bit_words : 0;
-    if (!use_chain || !v.chain) hipLaunchKernelGGL((k_static_walk<8, 0>), dim3(blocks), dim3(threads), 0, st, v, d_cursors, d_out, d_tokens, B, T, d_trace, d_visited, 0);
-    else if (v.blocks && v.bigram && use_async && threads == 256) {
-        // decoupled lanes (k_static_walk_async): the lanes' tokens ride in LDS beside the child bitmap (16 KiB + <= 4 KiB: 8 workgroups per CU);
-        // a bitmap too large for that stays in memory
-        const int lw = (size_t)lds_words * 4 + WALK_TCHUNK * 256 * 4 <= 20480 ? lds_words : 0;
-        const size_t lds = (size_t)lw * 4 + WALK_TCHUNK * 256 * 4;
-        if (v.chain_w == 8) hipLaunchKernelGGL((k_static_walk_async<8>), dim3(blocks), dim3(threads), lds, st, v, d_cursors, d_out, d_tokens, B, T, d_trace, d_visited, lw);
-        else hipLaunchKernelGGL((k_static_walk_async<4>), dim3(blocks), dim3(threads), lds, st, v, d_cursors, d_out, d_tokens, B, T, d_trace, d_visited, lw);
-    }
-    else if (v.blocks && v.bigram && v.chain_w == 8) hipLaunchKernelGGL((k_static_walk<8, 2>), dim3(blocks), dim3(threads), (size_t)lds_words * 4, st, v, d_cursors, d_out, d_tokens, B, T, d_trace, d_visited, lds_words);
-    else if (v.blocks && v.bigram) hipLaunchKernelGGL((k_static_walk<4, 2>), dim3(blocks), dim3(threads), (size_t)lds_words * 4, st, v, d_cursors, d_out, d_tokens, B, T, d_trace, d_visited, lds_words);
-    else if (v.chain_w == 8) hipLaunchKernelGGL((k_static_walk<8, 1>), dim3(blocks), dim3(threads), (size_t)lds_words * 4, st, v, d_cursors, d_out, d_tokens, B, T, d_trace, d_visited, lds_words);
-    else hipLaunchKernelGGL((k_static_walk<4, 1>), dim3(blocks), dim3(threads), (size_t)lds_words * 4, st, v, d_cursors, d_out, d_tokens, B, T, d_trace, d_visited, lds_words);
+    const int lds_words = path != 0 && bit_words * 4 <= 20480 ? bit_words : 0;
+#define WALK(W, PATH) hipLaunchKernelGGL((k_static_walk<W, PATH>), dim3(blocks), dim3(threads), (size_t)lds_words * 4, st, v, d_cursors, d_out, d_tokens, B, T, d_trace, d_visited, lds_words)
+    const bool w8 = v.chain_w == 8;
+    if (path == 0) WALK(8, 0);                                 // (W plays no part without chain words)
+    else if (path == 1) { if (w8) WALK(8, 1); else WALK(4, 1); }
+    else { if (w8) WALK(8, 2); else WALK(4, 2); }
+#undef WALK
 }
 
 // bigram table (samd_common.h): count the root children's edges, then fill.  One thread per vocabulary id.
@@ -720,51 +655,81 @@ static long long table_budget_bytes() {
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) { if ((long long)(free_b / 8) < budget) budget = (long long)(free_b / 8); } else (void)hipGetLastError();
     return budget;
 }
+// slots per entry of both hash tables.  A lock-step wave of the BATCHED walk pays a second probe round whenever ANY of its 64 lanes collides, so
+// that launch likes a very sparse table -- measured on the bench automaton (4.5 M pairs, same box): >= 2 x pairs 0.188 ms per launch, 4 x 0.176,
+// 8 x 0.170, 16 x 0.166 (2 GB).  The product path (st_transfer_tokens: ONE cursor, uniform addresses) gains nothing from the sparsity, and the
+// tables are per GPU replica next to weights and KV cache, so the DEFAULT is 4 (round 5; rounds 3-4: 16) and a caller that runs the batched walk
+// asks for more: samd_static_set_bigram_slots() / SAMD_BIGRAM_SLOTS_PER_PAIR (2 .. 64).
 static int table_slots_per_entry(int arg) {
     static const int per_env = [] { const char *e = getenv("SAMD_BIGRAM_SLOTS_PER_PAIR"); const int v = e ? atoi(e) : 4; return v < 2 ? 2 : (v > 64 ? 64 : v); }();
     return arg > 0 ? (arg < 2 ? 2 : (arg > 64 ? 64 : arg)) : per_env;
 }
 
-// the edge table of the branching states; sized and budgeted like the bigram table (slots per entry: the same knob).  An accelerator: when
-// the device cannot spare it the walks go through the nodes as before.  SAMD_EDGE_TABLE=0 switches it off (A/B).
-static int derive_edge_hash(samd_static_t *s, hipStream_t st, int per_arg) {
-    const char *env = getenv("SAMD_EDGE_TABLE");                      // read at every derivation: tests upload the same automaton both ways
-    const bool enabled = !(env && env[0] == '0');
-    if (s->d_ehash) { (void)hipFree(s->d_ehash); s->d_ehash = nullptr; }
-    s->n_ehash = 0;
-    if (!enabled || !s->d_chain || s->n_states < 2) return SAMD_OK;
-    const long long n = (long long)s->n_states;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    unsigned long long *d_total = nullptr, total = 0;
-    if (hipMalloc((void **)&d_total, 8) != hipSuccess) { (void)hipGetLastError(); return SAMD_OK; }
+// frees every derived walk table of the handle: hot words, edge blocks, the edge table, the bigram table, root entries and child bitmap
+static void drop_walk_tables(samd_static_t *s) {
+    for (void **p : {&s->d_hot, &s->d_blocks, &s->d_ehash, &s->d_d1hash, &s->d_root16, &s->d_rc_bits}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    s->n_block_slots = s->n_block_states = s->n_ehash = s->n_d1hash = 0;
+}
+
+// a count on the device: `launch(d_total)` adds into one zeroed u64, which is read back; blocking.  SAMD_E_CAPACITY: no memory for the counter.
+static int device_count(hipStream_t st, unsigned long long &total, const std::function<void(unsigned long long *)> &launch) {
+    unsigned long long *d_total = nullptr;
+    total = 0;
+    if (hipMalloc((void **)&d_total, 8) != hipSuccess) { (void)hipGetLastError(); return SAMD_E_CAPACITY; }
     int rc = SAMD_OK;
     if (hipMemsetAsync(d_total, 0, 8, st) != hipSuccess) rc = SAMD_E_HIP;
     if (rc == SAMD_OK) {
-        hipLaunchKernelGGL(k_eh_count, dim3(blocks), dim3(256), 0, st, s->d_nodes, n, d_total);
+        launch(d_total);
         if (hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = SAMD_E_HIP;
     }
     (void)hipFree(d_total);
-    if (rc != SAMD_OK) { samd_set_error("edge table derivation failed"); return rc; }
-    if (total == 0) return SAMD_OK;
+    return rc;
+}
+
+// *out = a hash table of 16-byte slots for `entries` keys; returns its slots (a power of two), 0 = go without.  table_slots_per_entry(per_arg)
+// slots per key, at least 1024; halved while over table_budget_bytes() (8 GB, an eighth of the free device memory) as long as 2 per key remain,
+// and halved again, down to the same floor, while hipMalloc fails.  A table still over the budget after that: the edge table goes without
+// (over_budget_ok = false), the bigram table is allocated anyway (true).
+static long long alloc_table(void **out, unsigned long long entries, int per_arg, bool over_budget_ok) {
     const int per = table_slots_per_entry(per_arg);
     const long long budget = table_budget_bytes();
     long long slots = 1024;
-    while (slots < per * (long long)total) slots <<= 1;
-    while (slots * 16 > budget && slots >= 4 * (long long)total) slots >>= 1;
-    if (slots > (1ll << 31) || slots * 16 > budget) return SAMD_OK;                     // does not fit: go without
-    while (hipMalloc(&s->d_ehash, (size_t)slots * 16) != hipSuccess) {
-        s->d_ehash = nullptr; (void)hipGetLastError();
-        if (slots < 4 * (long long)total || slots <= 1024) return SAMD_OK;
+    while (slots < per * (long long)entries) slots <<= 1;                          // load factor in (1 / 2 per, 1 / per]
+    while (slots * 16 > budget && slots >= 4 * (long long)entries) slots >>= 1;
+    if (slots > (1ll << 31) || (!over_budget_ok && slots * 16 > budget)) return 0;  // (beyond 2^31 the mask does not fit 32 bits)
+    while (hipMalloc(out, (size_t)slots * 16) != hipSuccess) {
+        *out = nullptr; (void)hipGetLastError();
+        if (slots < 4 * (long long)entries || slots <= 1024) return 0;
         slots >>= 1;
     }
+    return slots;
+}
+
+// the edge table of the branching states; sized and budgeted like the bigram table (alloc_table).  An accelerator: when the device cannot spare
+// it the walks go through the nodes as before.  SAMD_EDGE_TABLE=0 switches it off (A/B).
+static int derive_edge_hash(samd_static_t *s, hipStream_t st, int per_arg) {
+    const char *env = getenv("SAMD_EDGE_TABLE");                      // read at every derivation: tests upload the same automaton both ways
+    if ((env && env[0] == '0') || !s->d_chain || s->n_states < 2) return SAMD_OK;
+    const long long n = (long long)s->n_states;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    unsigned long long total = 0;
+    int rc = device_count(st, total, [&](unsigned long long *d_total) { hipLaunchKernelGGL(k_eh_count, dim3(blocks), dim3(256), 0, st, s->d_nodes, n, d_total); });
+    if (rc == SAMD_E_CAPACITY) return SAMD_OK;
+    if (rc != SAMD_OK) { samd_set_error("edge table derivation failed"); return rc; }
+    if (total == 0) return SAMD_OK;
+    const long long slots = alloc_table(&s->d_ehash, total, per_arg, false);
+    if (!slots) return SAMD_OK;
+    s->n_ehash = slots;
     if (hipMemsetAsync(s->d_ehash, 0xFF, (size_t)slots * 16, st) != hipSuccess) rc = SAMD_E_HIP;
     if (rc == SAMD_OK) {
         hipLaunchKernelGGL(k_eh_fill, dim3(blocks), dim3(256), 0, st, s->d_nodes, s->d_spill, n, (const uint4 *)s->d_chain, (uint4 *)s->d_ehash, (uint32_t)(slots - 1));
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = SAMD_E_HIP;
     }
-    if (rc != SAMD_OK) { (void)hipFree(s->d_ehash); s->d_ehash = nullptr; samd_set_error("edge table derivation failed"); return rc; }
-    s->n_ehash = slots;
-    return SAMD_OK;
+    if (rc != SAMD_OK) samd_set_error("edge table derivation failed");
+    return rc;
 }
 
 // hot words + edge blocks (samd_common.h, round 6).  On success *out_bref = the per-state block references (device, owned by the caller: the
@@ -774,9 +739,6 @@ static int derive_edge_hash(samd_static_t *s, hipStream_t st, int per_arg) {
 static int derive_edge_blocks(samd_static_t *s, hipStream_t st, int per_arg, uint32_t **out_bref) {
     *out_bref = nullptr;
     const char *env = getenv("SAMD_EDGE_BLOCKS");                     // read at every derivation: tests upload the same automaton every way
-    if (s->d_hot) { (void)hipFree(s->d_hot); s->d_hot = nullptr; }
-    if (s->d_blocks) { (void)hipFree(s->d_blocks); s->d_blocks = nullptr; }
-    s->n_block_slots = s->n_block_states = 0;
     const long long n = (long long)s->n_states;
     const int tok_bits = samd_eb_tok_bits(s->vocab);
     if ((env && env[0] == '0') || !s->d_chain || n < 2 || n > (long long)SAMD_EB_IDX_MASK || tok_bits > 24 || s->vocab < 1 || s->vocab > (1 << 24)) return SAMD_OK;
@@ -814,10 +776,7 @@ static int derive_edge_blocks(samd_static_t *s, hipStream_t st, int per_arg, uin
     hipLaunchKernelGGL(k_eb_rctok, dim3((unsigned)((s->vocab + 255) / 256)), dim3(256), 0, st, s->d_root, (int)s->vocab, d_rctok);
     if (hipMalloc(&d_hot, (size_t)n * 16) != hipSuccess || hipMalloc(&d_blk, (size_t)(total[0] ? total[0] : 1) * 16) != hipSuccess) return none();
     hipLaunchKernelGGL(k_eb_fill, dim3(blocks), dim3(256), 0, st, s->d_nodes, s->d_spill, n, (const uint4 *)s->d_chain, d_bref, d_rctok, tok_bits, (uint4 *)d_hot, (uint4 *)d_blk);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); cleanup(false); (void)hipFree(d_hot); (void)hipFree(d_blk);
-        samd_set_error("edge block derivation failed"); return SAMD_E_HIP;
-    }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { none(); samd_set_error("edge block derivation failed"); return SAMD_E_HIP; }
     s->d_hot = d_hot; s->d_blocks = d_blk; s->n_block_slots = (int64_t)total[0]; s->n_block_states = (int64_t)total[1];
     cleanup(true);
     *out_bref = d_bref;
@@ -825,8 +784,7 @@ static int derive_edge_blocks(samd_static_t *s, hipStream_t st, int per_arg, uin
 }
 
 static int derive_topk_counts(samd_static_t *s, hipStream_t st) {
-    static const bool enabled = [] { const char *e = getenv("SAMD_TOPK_COUNTS"); return !(e && e[0] == '0'); }();       // A/B switch, read once
-    if (!enabled || s->kind != SAMD_KIND_COUNT) return SAMD_OK;
+    if (s->kind != SAMD_KIND_COUNT) return SAMD_OK;
     const long long n = (long long)s->n_states * SAMD_TOPK;
     if (!s->d_topk_cnt && hipMalloc(&s->d_topk_cnt, (size_t)n * 4) != hipSuccess) { s->d_topk_cnt = nullptr; samd_set_error("hipMalloc(top-k counts) failed"); return SAMD_E_HIP; }
     hipLaunchKernelGGL(k_topk_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->d_nodes, s->d_spill, (long long)s->n_states, (int32_t *)s->d_topk_cnt);
@@ -834,83 +792,54 @@ static int derive_topk_counts(samd_static_t *s, hipStream_t st) {
     return SAMD_OK;
 }
 
-static int derive_root_hash(samd_static_t *s, hipStream_t st, int per_pair_arg = 0, const uint32_t *d_bref = nullptr) {
-    static const bool enabled = [] { const char *e = getenv("SAMD_ROOT_HASH"); return !(e && e[0] == '0'); }();      // A/B switch, read once
-    if (s->d_root16) { (void)hipFree(s->d_root16); s->d_root16 = nullptr; }
-    if (s->d_d1hash) { (void)hipFree(s->d_d1hash); s->d_d1hash = nullptr; }
-    if (s->d_rc_bits) { (void)hipFree(s->d_rc_bits); s->d_rc_bits = nullptr; }
-    s->n_d1hash = 0;
-    if (!enabled || s->vocab < 1 || s->vocab > (1 << 24) || !s->d_chain) return SAMD_OK;
+// the bigram table with its root entries and child bitmap, all three or none.  d_bref: derive_edge_blocks' block references, when the handle
+// has blocks.  An accelerator, not part of the image: when the device cannot spare it the walks resolve root children through their nodes.
+static int derive_root_hash(samd_static_t *s, hipStream_t st, int per_arg, const uint32_t *d_bref) {
+    if (s->vocab < 1 || s->vocab > (1 << 24) || !s->d_chain) return SAMD_OK;
     const int vocab = (int)s->vocab;
     const unsigned blocks = (unsigned)((vocab + 255) / 256);
-    unsigned long long *d_total = nullptr, total = 0;
-    int rc = SAMD_OK;
-    if (hipMalloc((void **)&d_total, 8) != hipSuccess) { samd_set_error("hipMalloc(bigram count) failed"); return SAMD_E_HIP; }
-    if (hipMemsetAsync(d_total, 0, 8, st) != hipSuccess) rc = SAMD_E_HIP;
-    if (rc == SAMD_OK) {
-        hipLaunchKernelGGL(k_bg_count, dim3(blocks), dim3(256), 0, st, s->d_nodes, s->d_root, vocab, d_total);
-        if (hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = SAMD_E_HIP;
-    }
-    (void)hipFree(d_total);
-    // slots per pair: a lock-step wave of the BATCHED walk pays a second probe round whenever ANY of its 64 lanes collides, so that launch
-    // likes a very sparse table -- measured on the bench automaton (4.5 M pairs, same box): >= 2 x pairs 0.188 ms per launch, 4 x 0.176,
-    // 8 x 0.170, 16 x 0.166 (2 GB).  The product path (st_transfer_tokens: ONE cursor, uniform addresses) gains nothing from the sparsity, and
-    // the table is per GPU replica next to weights and KV cache, so the DEFAULT is 4 slots per pair (round 5; rounds 3-4: 16) and a caller that
-    // runs the batched walk asks for more: samd_static_set_bigram_slots() / SAMD_BIGRAM_SLOTS_PER_PAIR (2 .. 64).  Whatever is asked for, the
-    // table stays under 8 GB and under an eighth of the device memory free right now, as long as 2 x pairs fit in that.
-    static const int per_pair_env = [] { const char *e = getenv("SAMD_BIGRAM_SLOTS_PER_PAIR"); const int v = e ? atoi(e) : 4; return v < 2 ? 2 : (v > 64 ? 64 : v); }();
-    const int per_pair = per_pair_arg > 0 ? (per_pair_arg < 2 ? 2 : (per_pair_arg > 64 ? 64 : per_pair_arg)) : per_pair_env;
-    long long budget = 8ll << 30;
-    { size_t free_b = 0, total_b = 0; if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (long long)(free_b / 8) < budget) budget = (long long)(free_b / 8); else (void)hipGetLastError(); }
-    long long slots = 1024;
-    while (slots < per_pair * (long long)total) slots <<= 1;                       // load factor in (1 / 2 per_pair, 1 / per_pair]
-    while (slots * 16 > budget && slots >= 4 * (long long)total) slots >>= 1;
-    if (rc == SAMD_OK && slots > (1ll << 31)) rc = -1;                            // the mask does not fit 32 bits: go without the table
+    unsigned long long total = 0;
+    int rc = device_count(st, total, [&](unsigned long long *d_total) { hipLaunchKernelGGL(k_bg_count, dim3(blocks), dim3(256), 0, st, s->d_nodes, s->d_root, vocab, d_total); });
+    if (rc == SAMD_E_CAPACITY) { samd_set_error("hipMalloc(bigram count) failed"); return SAMD_E_HIP; }
+    if (rc != SAMD_OK) { samd_set_error("bigram table derivation failed"); return rc; }
+    void *table = nullptr, *root16 = nullptr, *bits = nullptr;
     const size_t bit_bytes = (size_t)((vocab + 31) / 32) * 4;
+    const long long slots = alloc_table(&table, total, per_arg, true);
+    if (!slots) return SAMD_OK;
+    if (hipMalloc(&root16, (size_t)vocab * 16) != hipSuccess || hipMalloc(&bits, bit_bytes) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(table); if (root16) (void)hipFree(root16);
+        return SAMD_OK;
+    }
+    s->d_d1hash = table; s->n_d1hash = slots; s->d_root16 = root16; s->d_rc_bits = bits;
+    if (hipMemsetAsync(table, 0xFF, (size_t)slots * 16, st) != hipSuccess || hipMemsetAsync(bits, 0, bit_bytes, st) != hipSuccess) rc = SAMD_E_HIP;
     if (rc == SAMD_OK) {
-        // the table is an accelerator, not part of the image: when the device cannot spare its preferred size, halve it down to 2 slots per pair,
-        // and when even that does not fit go without it (walks then resolve root children through their nodes)
-        while (hipMalloc(&s->d_d1hash, (size_t)slots * 16) != hipSuccess) {
-            s->d_d1hash = nullptr; (void)hipGetLastError();
-            if (slots < 4 * (long long)total || slots <= 1024) { rc = -1; break; }
-            slots >>= 1;
-        }
-        if (rc == SAMD_OK && (hipMalloc(&s->d_root16, (size_t)vocab * 16) != hipSuccess || hipMalloc(&s->d_rc_bits, bit_bytes) != hipSuccess)) { (void)hipGetLastError(); rc = -1; }
-        if (rc == SAMD_OK && (hipMemsetAsync(s->d_d1hash, 0xFF, (size_t)slots * 16, st) != hipSuccess || hipMemsetAsync(s->d_rc_bits, 0, bit_bytes, st) != hipSuccess)) rc = SAMD_E_HIP;
-        if (rc == SAMD_OK) {
-            hipLaunchKernelGGL(k_bg_fill, dim3(blocks), dim3(256), 0, st, s->d_nodes, s->d_spill, s->d_root, vocab, (const uint4 *)s->d_chain, (uint4 *)s->d_root16,
-                               (uint4 *)s->d_d1hash, (uint32_t)(slots - 1), (uint32_t *)s->d_rc_bits, samd_chain_w(vocab), s->d_ehash ? 1 : 0, d_bref);
-            // (only the block path reads the bit, and only a handle with blocks may carry it: the edge-table path takes the dst word's low 31 bits as the index)
-            if (d_bref) hipLaunchKernelGGL(k_bg_displaced, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (uint4 *)s->d_d1hash, (uint32_t)(slots - 1), samd_chain_w(vocab));
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = SAMD_E_HIP;
-        }
-        if (rc == SAMD_OK) s->n_d1hash = slots;
+        hipLaunchKernelGGL(k_bg_fill, dim3(blocks), dim3(256), 0, st, s->d_nodes, s->d_spill, s->d_root, vocab, (const uint4 *)s->d_chain, (uint4 *)root16,
+                           (uint4 *)table, (uint32_t)(slots - 1), (uint32_t *)bits, samd_chain_w(vocab), s->d_ehash ? 1 : 0, d_bref);
+        // (only the block path reads the bit, and only a handle with blocks may carry it: the edge-table path takes the dst word's low 31 bits as the index)
+        if (d_bref) hipLaunchKernelGGL(k_bg_displaced, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (uint4 *)table, (uint32_t)(slots - 1), samd_chain_w(vocab));
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = SAMD_E_HIP;
     }
-    if (rc != SAMD_OK) {
-        if (s->d_root16) { (void)hipFree(s->d_root16); s->d_root16 = nullptr; }
-        if (s->d_d1hash) { (void)hipFree(s->d_d1hash); s->d_d1hash = nullptr; }
-        if (s->d_rc_bits) { (void)hipFree(s->d_rc_bits); s->d_rc_bits = nullptr; }
-        s->n_d1hash = 0;
-        if (rc == SAMD_E_HIP) { samd_set_error("bigram table derivation failed"); return rc; }
-    }
-    return SAMD_OK;
+    if (rc != SAMD_OK) samd_set_error("bigram table derivation failed");
+    return rc;
 }
 
 // the derived walk tables in the order they depend on each other: edge blocks (+ hot words) when they fit, else the edge table; then the
 // bigram table, whose entries name a target's block.  The block path needs the bigram table: without one the blocks go and the edge table
-// (which does not) comes back.
+// (which does not) comes back.  The handle ends in one of three states: (a) blocks + hot words + the bigram table, no edge table; (b) no
+// blocks, the edge table and the bigram table each present or not; (c) no derived walk tables -- after any error.
 static int derive_walk_tables(samd_static_t *s, hipStream_t st, int per_arg) {
+    drop_walk_tables(s);
     uint32_t *d_bref = nullptr;
     int rc = derive_edge_blocks(s, st, per_arg, &d_bref);
     if (rc == SAMD_OK && !s->d_blocks) rc = derive_edge_hash(s, st, per_arg);
-    else if (rc == SAMD_OK && s->d_ehash) { (void)hipFree(s->d_ehash); s->d_ehash = nullptr; s->n_ehash = 0; }
     if (rc == SAMD_OK) rc = derive_root_hash(s, st, per_arg, d_bref);
     if (d_bref) (void)hipFree(d_bref);
     if (rc == SAMD_OK && s->d_blocks && !s->d_d1hash) {
-        (void)hipFree(s->d_hot); (void)hipFree(s->d_blocks); s->d_hot = s->d_blocks = nullptr; s->n_block_slots = s->n_block_states = 0;
+        drop_walk_tables(s);
         rc = derive_edge_hash(s, st, per_arg);
         if (rc == SAMD_OK) rc = derive_root_hash(s, st, per_arg, nullptr);
     }
+    if (rc != SAMD_OK) drop_walk_tables(s);
     return rc;
 }
 

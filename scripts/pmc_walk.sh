@@ -1,7 +1,6 @@
 #!/bin/bash
 # PMC + trace passes for the SAM traversal kernel at bench.py's roofline configuration (run on the GPU box):
-#   scripts/pmc_walk.sh [tag]        tag = output sub-directory under gpurun_out/ (default pmc_r2); SAMD_WALK_CHAIN=0 in the
-#                                    environment profiles the node-only variant (the A/B of profiles/r02_walk_pmc.md)
+#   scripts/pmc_walk.sh [tag]        tag = name of the output sub-directory (default pmc_r2)
 # Counters are collected in their own runs (never together with --sys-trace etc.); FETCH_SIZE and WRITE_SIZE in separate passes.
 # The summary (walk_summary.json) is what profiles/walk_pmc.json -- bench.py's `roofline.traffic` -- is refreshed from.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
