@@ -616,6 +616,17 @@ int samd_gemm_skinny(const void *d_A, const void *d_W, int32_t rows_pad, int32_t
  * forward (-4 GB of a 7B replica).  Results are bit-identical to samd_gemm_skinny's. */
 int samd_gemm_skinny_groups(const void *d_A, const void *d_Wg, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial,
                             void *d_out, int32_t dtype, void *stream);
+/* FP8 weight-only projections (OCP e4m3fn weights, one fp32 scale per output column):
+ *   samd_gemm_pack_f8     row-major [N][K] e4m3fn bytes -> the packed 32 KiB (128-column tile, 256-k chunk) blocks samd_gemm_skinny_f8 streams;
+ *                         N % 128 == 0, K % 256 == 0, distinct buffers of N * K bytes.
+ *   samd_gemm_skinny_f8   out[m][n] = scale[n] * sum_k A[m][k] * q[n][k]: A in the model dtype (dtype), q as packed, fp32 accumulation, the column
+ *                         scale applied to the fp32 sum.  splits == 1: d_out [rows_pad][N] in the model dtype (one rounding); otherwise fp32
+ *                         partials [splits][rows_pad][N] in d_partial, already scaled -- the layout of samd_gemm_skinny, so the consumers that take
+ *                         its partials (samd_rmsnorm_warm, samd_rope_kv_write_cs(_vt), samd_silu_mul) take these unchanged.  Arguments as
+ *                         samd_gemm_skinny's (rows 16/32/48/64, N % 128, K % 256, 1 <= splits <= K / 256) plus a non-null d_scale [N]. */
+int samd_gemm_pack_f8(const void *d_W8, void *d_out, int32_t N, int32_t K, void *stream);
+int samd_gemm_skinny_f8(const void *d_A, const void *d_W8p, const float *d_scale, int32_t rows_pad, int32_t N, int32_t K, int32_t splits,
+                        float *d_partial, void *d_out, int32_t dtype, void *stream);
 
 /* ---- scripted verifier (tests, smoke and bench only): replaces the LM arg-max of every draft node by
  * the next token of a target stream while the node's context (committed history + root->node path) is a

@@ -1187,3 +1187,205 @@ int samd_gemm_skinny_groups(const void *d_A, const void *d_Wg, int32_t rows_pad,
 }
 
 }  // extern "C"
+
+// ================================================================================================
+// FP8 (OCP e4m3fn) weight-only projection: out[m][n] = scale[n] * sum_k A[m][k] * q[n][k], A in the model dtype, q one byte per weight,
+// scale fp32 per output column (per output row of the HF weight).  Same grid, A staging, k permutation and MFMA sequence as k_gemm_skinny;
+// only the weight load and a conversion differ, so the stream moves half the bytes.
+//   PACKED LAYOUT (samd_gemm_pack_f8): block (tile t = 128 columns, chunk c = 256 k) is 32 KiB contiguous at ((t * K/256 + c) * 2048) uint4
+//   units; unit b * 512 + tid holds q[128 t + 16 w + n][256 c + 64 b + 16 g .. +15] for tid = 64 w + 16 g + n -- in one 16-byte load the two
+//   8-element vectors (j = 0, 1) that k_gemm_skinny loads separately.
+// The bytes are widened in registers by v_cvt_scalef32_pk_{f16,bf16}_fp8 with scale 1: every e4m3fn value is exact in fp16 and in bf16, so
+// the MFMA sees the weights without error; the column scale is applied to the fp32 sums in the epilogue (one multiply per accumulator).
+// DEPTH: 4 chunks of 32 KiB in flight = the fp16 kernel's 128 KiB per workgroup and its 64 weight VGPRs; at 64 rows DEPTH + 1 = 5 A buffers
+// would take the whole 160 KiB of LDS, so that tile keeps 3 chunks in flight (4 buffers, 128 KiB).
+// ================================================================================================
+template <typename TT> struct F8Widen;
+template <> struct F8Widen<GF16> {
+    static __device__ __forceinline__ half8 cvt(unsigned w0, unsigned w1) {
+        const auto a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true);
+        const auto c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false), d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true);
+        return __builtin_bit_cast(half8, (u32x4){__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d)});
+    }
+};
+template <> struct F8Widen<GBF16> {
+    static __device__ __forceinline__ bf16x8 cvt(unsigned w0, unsigned w1) {
+        const auto a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true);
+        const auto c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true);
+        return __builtin_bit_cast(bf16x8, (u32x4){__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d)});
+    }
+};
+
+template <typename TT, int RT, int DEPTH>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_f8(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8,
+                                                                     const float *__restrict__ scale, float *__restrict__ partial,
+                                                                     typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int n_splits) {
+    typedef typename TT::elem E;
+    constexpr int R = 16 * RT;
+    constexpr int NT = 64 * GEMM_WAVES;
+    constexpr int XV = (R * 32) / NT;              // 16-byte units per thread to stage one A chunk (as k_gemm_skinny)
+    constexpr int NB = DEPTH + 1;
+    constexpr int PC = 4 + XV;                     // memory operations per thread and chunk: 4 weight loads + the A staging
+    constexpr size_t WCH = 32768, WU = 8192;       // bytes of one (tile, chunk) block; of one b row inside it
+    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
+    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
+
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
+    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    const int split = blockIdx.y;
+    const int c0 = (int)((long long)split * n_chunks / n_splits), c1 = (int)((long long)(split + 1) * n_chunks / n_splits);
+    const char *wtile = reinterpret_cast<const char *>(W8) + (size_t)blockIdx.x * n_chunks * WCH;
+    const uint32_t wlane = (uint32_t)tid * 16;
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
+    const float sc = scale[n0 + n];                // this lane's column; requested before the stream, used in the epilogue
+
+    floatx4 acc[RT];
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+
+    // hand-issued nt weight loads, counted waits and bare barriers: see k_gemm_skinny
+    u32x4 wr[DEPTH][4];
+    auto load_wb = [&](u32x4 (&dst)[4], int c, int b) {
+        const char *p = wtile + (size_t)c * WCH;
+        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(dst[b]) : "v"(wlane), "s"(p + WU * b) : "memory");
+    };
+    auto stage_xi = [&](int c, int buf, int i) {
+        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
+        const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
+        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        asm volatile("" ::: "memory");
+    };
+    auto load_w = [&](u32x4 (&dst)[4], int c) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) load_wb(dst, c, b);
+    };
+    auto stage_x = [&](int c, int buf) {
+#pragma unroll
+        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
+    };
+    auto phase = [&](u32x4 (&cur)[4], int c, int buf) {
+        gemm_wait_younger<DEPTH, PC>(c1 - 1 - c);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
+            u32x4 r[RT][2];
+            if constexpr (RT == 1)
+                asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r[0][0]), "=&v"(r[0][1]) : "v"(a0), "v"(a1));
+            else if constexpr (RT == 2)
+                asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %4 offset:8192\n\tds_read_b128 %3, %5 offset:8192\n\t"
+                             "s_waitcnt lgkmcnt(0)" : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]) : "v"(a0), "v"(a1));
+            else if constexpr (RT == 3)
+                asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %7\n\tds_read_b128 %2, %6 offset:8192\n\tds_read_b128 %3, %7 offset:8192\n\t"
+                             "ds_read_b128 %4, %6 offset:16384\n\tds_read_b128 %5, %7 offset:16384\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[2][0]), "=&v"(r[2][1]) : "v"(a0), "v"(a1));
+            else
+                asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %8 offset:8192\n\tds_read_b128 %3, %9 offset:8192\n\t"
+                             "ds_read_b128 %4, %8 offset:16384\n\tds_read_b128 %5, %9 offset:16384\n\tds_read_b128 %6, %8 offset:24576\n\t"
+                             "ds_read_b128 %7, %9 offset:24576\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[2][0]), "=&v"(r[2][1]), "=&v"(r[3][0]), "=&v"(r[3][1])
+                             : "v"(a0), "v"(a1));
+            // the conversion is ordinary VALU code on the loaded registers: re-define them here, behind the counted wait (volatile asm keeps its
+            // order), so that no conversion can be scheduled above the wait while the load is still in flight
+            asm volatile("" : "+v"(cur[b]) : : "memory");
+            const auto lo = F8Widen<TT>::cvt(cur[b][0], cur[b][1]), hi = F8Widen<TT>::cvt(cur[b][2], cur[b][3]);
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++) {
+                acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
+                acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, acc[mt]);
+            }
+            if (RT >= 3 && c + DEPTH < c1) {       // 48 / 64 rows: refill per k block (see k_gemm_skinny)
+                load_wb(cur, c + DEPTH, b);
+                if (b < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, b);
+            }
+        }
+        if (RT < 3 && c + DEPTH < c1) { load_w(cur, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
+    };
+    if (c0 < c1) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++)
+            if (c0 + d < c1) { load_w(wr[d], c0 + d); stage_x(c0 + d, d); }
+        int buf = 0;
+        for (int c = c0; c < c1; c += DEPTH) {
+#pragma unroll
+            for (int d = 0; d < DEPTH; d++)
+                if (c + d < c1) { phase(wr[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+        }
+    }
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n; the column scale goes on the fp32 sum, then ONE rounding to the model dtype
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int m = 16 * mt + 4 * g + r;
+            const float v = acc[mt][r] * sc;
+            if (out) out[(size_t)m * N + n0 + n] = (E)v;
+            else __hip_atomic_store(&partial[((size_t)split * R + m) * N + n0 + n], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// row-major [N][K] e4m3fn bytes -> the packed blocks of k_gemm_skinny_f8; one thread moves one 16-byte unit
+__global__ __launch_bounds__(256) void k_gemm_pack_f8(const uint4 *__restrict__ W8, uint4 *__restrict__ out, int N, int K) {
+    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;          // destination unit
+    const long long total = (long long)N * K / 16;
+    if (u >= total) return;
+    const int n_chunks = K / GEMM_KC;
+    const long long blk = u >> 11;                                          // 2048 units per 32 KiB block
+    const int in = (int)(u & 2047), b = in >> 9, tid = in & 511, w = tid >> 6, g = (tid >> 4) & 3, n = tid & 15;
+    const int t = (int)(blk / n_chunks), c = (int)(blk % n_chunks);
+    const long long row = 128LL * t + 16 * w + n, col = 256LL * c + 64 * b + 16 * g;
+    out[u] = W8[(row * K + col) / 16];
+}
+
+template <typename TT, int RT, int DEPTH>
+static hipError_t gemm_f8_launch(dim3 grid, hipStream_t st, const void *A, const void *W8, const float *scale, float *partial, void *out, int K, int N,
+                                 int splits) {
+    constexpr int lds = (DEPTH + 1) * 16 * RT * GEMM_KC * 2;
+    if constexpr (lds > 65536) {
+        static unsigned long long done = 0ull;                     // per-device (samd_common.h)
+        const hipError_t attr = samd_reserve_lds((const void *)k_gemm_skinny_f8<TT, RT, DEPTH>, lds, &done);
+        if (attr != hipSuccess) return attr;
+    }
+    hipLaunchKernelGGL((k_gemm_skinny_f8<TT, RT, DEPTH>), grid, dim3(64 * GEMM_WAVES), lds, st, (const typename TT::elem *)A, (const unsigned char *)W8, scale,
+                       partial, (typename TT::elem *)out, K, N, K / GEMM_KC, splits);
+    return hipSuccess;
+}
+
+extern "C" {
+
+int samd_gemm_pack_f8(const void *d_W8, void *d_out, int32_t N, int32_t K, void *stream) {
+    if (!d_W8 || !d_out || d_W8 == d_out || N < GEMM_COLS || N % GEMM_COLS != 0 || K < GEMM_KC || K % GEMM_KC != 0) {
+        samd_set_error("samd_gemm_pack_f8: needs N %% 128 == 0, K %% 256 == 0 and distinct buffers"); return SAMD_E_INVALID;
+    }
+    const long long units = (long long)N * K / 16;
+    hipLaunchKernelGGL(k_gemm_pack_f8, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)d_W8, (uint4 *)d_out, N, K);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_gemm_skinny_f8(const void *d_A, const void *d_W8p, const float *d_scale, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial,
+                        void *d_out, int32_t dtype, void *stream) {
+    if (!d_A || !d_W8p || !d_scale || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS || N % GEMM_COLS != 0 ||
+        K < GEMM_KC || K % GEMM_KC != 0 || splits < 1 || splits > K / GEMM_KC || (splits == 1 ? !d_out : !d_partial) || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("samd_gemm_skinny_f8: unsupported shape (rows 16/32/48/64, N %% 128 == 0, K %% 256 == 0) or null pointer"); return SAMD_E_INVALID;
+    }
+    const dim3 grid(N / GEMM_COLS, splits);
+    const hipStream_t st = (hipStream_t)stream;
+    float *part = splits == 1 ? nullptr : d_partial;
+    void *out = splits == 1 ? d_out : nullptr;
+#define GO(TT, RT, D) e = gemm_f8_launch<TT, RT, D>(grid, st, d_A, d_W8p, d_scale, part, out, K, N, splits)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1, 4); else if (rows_pad == 32) GO(TT, 2, 4); else if (rows_pad == 48) GO(TT, 3, 4); else GO(TT, 4, 3); } while (0)
+    hipError_t e;
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
+    if (e != hipSuccess) { samd_set_error("samd_gemm_skinny_f8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+}  // extern "C"

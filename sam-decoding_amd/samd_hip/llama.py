@@ -17,6 +17,29 @@ import torch
 
 from . import (F16, BF16, MAX_DRAFT, TILE_ROWS, SamdError, Session, Warm, _ptr, check, current_stream, lib, require_gpu,
                torch_dtype_code)
+from . import fp8 as F8
+
+
+def _env_weight_format(weight_format):
+    """an explicit weight_format, else SAMD_WEIGHT_FORMAT (for callers that cannot pass one: SamdModel, bench.py), else None"""
+    return weight_format if weight_format is not None else (os.environ.get("SAMD_WEIGHT_FORMAT") or None)
+
+
+def _weight_format(weight_format, weights, dtype):
+    """"fp8" or None (the model dtype).  Projections that arrive as float8_e4m3fn (an FP8 checkpoint) make the runner FP8 by themselves."""
+    has_f8 = any(l[k].dtype == torch.float8_e4m3fn for l in weights["layers"] for k in F8.PROJECTIONS if k in l)
+    names = {torch.float16: ("fp16", "float16", "half"), torch.bfloat16: ("bf16", "bfloat16")}.get(dtype, ())
+    if weight_format is None:
+        fmt = "fp8" if has_f8 else None
+    elif weight_format == "fp8":
+        fmt = "fp8"
+    elif weight_format == dtype or (isinstance(weight_format, str) and weight_format.lower() in names):
+        fmt = None
+    else:
+        raise SamdError(f"weight_format {weight_format!r}: expected None, 'fp8' or the model dtype ({dtype})")
+    if has_f8 and fmt != "fp8":
+        raise SamdError(f"the weights carry float8_e4m3fn projections; weight_format {weight_format!r} would need them dequantised (pass None or 'fp8')")
+    return fmt
 
 
 def _cfg_get(cfg, name, default=None):
@@ -82,18 +105,26 @@ class LlamaRunner:
     BUCKETS = (1, 8, 16, 32, 48, 64, 128)
 
     def __init__(self, shape, weights, max_cache_len, dtype=torch.float16, device="cuda", kv=None, native_gemm=True, packed_lm_head=None,
-                 attention=None):
+                 attention=None, weight_format=None):
         require_gpu()
         self.shape, self.dtype, self.device = shape, dtype, torch.device(device)
         self.dt = torch_dtype_code(dtype)
         if self.dt not in (F16, BF16):
             raise SamdError("LlamaRunner computes in fp16 or bf16")
+        # weight_format "fp8": the four projections of every layer as OCP e4m3fn with one fp32 scale per output column (samd_hip/fp8.py),
+        # streamed by samd_gemm_skinny_f8 only -- no row-major copy, no fused or norm-fold forms; embedding and lm_head stay in the model dtype
+        self.weight_format = _weight_format(weight_format, weights, dtype)
+        f8 = self.weight_format == "fp8"
+        if f8 and not native_gemm:
+            raise SamdError("FP8 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'fp8'")
         s = shape
         self.w = weights
         # samd_gemm_skinny streams the weights itself where the shape allows (N % 128 == 0, K % 256 == 0); a projection that
         # does not fit (say a fine-tune's 32001-row lm_head) goes to the library GEMM on its own, the others keep the kernel
         streams = lambda t: bool(native_gemm) and t.shape[0] % 128 == 0 and t.shape[1] % 256 == 0
         self.native_gemm_max_rows = int(os.environ.get("SAMD_NATIVE_GEMM_MAX_ROWS", 64))     # tuning knob; see forward_rows
+        if f8:
+            self.native_gemm_max_rows = TILE_ROWS            # (no library GEMM to hand rows to: every bucket up to 64 rows streams)
         # L2 warm-up (csrc/warm_device.h): the glue launch in front of a projection also reads the first KiB of every workgroup's
         # weight stream into the consuming XCD's L2 while HBM idles.  KiB per projection workgroup; 0 = off, the default: measured
         # zero-sum (profiles/r03_l2_warm.md -- the projections get faster by what the glue launches get slower).
@@ -163,9 +194,31 @@ class LlamaRunner:
             out = torch.empty_like(t)
             check(lib().samd_gemm_pack_groups(_ptr(t), _ptr(out), t.shape[0], t.shape[1], current_stream()))
             return out
+        def pack_f8(l, k):
+            """(packed e4m3fn bytes, fp32 column scales) of projection k: quantised on load (symmetric per row) unless the checkpoint
+            brought its own (q, scale); the model-dtype matrix is dropped as soon as it is packed"""
+            t = l[k]
+            N, K = t.shape
+            if N % 128 != 0 or K % 256 != 0:
+                raise SamdError(f"FP8 projection {k} of shape {tuple(t.shape)}: the FP8 kernel needs N % 128 == 0 and K % 256 == 0")
+            if t.dtype == torch.float8_e4m3fn:
+                q, scale = t.to(self.device).contiguous(), l.pop(k + "_scale").to(device=self.device, dtype=torch.float32).contiguous()
+            else:
+                q, scale = F8.quantize_rows(t)
+            l[k] = torch.empty(t.shape, dtype=torch.float8_e4m3fn, device="meta")
+            del t
+            out = torch.empty_like(q)
+            check(lib().samd_gemm_pack_f8(_ptr(q), _ptr(out), N, K, current_stream()))
+            return out, scale
         # packed_lm_head: a draft head shares the base model's lm_head, packed copy included
         layers = []
         for l in weights["layers"]:
+            if f8:
+                lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
+                for k in F8.PROJECTIONS:
+                    lp[k + "_f8"] = pack_f8(l, k)
+                layers.append(lp)
+                continue
             lp = dict(wgu=pack_gate_up(l["wgu"]), wqkv64=pack_qkv64(l["wqkv"]))
             # the 128-column packed q|k|v (split-K projection + samd_rope_kv_write_cs) only where the fused tile form does not exist:
             # with it, no launch of this runner ever reads the other (3.2 GB of a 7B model)
@@ -192,7 +245,7 @@ class LlamaRunner:
         self.norm_fold = (self.wp is not None and self.attention == "split"
                           and all(l.get("wo_g") is not None and l.get("wdown_g") is not None for l in self.wp["layers"]))
         self.scale = 1.0 / math.sqrt(s.head_dim)
-        self.row_major_released = False
+        self.row_major_released = f8                             # (FP8: there are no row-major projections; prefill runs in 64-row chunks)
         self._length_state(max_cache_len, kv)
         if os.environ.get("SAMD_RELEASE_ROW_MAJOR", "0") == "1":
             self.release_row_major()
@@ -207,7 +260,13 @@ class LlamaRunner:
             for k in ("wqkv", "wqkv64", "wo", "wo_g", "wgu", "wdown", "wdown_g"):
                 rep["packed_" + k] = sum(nbytes(l.get(k)) for l in self.wp["layers"])
             rep["packed_lm_head"] = nbytes(self.wp["lm_head"])
+            if self.weight_format == "fp8":
+                for k in F8.PROJECTIONS:
+                    rep["packed_" + k + "_f8"] = sum(nbytes(l[k + "_f8"][0]) for l in self.wp["layers"])
+                rep["fp8_scales"] = sum(nbytes(l[k + "_f8"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
         rep["total"] = sum(rep.values())
+        if self.weight_format == "fp8":
+            rep["weight_format"] = "fp8"
         return rep
 
     def release_row_major(self):
@@ -295,12 +354,21 @@ class LlamaRunner:
 
     # ------------------------------------------------------------------------------------------------
     @classmethod
-    def from_hf(cls, lm, max_cache_len, dtype=None, device="cuda", share_weights=None, **kw):
+    def from_hf(cls, lm, max_cache_len, dtype=None, device="cuda", share_weights=None, weight_format=None, **kw):
         """weights of a transformers LlamaForCausalLM (what the reference passes as `lm`).  share_weights (default: env
         SAMD_SHARE_HF_WEIGHTS, off): re-point the HF module's q/k/v and gate/up weights at row slices of the runner's concatenated
         matrices -- saves one row-major copy of the model, but the caller's parameters become views of storage the runner owns
-        (matters for save_pretrained / in-place edits), so it is opt-in and logged once."""
-        dtype = dtype or next(lm.parameters()).dtype
+        (matters for save_pretrained / in-place edits), so it is opt-in and logged once.
+        weight_format (default: env SAMD_WEIGHT_FORMAT, unset = the model dtype): "fp8" quantises the projections on load.  A module whose
+        projections already hold float8_e4m3fn weights with a `weight_scale` (per tensor, [N] or [N, 1]) is imported as it is (samd_hip/fp8.py)."""
+        weight_format = _env_weight_format(weight_format)
+        m = lm.model
+        parts = (("self_attn", "q_proj"), ("self_attn", "k_proj"), ("self_attn", "v_proj"), ("self_attn", "o_proj"), ("mlp", "gate_proj"),
+                 ("mlp", "up_proj"), ("mlp", "down_proj"))
+        ckpt_f8 = F8.checkpoint_is_fp8([(f"layers.{i}.{a}.{b}", getattr(getattr(lyr, a), b)) for i, lyr in enumerate(m.layers) for a, b in parts])
+        if F8.is_fp8_dtype(lm.lm_head.weight.dtype) or F8.is_fp8_dtype(m.embed_tokens.weight.dtype):
+            raise SamdError("FP8 embedding / lm_head weights are not supported: they stay in the model dtype")
+        dtype = dtype or next(p.dtype for p in lm.parameters() if not F8.is_fp8_dtype(p.dtype))
         shape = LlamaShape(lm.config)
         dev = torch.device(device)
 
@@ -331,6 +399,12 @@ class LlamaRunner:
             for lin in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, f.gate_proj, f.up_proj, f.down_proj):
                 if getattr(lin, "bias", None) is not None:
                     raise SamdError("LlamaRunner: projection biases are not supported")
+            if ckpt_f8:                                          # (q, scale) as the checkpoint has them; the runner packs them
+                lw = {}
+                for k, lins in (("wqkv", (a.q_proj, a.k_proj, a.v_proj)), ("wo", (a.o_proj,)), ("wgu", (f.gate_proj, f.up_proj)), ("wdown", (f.down_proj,))):
+                    lw[k], lw[k + "_scale"] = F8.fuse_fp8([F8.linear_fp8(x) for x in lins], dev)
+                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight)))
+                continue
             layers.append(dict(
                 wqkv=fuse((a.q_proj, a.k_proj, a.v_proj)),
                 wo=get(a.o_proj.weight),
@@ -342,11 +416,11 @@ class LlamaRunner:
             import logging
             logging.getLogger("samd_hip").info("LlamaRunner.from_hf: %d fused projection groups now back the HF module's q/k/v and gate/up "
                                                "weights (share_weights); its parameters are views of the runner's matrices", shared[0])
-        return cls(shape, weights, max_cache_len, dtype, device, **kw)
+        return cls(shape, weights, max_cache_len, dtype, device, weight_format=weight_format, **kw)
 
     @classmethod
-    def random_init(cls, cfg, max_cache_len, dtype=torch.float16, device="cuda", seed=0, std=0.02, **kw):
-        """random-init weights of the given architecture, created directly in HBM (no checkpoint on the box)."""
+    def random_init(cls, cfg, max_cache_len, dtype=torch.float16, device="cuda", seed=0, std=0.02, weight_format=None, **kw):
+        """random-init weights of the given architecture, created directly in HBM (no checkpoint on the box).  weight_format: as from_hf's."""
         require_gpu()
         shape = LlamaShape(cfg)
         g = torch.Generator(device=device).manual_seed(seed)
@@ -360,14 +434,18 @@ class LlamaRunner:
                        ln2=torch.ones(s.hidden, dtype=dtype, device=device)) for _ in range(s.layers)]
         weights = dict(embed=rnd(s.vocab, s.hidden), layers=layers, norm=torch.ones(s.hidden, dtype=dtype, device=device),
                        lm_head=rnd(s.vocab, s.hidden))
-        return cls(shape, weights, max_cache_len, dtype, device, **kw)
+        return cls(shape, weights, max_cache_len, dtype, device, weight_format=_env_weight_format(weight_format), **kw)
 
     def weight_bytes(self):
-        """bytes of weights one decode step streams from HBM (the embedding table is only gathered)."""
-        n = self.w["lm_head"].numel() + self.w["norm"].numel()
+        """bytes of weights one decode step streams from HBM (the embedding table is only gathered), tensor by tensor in its own format
+        (an FP8 projection: one byte per weight + its fp32 column scales)."""
+        nb = lambda t: t.numel() * t.element_size()
+        n = nb(self.w["lm_head"]) + nb(self.w["norm"])
         for l in self.w["layers"]:
-            n += sum(t.numel() for t in l.values())
-        return n * self.w["lm_head"].element_size()
+            n += sum(nb(t) for t in l.values())
+        if self.weight_format == "fp8":
+            n += sum(nb(l[k + "_f8"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
+        return n
 
     # ------------------------------------------------------------------------------------------------
     def _buffers(self, R):
@@ -427,10 +505,14 @@ class LlamaRunner:
             sp = 1 if (fused or is_head) else L.samd_gemm_splits(n, k, RP)
             return C.byref(Warm(wp.data_ptr(), n, k, sp, self.warm_kb, self.warm_delay, self.warm_where))
 
-        def gemm(a, w, wp, out, wg=None):
-            """out = a @ w.T (wp = w in the packed 128-column-tile layout, wg = w group-major: whichever exists); returns
-            (operand for the consumer, n_partials, partial_stride)."""
+        def gemm(a, w, wp, out, wg=None, f8=None):
+            """out = a @ w.T (wp = w in the packed 128-column-tile layout, wg = w group-major: whichever exists; f8 = (packed e4m3fn, column
+            scales) of an FP8 runner); returns (operand for the consumer, n_partials, partial_stride)."""
             n, k = w.shape
+            if f8 is not None:                                    # (RP <= 64 here: an FP8 runner has no library-GEMM path, see the check above)
+                sp = L.samd_gemm_splits(n, k, RP)
+                check(L.samd_gemm_skinny_f8(_ptr(a), _ptr(f8[0]), _ptr(f8[1]), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
+                return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
             # measured on MI355X (scripts/forward_ablation.py, whole forward incl. the consumers' partial-sum reads), ours vs
             # the library GEMM: 3.46 vs 4.75 ms at <= 16 rows, 3.74 vs 4.62 at 32, 4.72 vs 5.15 at 64
             if (wp is None and wg is None) or RP > self.native_gemm_max_rows:
@@ -476,7 +558,7 @@ class LlamaRunner:
                     _ptr(b["x"] if raw_in else b["h"]), _ptr(wp["wqkv64"]), RP, s.hidden, _ptr(b["cs"]), _ptr(d_L), _ptr(d_n),
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), s.heads, s.kv_heads, s.head_dim, self.max_len, dt, st))
             else:
-                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"])
+                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], f8=wp.get("wqkv_f8"))
             if block:
                 # RoPE + K row / V^T column write + tree attention + merge of the tile partials: one launch (csrc/attn_kernels.hip)
                 check(L.samd_attention_block(_ptr(src), n_p, stride, _ptr(b["cs"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R,
@@ -501,15 +583,15 @@ class LlamaRunner:
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R, s.heads,
                     s.kv_heads, s.head_dim, self.max_len, _ptr(d_mask), _ptr(d_L), _ptr(d_n), self.scale,
                     _ptr(b["ws"]), b["ws_bytes"], hint(w["wo"], wp.get("wo")), st))
-            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"))
+            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"))
             check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(src), _ptr(w["ln2"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, n_p, stride,
                                       None, st))           # (no warm-up hint: gate|up is packed group-major, the hint describes 128-column tiles)
             if self.fused_mlp and RP <= self.native_gemm_max_rows:
                 check(L.samd_gemm_pairs_silu(_ptr(b["h"]), _ptr(wp["wgu"]), RP, s.inter, s.hidden, _ptr(b["act"]), dt, st))
             else:
-                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"])           # wgu is only ever packed for the fused form
+                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"))     # wgu is only ever packed for the fused form (or FP8)
                 check(L.samd_silu_mul(_ptr(src), _ptr(b["act"]), R, s.inter, dt, n_p, stride, st))
-            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"))
+            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"))
         check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(delta), _ptr(self.w["norm"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, dn, dstride,
                                   hint(self.w["lm_head"], self.wp["lm_head"] if self.wp else None, is_head=True), st))
         # (for a draft head the call above only folds the last projection into the residual stream; its norm output is unused)
