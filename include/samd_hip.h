@@ -458,6 +458,27 @@ int samd_rope_kv_write_vt(const void *d_qkv, const int32_t *d_rel_pos, const int
                           const float *d_cos, const float *d_sin, void *d_q_out, void *d_k_cache, void *d_vt_cache, int32_t rows,
                           int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t max_len, int32_t max_pos, int32_t dtype,
                           int32_t n_partials, int64_t partial_stride, void *stream);
+/* The q|k|v epilogue of Qwen2 / Qwen3 in front of the RoPE + K/V write (csrc/lm_kernels.hip k_rope_kv<T, true>, k_rope_kv_wide_epi,
+ * k_v_rows_to_vt_bias).  Operands in the model dtype T; a null pointer = that part is absent.  For every row and head, in this order:
+ *   x = round_T(product + bias)      split-K partials: round_T(sum of the partials in today's order + float(bias)); a finished product
+ *                                    (library GEMM, one split): round_T(float(qkv) + float(bias)); no bias: the product as before;
+ *   q / k heads with the norms:      y = round_T(x * rsqrt(sum_j x_j^2 / 128 + eps)) (fp32 sum), z = round_T(float(w) * float(y)) -- HF's
+ *                                    Qwen3RMSNorm over the head's 128 elements (modeling_qwen3.py q_norm / k_norm);
+ *   then the RoPE of the entries above with its single rounding, and the K row / V row or V^T column write.  V heads: the bias only.
+ * head_dim must be 128; q_norm and k_norm come together. */
+typedef struct samd_qkv_epilogue {
+    const void *d_bias;            /* [(H + 2 H_kv) * 128] bias of q|k|v, or NULL */
+    const void *d_q_norm;          /* [128] q_norm weight, or NULL */
+    const void *d_k_norm;          /* [128] k_norm weight, or NULL (with d_q_norm) */
+    float eps;                     /* rms_norm_eps of the two norms */
+} samd_qkv_epilogue_t;
+/* One entry for the four forms above: d_cs != NULL takes the rows' cos | sin from d_cs (d_cos / d_sin NULL, max_pos unused), else the
+ * position tables; v_transposed = 1 writes V^T columns ([H_kv][D][max_len]; d_v_cache may then be NULL), 0 row-major V.  epi == NULL, or an
+ * epilogue without operands, is exactly samd_rope_kv_write / _cs / _vt / _cs_vt.  Rows >= n and positions at or past max_len stay untouched. */
+int samd_rope_kv_write_epi(const void *d_qkv, const int32_t *d_rel_pos, const int32_t *d_cache_length, const int32_t *d_n,
+                           const float *d_cos, const float *d_sin, const float *d_cs, void *d_q_out, void *d_k_cache, void *d_v_cache,
+                           int32_t v_transposed, int32_t rows, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t max_len,
+                           int32_t max_pos, int32_t dtype, int32_t n_partials, int64_t partial_stride, const samd_qkv_epilogue_t *epi, void *stream);
 int samd_kv_compact_vt(samd_session_t *s, void *const *d_tensors, int32_t n_tensors, int32_t n_transposed, int32_t n_heads, int64_t max_len,
                        int32_t head_dim, int32_t elem_bytes, void *stream);
 int samd_kv_compact_indices_vt(void *const *d_tensors, int32_t n_tensors, int32_t n_transposed, int32_t n_heads, int64_t max_len, int32_t head_dim,

@@ -9,6 +9,7 @@
 #include "samd_common.h"
 #include "prefill_attn_device.h"
 #include "warm_device.h"
+#include "topk_device.h"
 
 #define LAUNCHCHK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { samd_set_error("kernel launch: %s", hipGetErrorString(e_)); return SAMD_E_HIP; } } while (0)
 
@@ -177,11 +178,23 @@ __global__ __launch_bounds__(1024) void k_rmsnorm(T *__restrict__ x, const T *__
 //   v_cache[kvh][L + r][:]    <- v
 // position of row r = L + rel_pos[r] (tree depth or sequence offset; samd_model.py:127-132).
 // grid = (rows, H + 2*Hkv), block = D/2 threads; rows >= *d_n are skipped.
-template <typename T>
+//
+// EPI (samd_rope_kv_write_epi, Qwen2 / Qwen3; D == 128, so one wave per (row, head)): the q|k|v epilogue in front of the RoPE.
+// x = round_T(product + bias) -- the fp32 split-K sum plus the bias, rounded once, or the already-rounded product plus the bias, rounded --,
+// then per q / k head Qwen3's q_norm / k_norm: y = round_T(x * rsqrt(sum(x^2) / 128 + eps)), z = round_T(w * y) (HF Qwen3RMSNorm); then the
+// RoPE and the writes as without it.  V heads: the bias only.  The !EPI instantiations are the kernels of before, instruction for instruction.
+template <typename T> struct QkvEpi {
+    const T *bias;                     // [(H + 2 Hkv) * 128] or null
+    const T *q_norm, *k_norm;          // [128] each, or both null
+    float eps;
+};
+
+template <typename T, bool EPI>
 __global__ void k_rope_kv(const T *__restrict__ qkv, const int *__restrict__ rel_pos, const int *__restrict__ d_L,
                           const int *__restrict__ d_n, const float *__restrict__ cos_t, const float *__restrict__ sin_t,
                           T *__restrict__ q_out, T *__restrict__ k_cache, T *__restrict__ v_cache, int H, int Hkv, int D,
-                          long long max_len, int max_pos, int n_part, long long part_stride, int v_transposed, const float *__restrict__ cs) {
+                          long long max_len, int max_pos, int n_part, long long part_stride, int v_transposed, const float *__restrict__ cs,
+                          QkvEpi<T> epi) {
     const int r = blockIdx.x, hh = blockIdx.y, j = threadIdx.x, half = D >> 1;
     // cs != null: this row's cos | sin were prepared by k_rope_rows (once per forward, [rows][D]); they are requested HERE, in the same
     // round trip as the operands, instead of after L and the row's position are known (one dependent memory round trip less)
@@ -192,8 +205,12 @@ __global__ void k_rope_kv(const T *__restrict__ qkv, const int *__restrict__ rel
     const int rel = rel_pos[r], n = d_n[0], L = d_L[0];
     const size_t soff = ((size_t)r * (H + 2 * Hkv) + hh) * D;
     float x1, x2;                                              // elements j and j + D/2 of this head's row
-    if (n_part == 0) { x1 = (float)qkv[soff + j]; x2 = (float)qkv[soff + j + half]; }
-    else {
+    if (n_part == 0) {
+        x1 = (float)qkv[soff + j]; x2 = (float)qkv[soff + j + half];
+        if constexpr (EPI) {
+            if (epi.bias) { x1 = (float)(T)(x1 + (float)epi.bias[(size_t)hh * D + j]); x2 = (float)(T)(x2 + (float)epi.bias[(size_t)hh * D + j + half]); }
+        }
+    } else {
         const float *part = reinterpret_cast<const float *>(qkv);
         float a = 0.f, b = 0.f;
         for (int s0 = 0; s0 < n_part; s0 += 8) {                  // 16 loads in flight per group (see ld8_or_partials)
@@ -206,7 +223,20 @@ __global__ void k_rope_kv(const T *__restrict__ qkv, const int *__restrict__ rel
 #pragma unroll
             for (int k = 0; k < 8; k++) if (s0 + k < n_part) { a += pa[k]; b += pb[k]; }
         }
+        if constexpr (EPI) {
+            if (epi.bias) { a += (float)epi.bias[(size_t)hh * D + j]; b += (float)epi.bias[(size_t)hh * D + j + half]; }   // one rounding below
+        }
         x1 = (float)(T)a; x2 = (float)(T)b;                    // rounded like the GEMM's own output
+    }
+    if constexpr (EPI) {
+        // the head's RMSNorm: hh is uniform over the workgroup (one wave), all 64 lanes active -- the reduction precedes the early returns
+        if (epi.q_norm && hh < H + Hkv) {
+            const T *w = hh < H ? epi.q_norm : epi.k_norm;
+            const float ss = e2_wave_sum(x1 * x1 + x2 * x2);
+            const float inv = rsqrtf(ss / (float)D + epi.eps);
+            const T y1 = (T)(x1 * inv), y2 = (T)(x2 * inv);
+            x1 = (float)(T)((float)w[j] * (float)y1); x2 = (float)(T)((float)w[j + half] * (float)y2);
+        }
     }
     if (r >= n) return;
     if (L + r >= max_len) return;                              // never write past the cache (the host guard breaks earlier)
@@ -235,17 +265,53 @@ __global__ void k_rope_kv(const T *__restrict__ qkv, const int *__restrict__ rel
 // The same for the prompt's rows (round 5: 33 -> ~15 us per layer at 1.3-1.5 k rows, profiles/r05_prefill.md): head_dim 128, dtype operands, position
 // tables; 8 elements of each half per lane (16-byte loads / stores) and 8 heads per 64-thread workgroup instead of one 2-byte element pair
 // per thread.  Same expressions, same roundings as k_rope_kv.  grid = (rows, ceil((H + 2 Hkv) / 8)).
-template <typename T>
-__global__ __launch_bounds__(64) void k_rope_kv_wide(const T *__restrict__ qkv, const int *__restrict__ rel_pos, const int *__restrict__ d_L,
-                                                     const int *__restrict__ d_n, const float *__restrict__ cos_t, const float *__restrict__ sin_t,
-                                                     T *__restrict__ q_out, T *__restrict__ k_cache, T *__restrict__ v_cache, int H, int Hkv,
-                                                     long long max_len, int max_pos) {
+template <typename T, bool EPI>
+__device__ __forceinline__ void rope_kv_wide_row(const T *__restrict__ qkv, const int *__restrict__ rel_pos, const int *__restrict__ d_L,
+                                                 const int *__restrict__ d_n, const float *__restrict__ cos_t, const float *__restrict__ sin_t,
+                                                 T *__restrict__ q_out, T *__restrict__ k_cache, T *__restrict__ v_cache, int H, int Hkv,
+                                                 long long max_len, int max_pos, const QkvEpi<T> epi) {
     typedef T V8 __attribute__((ext_vector_type(8)));
-    const int r = blockIdx.x, hh = blockIdx.y * 8 + (threadIdx.x >> 3), j = (threadIdx.x & 7) * 8;
-    if (hh >= H + 2 * Hkv) return;
+    const int r = blockIdx.x, j = (threadIdx.x & 7) * 8;
+    int hh = blockIdx.y * 8 + (threadIdx.x >> 3);
+    const bool live = hh < H + 2 * Hkv;
+    if constexpr (!EPI) {
+        if (!live) return;
+    } else {
+        if (!live) hh = H + 2 * Hkv - 1;          // (EPI: lanes past the last head load a real one and take part in the reductions, then leave)
+    }
     const int rel = rel_pos[r], n = d_n[0], L = d_L[0];
     const size_t soff = ((size_t)r * (H + 2 * Hkv) + hh) * 128;
-    const V8 a = *reinterpret_cast<const V8 *>(qkv + soff + j), b = *reinterpret_cast<const V8 *>(qkv + soff + 64 + j);
+    V8 a = *reinterpret_cast<const V8 *>(qkv + soff + j), b = *reinterpret_cast<const V8 *>(qkv + soff + 64 + j);
+    if constexpr (EPI) {
+        float xa[8], xb[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) { xa[k] = (float)a[k]; xb[k] = (float)b[k]; }
+        if (epi.bias) {
+            const V8 ba = *reinterpret_cast<const V8 *>(epi.bias + (size_t)hh * 128 + j), bb = *reinterpret_cast<const V8 *>(epi.bias + (size_t)hh * 128 + 64 + j);
+#pragma unroll
+            for (int k = 0; k < 8; k++) { xa[k] = (float)(T)(xa[k] + (float)ba[k]); xb[k] = (float)(T)(xb[k] + (float)bb[k]); }
+        }
+        if (epi.q_norm) {
+            // the head's sum of squares over its 8 lanes (xor 1 / 2 / 4 stay inside the group); every lane of the wave takes part
+            float ss = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; k++) { ss += xa[k] * xa[k]; ss += xb[k] * xb[k]; }
+            ss += __shfl_xor(ss, 1); ss += __shfl_xor(ss, 2); ss += __shfl_xor(ss, 4);
+            if (hh < H + Hkv) {
+                const T *w = hh < H ? epi.q_norm : epi.k_norm;
+                const V8 wa = *reinterpret_cast<const V8 *>(w + j), wb = *reinterpret_cast<const V8 *>(w + 64 + j);
+                const float inv = rsqrtf(ss / 128.f + epi.eps);
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    xa[k] = (float)(T)((float)wa[k] * (float)(T)(xa[k] * inv));
+                    xb[k] = (float)(T)((float)wb[k] * (float)(T)(xb[k] * inv));
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) { a[k] = (T)xa[k]; b[k] = (T)xb[k]; }
+        if (!live) return;
+    }
     if (r >= n || L + r >= max_len) return;
     if (hh >= H + Hkv) {
         if (!v_cache) return;
@@ -267,13 +333,32 @@ __global__ __launch_bounds__(64) void k_rope_kv_wide(const T *__restrict__ qkv, 
     *reinterpret_cast<V8 *>(dst + j) = o1; *reinterpret_cast<V8 *>(dst + 64 + j) = o2;
 }
 
+template <typename T>
+__global__ __launch_bounds__(64) void k_rope_kv_wide(const T *__restrict__ qkv, const int *__restrict__ rel_pos, const int *__restrict__ d_L,
+                                                     const int *__restrict__ d_n, const float *__restrict__ cos_t, const float *__restrict__ sin_t,
+                                                     T *__restrict__ q_out, T *__restrict__ k_cache, T *__restrict__ v_cache, int H, int Hkv,
+                                                     long long max_len, int max_pos) {
+    rope_kv_wide_row<T, false>(qkv, rel_pos, d_L, d_n, cos_t, sin_t, q_out, k_cache, v_cache, H, Hkv, max_len, max_pos, QkvEpi<T>{nullptr, nullptr, nullptr, 0.f});
+}
+
+// the same with the q|k|v epilogue of k_rope_kv<T, true> (8 lanes per head: the head's sum of squares is an 8-lane reduction)
+template <typename T>
+__global__ __launch_bounds__(64) void k_rope_kv_wide_epi(const T *__restrict__ qkv, const int *__restrict__ rel_pos, const int *__restrict__ d_L,
+                                                         const int *__restrict__ d_n, const float *__restrict__ cos_t, const float *__restrict__ sin_t,
+                                                         T *__restrict__ q_out, T *__restrict__ k_cache, T *__restrict__ v_cache, int H, int Hkv,
+                                                         long long max_len, int max_pos, QkvEpi<T> epi) {
+    rope_kv_wide_row<T, true>(qkv, rel_pos, d_L, d_n, cos_t, sin_t, q_out, k_cache, v_cache, H, Hkv, max_len, max_pos, epi);
+}
+
 // The prompt's V rows into a TRANSPOSED cache (round 6): vt_cache[kvh][d][L + r] <- qkv[r][H + Hkv + kvh][d] for r < n.  One workgroup = one KV head x
 // 64 rows: the rows are read as 16-byte pieces (a wave's load = 4 rows x 256 contiguous bytes), turned in LDS, and leave as 16-byte pieces of 8 keys
 // of one column (a wave's store = 8 columns x 128 contiguous bytes) -- where k_rope_kv's transposed form writes one 2-byte element per lane and a
 // strided torch copy (what the prefill did before) takes 17-40 us per layer at 0.5-1.5 k rows.  L % 8 != 0 or the prompt's last, partial piece of 8
 // keys: element stores.  16-bit elements of either dtype (a copy).
-__global__ __launch_bounds__(256) void k_v_rows_to_vt(const unsigned short *__restrict__ qkv, const int *__restrict__ d_L, const int *__restrict__ d_n,
-                                                      unsigned short *__restrict__ vt_cache, int rows, int H, int Hkv, long long max_len) {
+// BIAS (samd_rope_kv_write_epi): each staged V element becomes round_T(v + bias), T = the model dtype; the non-BIAS kernel is the plain copy.
+template <typename T, bool BIAS>
+__device__ __forceinline__ void v_rows_to_vt(const unsigned short *__restrict__ qkv, const int *__restrict__ d_L, const int *__restrict__ d_n,
+                                             unsigned short *__restrict__ vt_cache, int rows, int H, int Hkv, long long max_len, const T *__restrict__ bias) {
     constexpr int RS = 128 + 8;                                  // halfs per staged row: 272 B (16-byte aligned, rows 8 apart fall on different banks)
     __shared__ __attribute__((aligned(16))) unsigned short tile[64 * RS];
     const int tid = threadIdx.x, kvh = blockIdx.y, r0 = 64 * blockIdx.x;
@@ -285,6 +370,15 @@ __global__ __launch_bounds__(256) void k_v_rows_to_vt(const unsigned short *__re
         const int u = tid + 256 * i, r = u >> 4, sl = u & 15;
         uint4 v = make_uint4(0, 0, 0, 0);
         if (r0 + r < n) v = *reinterpret_cast<const uint4 *>(qkv + (size_t)(r0 + r) * row_elems + (size_t)(H + Hkv + kvh) * 128 + 8 * sl);
+        if constexpr (BIAS) {
+            if (r0 + r < n) {
+                Vec8<T> x = __builtin_bit_cast(Vec8<T>, v);
+                const Vec8<T> bv = ld8(bias + (size_t)(H + Hkv + kvh) * 128 + 8 * sl);
+#pragma unroll
+                for (int k = 0; k < 8; k++) x.v[k] = (T)((float)x.v[k] + (float)bv.v[k]);
+                v = __builtin_bit_cast(uint4, x);
+            }
+        }
         *reinterpret_cast<uint4 *>(&tile[r * RS + 8 * sl]) = v;
     }
     __syncthreads();
@@ -307,6 +401,18 @@ __global__ __launch_bounds__(256) void k_v_rows_to_vt(const unsigned short *__re
             for (int j = 0; j < 8; j++) if (j < live) dst[j] = e[j];
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_v_rows_to_vt(const unsigned short *__restrict__ qkv, const int *__restrict__ d_L, const int *__restrict__ d_n,
+                                                      unsigned short *__restrict__ vt_cache, int rows, int H, int Hkv, long long max_len) {
+    v_rows_to_vt<unsigned short, false>(qkv, d_L, d_n, vt_cache, rows, H, Hkv, max_len, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_v_rows_to_vt_bias(const unsigned short *__restrict__ qkv, const int *__restrict__ d_L, const int *__restrict__ d_n,
+                                                           unsigned short *__restrict__ vt_cache, int rows, int H, int Hkv, long long max_len,
+                                                           const T *__restrict__ bias) {
+    v_rows_to_vt<T, true>(qkv, d_L, d_n, vt_cache, rows, H, Hkv, max_len, bias);
 }
 
 // out = silu(gate) * up, gate|up concatenated per row: gu[r] = [gate(I) | up(I)]
@@ -420,8 +526,8 @@ static int rope_kv_write(const void *d_qkv, const int32_t *d_rel_pos, const int3
         return SAMD_OK;
     }
     const dim3 grid(rows, n_heads + 2 * n_kv_heads), block(head_dim / 2);
-    if (dtype == SAMD_F16) hipLaunchKernelGGL(k_rope_kv<_Float16>, grid, block, 0, st, (const _Float16 *)d_qkv, d_rel_pos, d_cache_length, d_n, d_cos, d_sin, (_Float16 *)d_q_out, (_Float16 *)d_k_cache, (_Float16 *)d_v_cache, n_heads, n_kv_heads, head_dim, (long long)max_len, max_pos, n_partials, (long long)partial_stride, v_transposed, d_cs);
-    else if (dtype == SAMD_BF16) hipLaunchKernelGGL(k_rope_kv<__bf16>, grid, block, 0, st, (const __bf16 *)d_qkv, d_rel_pos, d_cache_length, d_n, d_cos, d_sin, (__bf16 *)d_q_out, (__bf16 *)d_k_cache, (__bf16 *)d_v_cache, n_heads, n_kv_heads, head_dim, (long long)max_len, max_pos, n_partials, (long long)partial_stride, v_transposed, d_cs);
+    if (dtype == SAMD_F16) hipLaunchKernelGGL((k_rope_kv<_Float16, false>), grid, block, 0, st, (const _Float16 *)d_qkv, d_rel_pos, d_cache_length, d_n, d_cos, d_sin, (_Float16 *)d_q_out, (_Float16 *)d_k_cache, (_Float16 *)d_v_cache, n_heads, n_kv_heads, head_dim, (long long)max_len, max_pos, n_partials, (long long)partial_stride, v_transposed, d_cs, QkvEpi<_Float16>{});
+    else if (dtype == SAMD_BF16) hipLaunchKernelGGL((k_rope_kv<__bf16, false>), grid, block, 0, st, (const __bf16 *)d_qkv, d_rel_pos, d_cache_length, d_n, d_cos, d_sin, (__bf16 *)d_q_out, (__bf16 *)d_k_cache, (__bf16 *)d_v_cache, n_heads, n_kv_heads, head_dim, (long long)max_len, max_pos, n_partials, (long long)partial_stride, v_transposed, d_cs, QkvEpi<__bf16>{});
     else { samd_set_error("samd_rope_kv_write: dtype must be f16/bf16"); return SAMD_E_INVALID; }
     LAUNCHCHK();
     return SAMD_OK;
@@ -462,6 +568,68 @@ int samd_rope_kv_write_cs_vt(const void *d_qkv, const int32_t *d_rel_pos, const 
     if (!d_vt_cache) { samd_set_error("samd_rope_kv_write_cs_vt: null pointer"); return SAMD_E_INVALID; }
     return rope_kv_write(d_qkv, d_rel_pos, d_cache_length, d_n, nullptr, nullptr, d_q_out, d_k_cache, d_vt_cache, rows, n_heads, n_kv_heads, head_dim, max_len,
                          1, dtype, n_partials, partial_stride, 1, d_cs, stream);
+}
+
+}  // extern "C"
+
+// samd_rope_kv_write_epi with a non-empty epilogue: the four forms of rope_kv_write over the EPI kernels
+template <typename T>
+static int rope_kv_write_epi(const void *d_qkv, const int32_t *d_rel_pos, const int32_t *d_cache_length, const int32_t *d_n, const float *d_cos,
+                             const float *d_sin, const float *d_cs, void *d_q_out, void *d_k_cache, void *d_v_cache, int32_t v_transposed, int32_t rows,
+                             int32_t n_heads, int32_t n_kv_heads, int64_t max_len, int32_t max_pos, int32_t n_partials, int64_t partial_stride,
+                             const QkvEpi<T> &epi, hipStream_t st) {
+    if (rows >= 128 && n_partials == 0 && !d_cs) {                     // the prompt's rows: rope_kv_write's wide form
+        if (v_transposed && d_v_cache) {
+            if (max_len % 8 != 0) { samd_set_error("samd_rope_kv_write_epi: max_len must be a multiple of 8"); return SAMD_E_INVALID; }
+            const dim3 vgrid((rows + 63) / 64, n_kv_heads);
+            if (epi.bias) hipLaunchKernelGGL(k_v_rows_to_vt_bias<T>, vgrid, dim3(256), 0, st, (const unsigned short *)d_qkv, d_cache_length, d_n,
+                                             (unsigned short *)d_v_cache, rows, n_heads, n_kv_heads, (long long)max_len, epi.bias);
+            else hipLaunchKernelGGL(k_v_rows_to_vt, vgrid, dim3(256), 0, st, (const unsigned short *)d_qkv, d_cache_length, d_n,
+                                    (unsigned short *)d_v_cache, rows, n_heads, n_kv_heads, (long long)max_len);
+            d_v_cache = nullptr;
+        }
+        const dim3 wgrid(rows, (n_heads + (d_v_cache ? 2 : 1) * n_kv_heads + 7) / 8);
+        hipLaunchKernelGGL(k_rope_kv_wide_epi<T>, wgrid, dim3(64), 0, st, (const T *)d_qkv, d_rel_pos, d_cache_length, d_n, d_cos, d_sin, (T *)d_q_out,
+                           (T *)d_k_cache, (T *)d_v_cache, n_heads, n_kv_heads, (long long)max_len, max_pos, epi);
+    } else {
+        hipLaunchKernelGGL((k_rope_kv<T, true>), dim3(rows, n_heads + 2 * n_kv_heads), dim3(64), 0, st, (const T *)d_qkv, d_rel_pos, d_cache_length, d_n,
+                           d_cos, d_sin, (T *)d_q_out, (T *)d_k_cache, (T *)d_v_cache, n_heads, n_kv_heads, 128, (long long)max_len, max_pos, n_partials,
+                           (long long)partial_stride, v_transposed, d_cs, epi);
+    }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+extern "C" {
+
+// one entry for the four forms (position tables or d_cs; row-major V or V^T) with an optional q|k|v epilogue (Qwen2 bias, Qwen3 q/k norm).
+// A null epi, or one without operands, is exactly the matching entry above.
+int samd_rope_kv_write_epi(const void *d_qkv, const int32_t *d_rel_pos, const int32_t *d_cache_length, const int32_t *d_n,
+                           const float *d_cos, const float *d_sin, const float *d_cs, void *d_q_out, void *d_k_cache, void *d_v_cache,
+                           int32_t v_transposed, int32_t rows, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t max_len,
+                           int32_t max_pos, int32_t dtype, int32_t n_partials, int64_t partial_stride, const samd_qkv_epilogue_t *epi, void *stream) {
+    if (v_transposed != 0 && v_transposed != 1) { samd_set_error("samd_rope_kv_write_epi: v_transposed must be 0 or 1"); return SAMD_E_INVALID; }
+    if (d_cs && (d_cos || d_sin)) { samd_set_error("samd_rope_kv_write_epi: pass the position tables or d_cs, not both"); return SAMD_E_INVALID; }
+    const bool any = epi && (epi->d_bias || epi->d_q_norm || epi->d_k_norm);
+    if (!any)
+        return rope_kv_write(d_qkv, d_rel_pos, d_cache_length, d_n, d_cos, d_sin, d_q_out, d_k_cache, d_v_cache, rows, n_heads, n_kv_heads, head_dim,
+                             max_len, d_cs ? 1 : max_pos, dtype, n_partials, partial_stride, v_transposed, d_cs, stream);
+    if (head_dim != 128 || (dtype != SAMD_F16 && dtype != SAMD_BF16) || (!epi->d_q_norm) != (!epi->d_k_norm) ||
+        (epi->d_q_norm && !(epi->eps >= 0.f && epi->eps < 1.f))) {
+        samd_set_error("samd_rope_kv_write_epi: invalid epilogue (head_dim 128, f16/bf16, q and k norm weights together, 0 <= eps < 1)"); return SAMD_E_INVALID;
+    }
+    if (!d_qkv || !d_rel_pos || !d_cache_length || !d_n || ((!d_cos || !d_sin) && !d_cs) || !d_q_out || !d_k_cache || (!d_v_cache && !v_transposed) ||
+        rows < 1 || n_heads < 1 || n_kv_heads < 1 || max_len < 1 || (!d_cs && max_pos < 1) || n_partials < 0 || (n_partials > 0 && partial_stride < 1)) {
+        samd_set_error("samd_rope_kv_write_epi: invalid argument"); return SAMD_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == SAMD_F16)
+        return rope_kv_write_epi<_Float16>(d_qkv, d_rel_pos, d_cache_length, d_n, d_cos, d_sin, d_cs, d_q_out, d_k_cache, d_v_cache, v_transposed, rows,
+                                           n_heads, n_kv_heads, max_len, d_cs ? 1 : max_pos, n_partials, partial_stride,
+                                           QkvEpi<_Float16>{(const _Float16 *)epi->d_bias, (const _Float16 *)epi->d_q_norm, (const _Float16 *)epi->d_k_norm, epi->eps}, st);
+    return rope_kv_write_epi<__bf16>(d_qkv, d_rel_pos, d_cache_length, d_n, d_cos, d_sin, d_cs, d_q_out, d_k_cache, d_v_cache, v_transposed, rows,
+                                     n_heads, n_kv_heads, max_len, d_cs ? 1 : max_pos, n_partials, partial_stride,
+                                     QkvEpi<__bf16>{(const __bf16 *)epi->d_bias, (const __bf16 *)epi->d_q_norm, (const __bf16 *)epi->d_k_norm, epi->eps}, st);
 }
 
 int samd_silu_mul(const void *d_gate_up, void *d_out, int32_t rows, int32_t inter, int32_t dtype, int32_t n_partials,

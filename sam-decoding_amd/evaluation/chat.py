@@ -191,13 +191,20 @@ def console_reader(multiline: bool) -> Callable[[str], Optional[str]]:
     return read
 
 
+def load_lm(path: str, dtype=None, device: str = "cuda"):
+    """the checkpoint's own model class (AutoModelForCausalLM: LlamaForCausalLM, Qwen2ForCausalLM, Qwen3ForCausalLM, ...).  Loading a Qwen
+    checkpoint into LlamaForCausalLM would drop its q|k|v biases / q-k norm weights as unexpected keys, which nothing downstream could see."""
+    import torch
+    from transformers import AutoModelForCausalLM
+    return AutoModelForCausalLM.from_pretrained(path, torch_dtype=dtype or torch.float16, low_cpu_mem_usage=True, device_map=device)
+
+
 def run_console(args, build_model: Callable[[object, object], object], baseline: bool = False):
     """load the HF model + tokenizer, build the SamdModel through `build_model(lm, tokenizer)`, run the REPL"""
     import sys
-    import torch
-    from transformers import AutoTokenizer, LlamaForCausalLM
+    from transformers import AutoTokenizer
     from samd_sam_only import SamdGenerationConfig
-    lm = LlamaForCausalLM.from_pretrained(args.model, torch_dtype=torch.float16, low_cpu_mem_usage=True, device_map="cuda")
+    lm = load_lm(args.model)
     tokenizer = AutoTokenizer.from_pretrained(args.model)
     samd_model = build_model(lm, tokenizer)
     session = ChatSession(args.conv_template or args.model, args.conv_system_msg, keep_history=not args.no_history)

@@ -18,7 +18,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model-path", required=True)
     ap.add_argument("--model-id", default="vicuna-7b-v1.3-samd")
-    ap.add_argument("--model-type", default="vicuna", choices=["vicuna", "llama3"])
+    ap.add_argument("--model-type", default="vicuna", choices=["vicuna", "llama3", "qwen"])
     ap.add_argument("--sam-path", default=None)
     ap.add_argument("--question-file", required=True)
     ap.add_argument("--question-begin", type=int, default=None)

@@ -1,7 +1,7 @@
 """Conversation templates (the reference takes them from FastChat: eval_vicuna.py:99-105, eval_llama3.py).
 
 `vicuna` is FastChat's "vicuna_v1.1" (system sentence, roles USER/ASSISTANT, separators " " and "</s>"), which is what
-`get_conversation_template("vicuna")` resolves to; `llama3` is Meta's Llama-3-Instruct header format."""
+`get_conversation_template("vicuna")` resolves to; `llama3` is Meta's Llama-3-Instruct header format; `qwen` is ChatML (Qwen2 / Qwen2.5 / Qwen3)."""
 from typing import List, Optional
 
 
@@ -52,10 +52,31 @@ class Llama3Conversation(Conversation):
         return out
 
 
+class ChatMLConversation(Conversation):
+    """ChatML, the format of the Qwen2 / Qwen2.5 / Qwen3 chat models: <|im_start|>role\ncontent<|im_end|>\n per message, the open
+    assistant turn last"""
+    name = "qwen"
+    roles = ("user", "assistant")
+    system = ""
+    stop_str = "<|im_end|>"
+
+    def get_prompt(self) -> str:
+        out = ""
+        if self.system:
+            out += "<|im_start|>system\n" + self.system + "<|im_end|>\n"
+        for role, message in self.messages:
+            out += "<|im_start|>" + role + "\n"
+            if message:
+                out += message + "<|im_end|>\n"
+        return out
+
+
 def get_conversation_template(name: str) -> Conversation:
     key = name.lower()
     if "llama-3" in key or "llama3" in key:
         return Llama3Conversation()
+    if "qwen" in key or "chatml" in key:
+        return ChatMLConversation()
     if "vicuna" in key:
         return VicunaConversation()
     raise ValueError(f"no conversation template for '{name}'")

@@ -229,6 +229,22 @@ class Eagle2Head(torch.nn.Module):
         return draft_tokens, parents
 
 
+def _base_has_qkv_epilogue(lm, runner):
+    """True for a Qwen2 / Qwen3-style base model (q|k|v bias or q / k norm), given as a LlamaRunner (or a wrapper of one) or as the HF module
+    itself, whose runner does not exist yet when the draft plugin is made"""
+    if runner is not None and hasattr(runner, "qkv_epilogue"):
+        return bool(runner.qkv_epilogue)
+    layers = getattr(getattr(lm, "model", None), "layers", None)
+    if layers is None:
+        return False
+    from samd_hip import SamdError
+    from samd_hip.llama import LlamaRunner
+    try:
+        return any(LlamaRunner._hf_layer_extras(layers))
+    except SamdError:                       # a module the runner rejects anyway, with its own message, when it is built
+        return False
+
+
 class Eagle2(TreeModel):
     """TreeModel plugin over Eagle2Head (reference wrapper: eagle2.py:12-70)."""
     fused = False
@@ -253,6 +269,9 @@ class Eagle2(TreeModel):
         """the head on the library's kernels when the base model runs on them too (a samd_hip LlamaRunner, possibly wrapped);
         SAMD_EAGLE_DEVICE_HEAD=0 keeps the PyTorch forward"""
         runner = lm if hasattr(lm, "forward_rows") else getattr(lm, "runner", None)
+        if _base_has_qkv_epilogue(lm, runner):
+            from samd_hip import SamdError
+            raise SamdError("EAGLE / EAGLE-2 draft heads are supported on Llama base models only (this base model has a q|k|v bias or q / k norm)")
         if runner is None or not hasattr(runner, "forward_rows") or os.environ.get("SAMD_EAGLE_DEVICE_HEAD", "1") == "0":
             return None
         if self.model.head_dim != 128 or str(self.model.device).startswith("cpu"):

@@ -56,6 +56,11 @@ class Warm(C.Structure):
                 ("delay", C.c_int32), ("where", C.c_int32)]
 
 
+class QkvEpilogue(C.Structure):
+    """samd_qkv_epilogue_t: q|k|v bias and per-head q / k RMSNorm weights in front of the RoPE (include/samd_hip.h)"""
+    _fields_ = [("d_bias", C.c_void_p), ("d_q_norm", C.c_void_p), ("d_k_norm", C.c_void_p), ("eps", C.c_float)]
+
+
 class VerdictHost(C.Structure):
     """samd_verdict_host_t"""
     _fields_ = [("best", C.c_int32), ("accept", C.c_int32), ("next_node", C.c_int32), ("next_token", C.c_int32),
@@ -148,6 +153,8 @@ _PROTOS = {
     "samd_rope_kv_write_cs": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _I64, _VP]),
     "samd_rope_kv_write_cs_vt": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _I64, _VP]),
     "samd_rope_kv_write_vt": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _I32, _I64, _VP]),
+    "samd_rope_kv_write_epi": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _I32, _I64,
+                                         _VP, _VP]),
     "samd_kv_compact_vt": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I64, _I32, _I32, _VP]),
     "samd_kv_compact_indices_vt": (C.c_int, [_VP, _I32, _I32, _I32, _I64, _I32, _I32, _I32, _VP, _I32, _VP]),
     "samd_posterior_sampled": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I64, _VP, _I32, _VP, _VP, _VP]),

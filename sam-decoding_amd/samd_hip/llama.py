@@ -15,7 +15,7 @@ import os
 
 import torch
 
-from . import (F16, BF16, MAX_DRAFT, TILE_ROWS, SamdError, Session, Warm, _ptr, check, current_stream, lib, require_gpu,
+from . import (F16, BF16, MAX_DRAFT, TILE_ROWS, QkvEpilogue, SamdError, Session, Warm, _ptr, check, current_stream, lib, require_gpu,
                torch_dtype_code)
 from . import fp8 as F8
 
@@ -49,9 +49,13 @@ def _cfg_get(cfg, name, default=None):
 
 
 class LlamaShape:
-    """the architecture numbers the runner needs (subset of transformers.LlamaConfig)."""
+    """the architecture numbers the runner needs (subset of transformers.LlamaConfig, Qwen2Config, Qwen3Config).
 
-    def __init__(self, cfg):
+    qkv_bias: q|k|v carry a bias (Qwen2 / Qwen2.5); qk_norm: q and k go through a per-head RMSNorm before the RoPE (Qwen3).  Both default to
+    what the config's model_type implies; from_hf passes what the module actually holds.  Raises SamdError for what the runner does not run:
+    sliding-window layers, an o_proj bias, MLP biases, head_dim != 128."""
+
+    def __init__(self, cfg, qkv_bias=None, qk_norm=None):
         self.hidden = int(_cfg_get(cfg, "hidden_size"))
         self.inter = int(_cfg_get(cfg, "intermediate_size"))
         self.layers = int(_cfg_get(cfg, "num_hidden_layers"))
@@ -71,6 +75,16 @@ class LlamaShape:
         self.rope_scaling = dict(rp) if isinstance(rp, dict) else {}
         if self.head_dim != 128:
             raise SamdError("the gfx950 tree-attention kernel is specialised for head_dim 128 (Vicuna-7B / Llama-3-8B)")
+        self.model_type = str(_cfg_get(cfg, "model_type", None) or "llama")
+        layer_types = _cfg_get(cfg, "layer_types", None) or ()
+        if _cfg_get(cfg, "use_sliding_window", False) or any(t != "full_attention" for t in layer_types):
+            raise SamdError("sliding-window attention layers are not supported (use_sliding_window / layer_types)")
+        if _cfg_get(cfg, "attention_bias", False):
+            raise SamdError("attention_bias=True puts a bias on o_proj, which the runner does not support (q|k|v biases alone are)")
+        if _cfg_get(cfg, "mlp_bias", False):
+            raise SamdError("MLP projection biases (mlp_bias=True) are not supported")
+        self.qkv_bias = (self.model_type == "qwen2") if qkv_bias is None else bool(qkv_bias)
+        self.qk_norm = (self.model_type == "qwen3") if qk_norm is None else bool(qk_norm)
 
     def inv_freq(self):
         """rotary inverse frequencies incl. the 'llama3' scaling rule (what HF's ROPE_INIT_FUNCTIONS computes)."""
@@ -146,6 +160,12 @@ class LlamaRunner:
         self.attention = attention or os.environ.get("SAMD_ATTENTION", "split")
         if self.attention not in ("split", "split2", "split3", "block"):
             raise SamdError(f"unknown attention mode '{self.attention}'")
+        # Qwen2 q|k|v bias / Qwen3 q / k norm: applied by samd_rope_kv_write_epi between the q|k|v product and the RoPE, so only the forms whose
+        # RoPE runs there exist: "split" / "split3", the split-K (or library) q|k|v projection -- no fused q|k|v tiles, no norm-fold forward
+        self.qkv_epilogue = bool(s.qkv_bias or s.qk_norm)
+        if self.qkv_epilogue and self.attention not in ("split", "split3"):
+            raise SamdError(f"attention mode '{self.attention}' rotates q / k inside its own kernel, which has no q|k|v bias or q / k norm: "
+                            f"use 'split' or 'split3' for this model")
         # round 6: "split" / "split3" keep V TRANSPOSED too ([H_kv][D][max_len]) wherever the cache length allows 16-byte loads along it: at <= 16 rows
         # samd_tree_attention_vt then runs one wave per (head, KV split) that feeds its MFMAs straight from the V^T rows -- no LDS staging, no
         # workgroup barrier, 11.9 -> 11.0 us per layer at 8 rows (profiles/r06_attention.md).  SAMD_V_LAYOUT=rows keeps the row-major cache (A/B).
@@ -182,7 +202,8 @@ class LlamaRunner:
             # fused launch only equals split-K + k_rope_kv there, but it is what the norm-fold forward builds on)
             n_cols = heads_total * 128
             enough = n_cols // 64 >= 128 or (n_cols % 48 == 0 and n_cols // 48 >= 128)
-            if (not streams(t) or self.attention != "split" or (not enough and mode != "force") or s.head_dim != 128 or mode == "0"):
+            if (not streams(t) or self.attention != "split" or (not enough and mode != "force") or s.head_dim != 128 or mode == "0"
+                    or self.qkv_epilogue):
                 return None
             out = torch.empty_like(t)
             check(lib().samd_gemm_pack_qkv64(_ptr(t), _ptr(out), heads_total, t.shape[1], current_stream()))
@@ -245,6 +266,27 @@ class LlamaRunner:
         self.norm_fold = (self.wp is not None and self.attention == "split"
                           and all(l.get("wo_g") is not None and l.get("wdown_g") is not None for l in self.wp["layers"]))
         self.scale = 1.0 / math.sqrt(s.head_dim)
+        # per layer: the samd_qkv_epilogue_t of samd_rope_kv_write_epi (pointers into self.w, which keeps the tensors alive), and the same
+        # without the bias for the wide prefill, whose library q|k|v product adds the bias itself
+        self.epi = self.epi_nobias = None
+        if self.qkv_epilogue:
+            def epi(l, bias):
+                return QkvEpilogue(l["bqkv"].data_ptr() if bias and l.get("bqkv") is not None else None,
+                                   l["q_norm"].data_ptr() if l.get("q_norm") is not None else None,
+                                   l["k_norm"].data_ptr() if l.get("k_norm") is not None else None, s.eps)
+            for l in weights["layers"]:
+                if s.qkv_bias != (l.get("bqkv") is not None) or s.qk_norm != (l.get("q_norm") is not None and l.get("k_norm") is not None):
+                    raise SamdError("the layer weights do not match the shape's qkv_bias / qk_norm")
+                if s.qkv_bias and tuple(l["bqkv"].shape) != ((s.heads + 2 * s.kv_heads) * s.head_dim,):
+                    raise SamdError(f"q|k|v bias of shape {tuple(l['bqkv'].shape)}")
+                if s.qk_norm and (tuple(l["q_norm"].shape) != (s.head_dim,) or tuple(l["k_norm"].shape) != (s.head_dim,)):
+                    raise SamdError("q_norm / k_norm weights must have head_dim elements")
+                for k in ("bqkv", "q_norm", "k_norm"):
+                    t = l.get(k)
+                    if t is not None and (t.dtype != dtype or t.device.type != self.device.type or not t.is_contiguous()):
+                        raise SamdError(f"{k} must be a contiguous {dtype} tensor on the GPU")
+            self.epi = [epi(l, True) for l in weights["layers"]]
+            self.epi_nobias = [epi(l, False) for l in weights["layers"]]
         self.row_major_released = f8                             # (FP8: there are no row-major projections; prefill runs in 64-row chunks)
         self._length_state(max_cache_len, kv)
         if os.environ.get("SAMD_RELEASE_ROW_MAJOR", "0") == "1":
@@ -255,7 +297,11 @@ class LlamaRunner:
         GEMMs), and the packed forms the streaming kernels read"""
         def nbytes(t):
             return 0 if t is None or t.device.type == "meta" else t.numel() * t.element_size()
-        rep = dict(row_major=sum(nbytes(t) for l in self.w["layers"] for t in l.values()) + nbytes(self.w["lm_head"]) + nbytes(self.w["embed"]))
+        epi_keys = ("bqkv", "q_norm", "k_norm")
+        rep = dict(row_major=sum(nbytes(t) for l in self.w["layers"] for k, t in l.items() if k not in epi_keys) + nbytes(self.w["lm_head"])
+                   + nbytes(self.w["embed"]))
+        if self.qkv_epilogue:                                    # Qwen2 q|k|v biases, Qwen3 q / k norm weights (model dtype, read by the RoPE launch)
+            rep["qkv_epilogue"] = sum(nbytes(l.get(k)) for l in self.w["layers"] for k in epi_keys)
         if self.wp:
             for k in ("wqkv", "wqkv64", "wo", "wo_g", "wgu", "wdown", "wdown_g"):
                 rep["packed_" + k] = sum(nbytes(l.get(k)) for l in self.wp["layers"])
@@ -369,7 +415,8 @@ class LlamaRunner:
         if F8.is_fp8_dtype(lm.lm_head.weight.dtype) or F8.is_fp8_dtype(m.embed_tokens.weight.dtype):
             raise SamdError("FP8 embedding / lm_head weights are not supported: they stay in the model dtype")
         dtype = dtype or next(p.dtype for p in lm.parameters() if not F8.is_fp8_dtype(p.dtype))
-        shape = LlamaShape(lm.config)
+        qkv_bias, qk_norm = cls._hf_layer_extras(m.layers)
+        shape = LlamaShape(lm.config, qkv_bias=qkv_bias, qk_norm=qk_norm)
         dev = torch.device(device)
 
         def get(t):
@@ -396,27 +443,66 @@ class LlamaRunner:
             return cat
         for lyr in m.layers:
             a, f = lyr.self_attn, lyr.mlp
-            for lin in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, f.gate_proj, f.up_proj, f.down_proj):
-                if getattr(lin, "bias", None) is not None:
-                    raise SamdError("LlamaRunner: projection biases are not supported")
+            extra = {}                                           # Qwen2 q|k|v bias, Qwen3 q / k norm (samd_rope_kv_write_epi)
+            if qkv_bias:
+                extra["bqkv"] = get(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias]))
+            if qk_norm:
+                extra["q_norm"], extra["k_norm"] = get(a.q_norm.weight), get(a.k_norm.weight)
             if ckpt_f8:                                          # (q, scale) as the checkpoint has them; the runner packs them
                 lw = {}
                 for k, lins in (("wqkv", (a.q_proj, a.k_proj, a.v_proj)), ("wo", (a.o_proj,)), ("wgu", (f.gate_proj, f.up_proj)), ("wdown", (f.down_proj,))):
                     lw[k], lw[k + "_scale"] = F8.fuse_fp8([F8.linear_fp8(x) for x in lins], dev)
-                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight)))
+                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
                 continue
             layers.append(dict(
                 wqkv=fuse((a.q_proj, a.k_proj, a.v_proj)),
                 wo=get(a.o_proj.weight),
                 wgu=fuse((f.gate_proj, f.up_proj)),
                 wdown=get(f.down_proj.weight),
-                ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight)))
+                ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
         weights = dict(embed=get(m.embed_tokens.weight), layers=layers, norm=get(m.norm.weight), lm_head=get(lm.lm_head.weight))
         if shared[0]:
             import logging
             logging.getLogger("samd_hip").info("LlamaRunner.from_hf: %d fused projection groups now back the HF module's q/k/v and gate/up "
                                                "weights (share_weights); its parameters are views of the runner's matrices", shared[0])
         return cls(shape, weights, max_cache_len, dtype, device, weight_format=weight_format, **kw)
+
+    # the parameters of a decoder layer that from_hf reads (named_parameters; FP8 checkpoints' weight_scale tensors are buffers)
+    _LAYER_PARAMS = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
+                     "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight", "input_layernorm.weight", "post_attention_layernorm.weight")
+    _QKV_BIAS = ("self_attn.q_proj.bias", "self_attn.k_proj.bias", "self_attn.v_proj.bias")
+    _QK_NORM = ("self_attn.q_norm.weight", "self_attn.k_norm.weight")
+
+    @classmethod
+    def _hf_layer_extras(cls, layers):
+        """(qkv_bias, qk_norm) of an HF decoder stack (Llama, Qwen2, Qwen3).  Every layer's named parameters must be exactly the set the runner
+        consumes: the Llama ones, plus q|k|v biases, plus q / k norm weights, the same in every layer (an FP8 projection's weight_scale /
+        input_scale count as its own, whether buffers or parameters).  Anything else -- an o_proj or MLP bias, a parameter the runner would
+        not read -- raises instead of being dropped."""
+        if len(layers) == 0:
+            raise SamdError("the model has no decoder layers")
+        def names_of(lyr):
+            # an FP8 projection's scales may be parameters as well as buffers (fbgemm / compressed-tensors layers): the runner reads
+            # weight_scale through samd_hip/fp8.py (input scales are not used: weight-only FP8), so they are not extra parameters
+            skip = {f"{n[:-len('.weight')]}.{sc}" for n, p in lyr.named_parameters() if n.endswith(".weight") and F8.is_fp8_dtype(p.dtype)
+                    for sc in ("weight_scale", "input_scale")}
+            return {n for n, _ in lyr.named_parameters()} - skip
+        names0 = names_of(layers[0])
+        qkv_bias = any(n in names0 for n in cls._QKV_BIAS)
+        qk_norm = any(n in names0 for n in cls._QK_NORM)
+        want = set(cls._LAYER_PARAMS) | (set(cls._QKV_BIAS) if qkv_bias else set()) | (set(cls._QK_NORM) if qk_norm else set())
+        for i, lyr in enumerate(layers):
+            names = names_of(lyr)
+            if names == want:
+                continue
+            extra, missing = sorted(names - want), sorted(want - names)
+            if "self_attn.o_proj.bias" in extra:
+                raise SamdError(f"layer {i}: o_proj bias is not supported (q|k|v biases are)")
+            if any(n.startswith("mlp.") and n.endswith(".bias") for n in extra):
+                raise SamdError(f"layer {i}: MLP projection biases are not supported")
+            raise SamdError(f"layer {i}: parameters the runner does not consume {extra}, or lacks {missing} "
+                            f"(it reads the Llama layer, q|k|v biases (Qwen2) and q / k norm weights (Qwen3))")
+        return qkv_bias, qk_norm
 
     @classmethod
     def random_init(cls, cfg, max_cache_len, dtype=torch.float16, device="cuda", seed=0, std=0.02, weight_format=None, **kw):
@@ -432,6 +518,16 @@ class LlamaRunner:
         layers = [dict(wqkv=rnd(qkv_out, s.hidden), wo=rnd(s.hidden, s.heads * s.head_dim), wgu=rnd(2 * s.inter, s.hidden),
                        wdown=rnd(s.hidden, s.inter), ln1=torch.ones(s.hidden, dtype=dtype, device=device),
                        ln2=torch.ones(s.hidden, dtype=dtype, device=device)) for _ in range(s.layers)]
+
+        def norm_w():                                            # +-[0.5, 2]: a weight on the wrong channel or a skipped norm shows
+            mag = 0.5 + 1.5 * torch.rand(s.head_dim, generator=g, device=device)
+            sign = torch.where(torch.rand(s.head_dim, generator=g, device=device) < 0.5, -1.0, 1.0)
+            return (mag * sign).to(dtype)
+        for l in layers:
+            if s.qkv_bias:
+                l["bqkv"] = (torch.randn(qkv_out, generator=g, device=device, dtype=torch.float32) * 0.5).to(dtype)
+            if s.qk_norm:
+                l["q_norm"], l["k_norm"] = norm_w(), norm_w()
         weights = dict(embed=rnd(s.vocab, s.hidden), layers=layers, norm=torch.ones(s.hidden, dtype=dtype, device=device),
                        lm_head=rnd(s.vocab, s.hidden))
         return cls(shape, weights, max_cache_len, dtype, device, weight_format=_env_weight_format(weight_format), **kw)
@@ -570,6 +666,13 @@ class LlamaRunner:
             else:
                 if fused_qkv:
                     pass
+                elif self.epi is not None:
+                    # Qwen2 / Qwen3: bias and q / k norm between the product (split-K partials, one split, or the 128-row library GEMM) and the RoPE
+                    cs_form = self.attention == "split"
+                    check(L.samd_rope_kv_write_epi(
+                        _ptr(src), _ptr(d_relpos), _ptr(d_L), _ptr(d_n), None if cs_form else _ptr(self.cos), None if cs_form else _ptr(self.sin),
+                        _ptr(b["cs"]) if cs_form else None, _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), int(vt), R, s.heads,
+                        s.kv_heads, s.head_dim, self.max_len, self.rope_rows, dt, n_p, stride, C.byref(self.epi[li]), st))
                 elif self.attention == "split":
                     check((L.samd_rope_kv_write_cs_vt if vt else L.samd_rope_kv_write_cs)(
                         _ptr(src), _ptr(d_relpos), _ptr(d_L), _ptr(d_n), _ptr(b["cs"]), _ptr(b["q"]), _ptr(self.kv[li, 0]),
@@ -736,13 +839,16 @@ class LlamaRunner:
         rest = -(-(M - R) // 64) * 64
         return R if self._pf_plan.get(key, {}).get(R, {}).get(rest, False) else 0
 
-    def _pf_mm(self, x, w, out, key):
+    def _pf_mm(self, x, w, out, key, bias=None):
+        """out = x @ w.T (+ bias: HF's own nn.Linear arithmetic, torch.addmm -- the q|k|v of Qwen2, whose V may go to the cache or to SDPA
+        without passing the RoPE kernel's per-element path)"""
         R = self._pf_split(key, x.shape[0])
+        mm = torch.mm if bias is None else (lambda a, b, out: torch.addmm(bias, a, b, out=out))
         if R:
-            torch.mm(x[:R], w.t(), out=out[:R])
-            torch.mm(x[R:], w.t(), out=out[R:])
+            mm(x[:R], w.t(), out=out[:R])
+            mm(x[R:], w.t(), out=out[R:])
         else:
-            torch.mm(x, w.t(), out=out)
+            mm(x, w.t(), out=out)
 
     def _prefill_wide(self, session: Session, ids, on_chunk=None):
         """the whole prompt in one pass: compute-bound, so the GEMMs go to the library (N x K x N_out at full MFMA rate) and
@@ -781,8 +887,17 @@ class LlamaRunner:
         delta = None
         for li, w in enumerate(self.w["layers"]):
             check(L.samd_rmsnorm(_ptr(x), _ptr(delta), _ptr(w["ln1"]), _ptr(h), N, s.hidden, s.eps, dt, 0, 0, st))
-            self._pf_mm(h, w["wqkv"], qkv, "wqkv")
-            if self.v_transposed:
+            self._pf_mm(h, w["wqkv"], qkv, "wqkv", bias=w.get("bqkv"))
+            if self.epi is not None:
+                # Qwen2 / Qwen3: the bias is already in the product; q / k norm (if any) in front of the RoPE
+                check(L.samd_rope_kv_write_epi(_ptr(qkv), _ptr(relpos), _ptr(d_L), _ptr(d_n), _ptr(self.cos), _ptr(self.sin), None, _ptr(q),
+                                               _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), int(self.v_transposed), N, s.heads, s.kv_heads,
+                                               s.head_dim, self.max_len, self.rope_rows, dt, 0, 0, C.byref(self.epi_nobias[li]), st))
+                if self.v_transposed:
+                    vv = qkv_p[:, (s.heads + s.kv_heads) * s.head_dim:].view(Np, s.kv_heads, s.head_dim).transpose(0, 1)
+                else:
+                    vv = self.kv[li, 1][:, :Np]
+            elif self.v_transposed:
                 check(L.samd_rope_kv_write_vt(_ptr(qkv), _ptr(relpos), _ptr(d_L), _ptr(d_n), _ptr(self.cos), _ptr(self.sin), _ptr(q),
                                               _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), N, s.heads, s.kv_heads, s.head_dim, self.max_len,
                                               self.rope_rows, dt, 0, 0, st))                                         # q, K rows, V^T columns of the cache
