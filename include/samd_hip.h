@@ -648,6 +648,19 @@ int samd_gemm_skinny_groups(const void *d_A, const void *d_Wg, int32_t rows_pad,
 int samd_gemm_pack_f8(const void *d_W8, void *d_out, int32_t N, int32_t K, void *stream);
 int samd_gemm_skinny_f8(const void *d_A, const void *d_W8p, const float *d_scale, int32_t rows_pad, int32_t N, int32_t K, int32_t splits,
                         float *d_partial, void *d_out, int32_t dtype, void *stream);
+/* MXFP4 weight-only projections (OCP Microscaling: e2m1 elements, two per byte with the low nibble first, one e8m0 scale 2^(e8 - 127) per 32
+ * elements along k; no per-row or per-tensor scale):
+ *   samd_gemm_pack_f4     row-major q [N][K/2] bytes + e8 [N][K/32] codes -> ONE buffer of N * K / 2 + N * K / 32 bytes: per (128-column tile,
+ *                         256-k chunk) a 17 KiB block, 16 KiB of elements followed by their 1 KiB of scales (layout: csrc/gemm_kernels.hip).
+ *                         N % 128 == 0, K % 256 == 0, d_out distinct from both inputs.
+ *   samd_gemm_skinny_f4   out[m][n] = sum_k A[m][k] * fp4(q[n][k]) * 2^(e8[n][k/32] - 127): A in the model dtype (dtype), fp32 accumulation, the
+ *                         block scale applied by the widening conversion (exact in the model dtype for the exponents samd_hip/mxfp4.py admits),
+ *                         nothing in the epilogue.  splits == 1: d_out [rows_pad][N] in the model dtype (one rounding); otherwise fp32 partials
+ *                         [splits][rows_pad][N] in d_partial, the layout of samd_gemm_skinny.  Arguments as samd_gemm_skinny's (rows 16/32/48/64,
+ *                         N % 128, K % 256, 1 <= splits <= K / 256); the scales travel inside d_W4p. */
+int samd_gemm_pack_f4(const void *d_q, const void *d_e8, void *d_out, int32_t N, int32_t K, void *stream);
+int samd_gemm_skinny_f4(const void *d_A, const void *d_W4p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
+                        int32_t dtype, void *stream);
 
 /* ---- scripted verifier (tests, smoke and bench only): replaces the LM arg-max of every draft node by
  * the next token of a target stream while the node's context (committed history + root->node path) is a

@@ -1389,3 +1389,246 @@ int samd_gemm_skinny_f8(const void *d_A, const void *d_W8p, const float *d_scale
 }
 
 }  // extern "C"
+
+// ================================================================================================
+// MXFP4 (OCP Microscaling: e2m1 elements, one e8m0 scale per 32 elements along k) weight-only projection:
+// out[m][n] = sum_k A[m][k] * fp4(q[n][k]) * 2^(e8[n][k / 32] - 127), A in the model dtype.  Same grid, A staging and MFMA sequence as
+// k_gemm_skinny_f8; the weight load, the conversion, the k permutation and the packed layout differ, and the stream moves 4.25 bits per weight.
+//   PACKED LAYOUT (samd_gemm_pack_f4): block (tile t = 128 columns, chunk c = 256 k) is 17 KiB contiguous at (t * K/256 + c) * 17408 bytes:
+//   16 KiB of elements, then 1 KiB of scales.  Element unit j * 512 + tid (16 bytes, j = 0, 1) holds the row-major bytes of
+//   q[128 t + 16 w + n][256 c + 128 j + 32 g .. +31] for tid = 64 w + 16 g + n (byte i: low nibble k + 2 i, high nibble k + 2 i + 1) --
+//   exactly one MX block, so a lane's unit converts with one scale.  Scale byte 16384 + 2 tid + j is e8[128 t + 16 w + n][8 c + 4 j + g]:
+//   a lane fetches the two scales of its two units of a chunk in one 2-byte nt load, once per chunk (3 + XV memory operations per chunk).
+// dword i of a unit is the 8-element MFMA operand k + 8 i .. + 7, so the A-side reads unit (16 j + 4 g + i) ^ n of row n.
+// v_cvt_scalef32_pk_{f16,bf16}_fp4 widens two nibbles WITH the block scale (the float whose bits are e8 << 23): fp4 * 2^e is exact in the
+// model dtype over the exponent range samd_hip/mxfp4.py admits, so the MFMA sees the weights without error and the epilogue applies nothing.
+// DEPTH (chunks of 16 KiB + 1 KiB in flight per workgroup): 16 rows 8 (136 KiB; 9 A buffers = 72 KiB of LDS, two workgroups per CU),
+// 32 rows 4 (5 buffers = 80 KiB, two workgroups per CU), 48 rows 5 (6 buffers = 144 KiB), 64 rows 3 (4 buffers = 128 KiB).  The only
+// inline assembly beyond k_gemm_skinny_f8's forms is the 2-byte sibling of its weight load, global_load_ushort ... nt, for the scales.
+// ================================================================================================
+template <typename TT> struct F4Widen;
+template <> struct F4Widen<GF16> {
+    static __device__ __forceinline__ half8 cvt(unsigned w, float s) {
+        const auto a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 1);
+        const auto c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 2), d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 3);
+        return __builtin_bit_cast(half8, (u32x4){__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d)});
+    }
+};
+template <> struct F4Widen<GBF16> {
+    static __device__ __forceinline__ bf16x8 cvt(unsigned w, float s) {
+        const auto a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 1);
+        const auto c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 2), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 3);
+        return __builtin_bit_cast(bf16x8, (u32x4){__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d)});
+    }
+};
+
+// gemm_wait_younger for pipelines deeper than 4 chunks: wait until at most min(younger, DEPTH - 1) * PC memory operations are outstanding
+template <int DEPTH, int PC>
+__device__ __forceinline__ void gemm_wait_younger_deep(int younger) {
+    static_assert(DEPTH <= 8 && (DEPTH - 1) * PC <= 63, "vmcnt is a 6-bit counter");
+#define SAMD_WAIT_IF(i) if (DEPTH > i && younger >= i) { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(DEPTH > i ? i * PC : 0) : "memory"); return; }
+    SAMD_WAIT_IF(7) SAMD_WAIT_IF(6) SAMD_WAIT_IF(5) SAMD_WAIT_IF(4) SAMD_WAIT_IF(3) SAMD_WAIT_IF(2) SAMD_WAIT_IF(1)
+#undef SAMD_WAIT_IF
+    asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+}
+
+// two A operands (16-byte units at a0, a1 of this lane's row) for each of the RT row tiles, as k_gemm_skinny_f8 reads them
+template <int RT>
+__device__ __forceinline__ void gemm_f4_read_a(u32x4 (&r)[RT][2], uint32_t a0, uint32_t a1) {
+    if constexpr (RT == 1)
+        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r[0][0]), "=&v"(r[0][1]) : "v"(a0), "v"(a1));
+    else if constexpr (RT == 2)
+        asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %4 offset:8192\n\tds_read_b128 %3, %5 offset:8192\n\t"
+                     "s_waitcnt lgkmcnt(0)" : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]) : "v"(a0), "v"(a1));
+    else if constexpr (RT == 3)
+        asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %7\n\tds_read_b128 %2, %6 offset:8192\n\tds_read_b128 %3, %7 offset:8192\n\t"
+                     "ds_read_b128 %4, %6 offset:16384\n\tds_read_b128 %5, %7 offset:16384\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[2][0]), "=&v"(r[2][1]) : "v"(a0), "v"(a1));
+    else
+        asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %8 offset:8192\n\tds_read_b128 %3, %9 offset:8192\n\t"
+                     "ds_read_b128 %4, %8 offset:16384\n\tds_read_b128 %5, %9 offset:16384\n\tds_read_b128 %6, %8 offset:24576\n\t"
+                     "ds_read_b128 %7, %9 offset:24576\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[2][0]), "=&v"(r[2][1]), "=&v"(r[3][0]), "=&v"(r[3][1])
+                     : "v"(a0), "v"(a1));
+}
+
+template <typename TT, int RT, int DEPTH>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_f4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4,
+                                                                     float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
+                                                                     int n_chunks, int n_splits) {
+    typedef typename TT::elem E;
+    constexpr int R = 16 * RT;
+    constexpr int NT = 64 * GEMM_WAVES;
+    constexpr int XV = (R * 32) / NT;              // 16-byte units per thread to stage one A chunk (as k_gemm_skinny)
+    constexpr int NB = DEPTH + 1;
+    constexpr int PC = 3 + XV;                     // memory operations per thread and chunk: 2 element loads + 1 scale load + the A staging
+    constexpr size_t WCH = 17408, WU = 8192, WS = 16384;   // bytes of one (tile, chunk) block; of one j row inside it; offset of its scales
+    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
+    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
+
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
+    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    const int split = blockIdx.y;
+    const int c0 = (int)((long long)split * n_chunks / n_splits), c1 = (int)((long long)(split + 1) * n_chunks / n_splits);
+    const char *wtile = reinterpret_cast<const char *>(W4) + (size_t)blockIdx.x * n_chunks * WCH;
+    const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)tid * 2;
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
+
+    floatx4 acc[RT];
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+
+    // hand-issued nt weight and scale loads, counted waits and bare barriers: see k_gemm_skinny.  The destination registers are defined
+    // once, up front, and every load is an in-out ("+v") of that value: a load that a short split skips then leaves the SAME register
+    // behind, so the compiler has no two values to merge with a copy -- a v_mov of a register whose load is still in flight would move
+    // stale bits and leave the landing load to overwrite whatever lives there by then.
+    u32x4 wr[DEPTH][2];
+    unsigned ws[DEPTH];                            // the chunk's two e8m0 codes of this lane: bits 0-7 unit 0, bits 8-15 unit 1
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(ws[d]));
+    auto load_wj = [&](u32x4 (&dst)[2], int c, int j) {
+        const char *p = wtile + (size_t)c * WCH;
+        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[j]) : "v"(wlane), "s"(p + WU * j) : "memory");
+    };
+    auto load_s = [&](unsigned &dst, int c) {
+        const char *p = wtile + (size_t)c * WCH + WS;
+        asm volatile("global_load_ushort %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
+    };
+    auto stage_xi = [&](int c, int buf, int i) {
+        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
+        const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
+        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        asm volatile("" ::: "memory");
+    };
+    auto load_w = [&](u32x4 (&dst)[2], unsigned &sdst, int c) {
+        load_wj(dst, c, 0); load_wj(dst, c, 1); load_s(sdst, c);
+    };
+    auto stage_x = [&](int c, int buf) {
+#pragma unroll
+        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
+    };
+    auto phase = [&](u32x4 (&cur)[2], unsigned &cs, int c, int buf) {
+        gemm_wait_younger_deep<DEPTH, PC>(c1 - 1 - c);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
+        // the conversion is ordinary VALU code on the loaded registers: re-define them here, behind the counted wait (volatile asm keeps its
+        // order), so that no conversion can be scheduled above the wait while the load is still in flight
+        asm volatile("" : "+v"(cs) : : "memory");
+        const unsigned e8s = cs;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            asm volatile("" : "+v"(cur[j]) : : "memory");
+            const float sc = __builtin_bit_cast(float, ((e8s >> (8 * j)) & 0xffu) << 23);       // 2^(e8 - 127)
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int u = 16 * j + 4 * g + 2 * h;
+                const uint32_t a0 = xbase + (uint32_t)(u ^ n) * 16, a1 = xbase + (uint32_t)((u + 1) ^ n) * 16;
+                u32x4 r[RT][2];
+                gemm_f4_read_a<RT>(r, a0, a1);
+                const auto lo = F4Widen<TT>::cvt(cur[j][2 * h], sc), hi = F4Widen<TT>::cvt(cur[j][2 * h + 1], sc);
+#pragma unroll
+                for (int mt = 0; mt < RT; mt++) {
+                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
+                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, acc[mt]);
+                }
+            }
+            if (RT >= 3 && c + DEPTH < c1) {       // 48 / 64 rows: refill per unit (see k_gemm_skinny)
+                load_wj(cur, c + DEPTH, j);
+                if (j == 1) load_s(cs, c + DEPTH);
+#pragma unroll
+                for (int i = 2 * j; i < 2 * j + 2; i++)
+                    if (i < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, i);
+            }
+        }
+        if (RT < 3 && c + DEPTH < c1) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
+    };
+    if (c0 < c1) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++)
+            if (c0 + d < c1) { load_w(wr[d], ws[d], c0 + d); stage_x(c0 + d, d); }
+        int buf = 0;
+        for (int c = c0; c < c1; c += DEPTH) {
+#pragma unroll
+            for (int d = 0; d < DEPTH; d++)
+                if (c + d < c1) { phase(wr[d], ws[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+        }
+    }
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n; the block scales went in with the conversion, so ONE rounding and nothing else
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int m = 16 * mt + 4 * g + r;
+            const float v = acc[mt][r];
+            if (out) out[(size_t)m * N + n0 + n] = (E)v;
+            else __hip_atomic_store(&partial[((size_t)split * R + m) * N + n0 + n], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// row-major q [N][K/2] bytes + e8 [N][K/32] codes -> the packed blocks of k_gemm_skinny_f4; one thread moves one 16-byte unit and its scale
+__global__ __launch_bounds__(256) void k_gemm_pack_f4(const uint4 *__restrict__ q, const unsigned char *__restrict__ e8, unsigned char *__restrict__ out,
+                                                      int N, int K) {
+    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;          // element unit = MX block
+    const long long total = (long long)N * K / 32;
+    if (u >= total) return;
+    const int n_chunks = K / GEMM_KC;
+    const long long blk = u >> 10;                                          // 1024 element units per block
+    const int in = (int)(u & 1023), j = in >> 9, tid = in & 511, w = tid >> 6, g = (tid >> 4) & 3, n = tid & 15;
+    const int t = (int)(blk / n_chunks), c = (int)(blk % n_chunks);
+    const long long row = 128LL * t + 16 * w + n, mxb = 8LL * c + 4 * j + g;      // weight row; its MX block along k
+    unsigned char *dst = out + blk * 17408;
+    reinterpret_cast<uint4 *>(dst)[in] = q[row * (K / 32) + mxb];
+    dst[16384 + 2 * tid + j] = e8[row * (K / 32) + mxb];
+}
+
+template <typename TT, int RT, int DEPTH>
+static hipError_t gemm_f4_launch(dim3 grid, hipStream_t st, const void *A, const void *W4, float *partial, void *out, int K, int N, int splits) {
+    constexpr int lds = (DEPTH + 1) * 16 * RT * GEMM_KC * 2;
+    if constexpr (lds > 65536) {
+        static unsigned long long done = 0ull;                     // per-device (samd_common.h)
+        const hipError_t attr = samd_reserve_lds((const void *)k_gemm_skinny_f4<TT, RT, DEPTH>, lds, &done);
+        if (attr != hipSuccess) return attr;
+    }
+    hipLaunchKernelGGL((k_gemm_skinny_f4<TT, RT, DEPTH>), grid, dim3(64 * GEMM_WAVES), lds, st, (const typename TT::elem *)A, (const unsigned char *)W4,
+                       partial, (typename TT::elem *)out, K, N, K / GEMM_KC, splits);
+    return hipSuccess;
+}
+
+extern "C" {
+
+int samd_gemm_pack_f4(const void *d_q, const void *d_e8, void *d_out, int32_t N, int32_t K, void *stream) {
+    if (!d_q || !d_e8 || !d_out || d_q == d_out || d_e8 == d_out || N < GEMM_COLS || N % GEMM_COLS != 0 || K < GEMM_KC || K % GEMM_KC != 0) {
+        samd_set_error("samd_gemm_pack_f4: needs N %% 128 == 0, K %% 256 == 0 and distinct buffers"); return SAMD_E_INVALID;
+    }
+    const long long units = (long long)N * K / 32;
+    hipLaunchKernelGGL(k_gemm_pack_f4, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)d_q,
+                       (const unsigned char *)d_e8, (unsigned char *)d_out, N, K);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_gemm_skinny_f4(const void *d_A, const void *d_W4p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
+                        int32_t dtype, void *stream) {
+    if (!d_A || !d_W4p || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS || N % GEMM_COLS != 0 ||
+        K < GEMM_KC || K % GEMM_KC != 0 || splits < 1 || splits > K / GEMM_KC || (splits == 1 ? !d_out : !d_partial) || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("samd_gemm_skinny_f4: unsupported shape (rows 16/32/48/64, N %% 128 == 0, K %% 256 == 0) or null pointer"); return SAMD_E_INVALID;
+    }
+    const dim3 grid(N / GEMM_COLS, splits);
+    const hipStream_t st = (hipStream_t)stream;
+    float *part = splits == 1 ? nullptr : d_partial;
+    void *out = splits == 1 ? d_out : nullptr;
+#define GO(TT, RT, D) e = gemm_f4_launch<TT, RT, D>(grid, st, d_A, d_W4p, part, out, K, N, splits)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1, 8); else if (rows_pad == 32) GO(TT, 2, 4); else if (rows_pad == 48) GO(TT, 3, 5); else GO(TT, 4, 3); } while (0)
+    hipError_t e;
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
+    if (e != hipSuccess) { samd_set_error("samd_gemm_skinny_f4: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+}  // extern "C"

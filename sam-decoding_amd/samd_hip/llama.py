@@ -18,6 +18,7 @@ import torch
 from . import (F16, BF16, MAX_DRAFT, TILE_ROWS, QkvEpilogue, SamdError, Session, Warm, _ptr, check, current_stream, lib, require_gpu,
                torch_dtype_code)
 from . import fp8 as F8
+from . import mxfp4 as MX
 
 
 def _env_weight_format(weight_format):
@@ -26,20 +27,28 @@ def _env_weight_format(weight_format):
 
 
 def _weight_format(weight_format, weights, dtype):
-    """"fp8" or None (the model dtype).  Projections that arrive as float8_e4m3fn (an FP8 checkpoint) make the runner FP8 by themselves."""
+    """"fp8", "mxfp4" or None (the model dtype).  Projections that arrive as float8_e4m3fn (an FP8 checkpoint) or as packed e2m1 bytes (an
+    MXFP4 checkpoint: uint8 / float4_e2m1fn_x2 [N, K/2]) make the runner FP8 / MXFP4 by themselves."""
     has_f8 = any(l[k].dtype == torch.float8_e4m3fn for l in weights["layers"] for k in F8.PROJECTIONS if k in l)
+    has_f4 = any(_is_f4_tensor(l[k]) for l in weights["layers"] for k in MX.PROJECTIONS if k in l)
     names = {torch.float16: ("fp16", "float16", "half"), torch.bfloat16: ("bf16", "bfloat16")}.get(dtype, ())
     if weight_format is None:
-        fmt = "fp8" if has_f8 else None
-    elif weight_format == "fp8":
-        fmt = "fp8"
+        fmt = "fp8" if has_f8 else ("mxfp4" if has_f4 else None)
+    elif weight_format in ("fp8", "mxfp4"):
+        fmt = weight_format
     elif weight_format == dtype or (isinstance(weight_format, str) and weight_format.lower() in names):
         fmt = None
     else:
-        raise SamdError(f"weight_format {weight_format!r}: expected None, 'fp8' or the model dtype ({dtype})")
+        raise SamdError(f"weight_format {weight_format!r}: expected None, 'fp8', 'mxfp4' or the model dtype ({dtype})")
     if has_f8 and fmt != "fp8":
         raise SamdError(f"the weights carry float8_e4m3fn projections; weight_format {weight_format!r} would need them dequantised (pass None or 'fp8')")
+    if has_f4 and fmt != "mxfp4":
+        raise SamdError(f"the weights carry MXFP4 projections; weight_format {weight_format!r} would need them dequantised (pass None or 'mxfp4')")
     return fmt
+
+
+def _is_f4_tensor(t):
+    return t.dtype == torch.uint8 or MX.is_fp4_dtype(t.dtype)
 
 
 def _cfg_get(cfg, name, default=None):
@@ -128,16 +137,21 @@ class LlamaRunner:
         # weight_format "fp8": the four projections of every layer as OCP e4m3fn with one fp32 scale per output column (samd_hip/fp8.py),
         # streamed by samd_gemm_skinny_f8 only -- no row-major copy, no fused or norm-fold forms; embedding and lm_head stay in the model dtype
         self.weight_format = _weight_format(weight_format, weights, dtype)
-        f8 = self.weight_format == "fp8"
+        # weight_format "mxfp4": the same four projections as e2m1 elements with one e8m0 scale per 32 along K (samd_hip/mxfp4.py), streamed by
+        # samd_gemm_skinny_f4 only; everything FP8 implies for the runner holds here too (quant)
+        f8, f4 = self.weight_format == "fp8", self.weight_format == "mxfp4"
+        quant = f8 or f4
         if f8 and not native_gemm:
             raise SamdError("FP8 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'fp8'")
+        if f4 and not native_gemm:
+            raise SamdError("MXFP4 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'mxfp4'")
         s = shape
         self.w = weights
         # samd_gemm_skinny streams the weights itself where the shape allows (N % 128 == 0, K % 256 == 0); a projection that
         # does not fit (say a fine-tune's 32001-row lm_head) goes to the library GEMM on its own, the others keep the kernel
         streams = lambda t: bool(native_gemm) and t.shape[0] % 128 == 0 and t.shape[1] % 256 == 0
         self.native_gemm_max_rows = int(os.environ.get("SAMD_NATIVE_GEMM_MAX_ROWS", 64))     # tuning knob; see forward_rows
-        if f8:
+        if quant:
             self.native_gemm_max_rows = TILE_ROWS            # (no library GEMM to hand rows to: every bucket up to 64 rows streams)
         # L2 warm-up (csrc/warm_device.h): the glue launch in front of a projection also reads the first KiB of every workgroup's
         # weight stream into the consuming XCD's L2 while HBM idles.  KiB per projection workgroup; 0 = off, the default: measured
@@ -231,9 +245,35 @@ class LlamaRunner:
             out = torch.empty_like(q)
             check(lib().samd_gemm_pack_f8(_ptr(q), _ptr(out), N, K, current_stream()))
             return out, scale
+        def pack_f4(l, k):
+            """projection k in samd_gemm_pack_f4's form (e2m1 elements with their e8m0 block scales inline): quantised on load per block of 32
+            unless the checkpoint brought its own (q, e8), whose exponents must lie in the model dtype's exact range; the model-dtype matrix
+            is dropped as soon as it is packed"""
+            t = l[k]
+            N, K = (t.shape[0], 2 * t.shape[1]) if _is_f4_tensor(t) else t.shape
+            if N % 128 != 0 or K % 256 != 0:
+                raise SamdError(f"MXFP4 projection {k} of shape ({N}, {K}): the MXFP4 kernel needs N % 128 == 0 and K % 256 == 0")
+            if _is_f4_tensor(t):
+                q, e8 = MX.fuse_mxfp4([(t, l.pop(k + "_e8"))], self.device)
+                if tuple(e8.shape) != (N, K // 32):
+                    raise SamdError(f"MXFP4 projection {k}: block scales of shape {tuple(e8.shape)} for a ({N}, {K}) matrix")
+                MX.check_exponents(e8, dtype, f"MXFP4 projection {k}")
+            else:
+                q, e8 = MX.quantize_blocks(t, dtype)
+            l[k] = torch.empty((N, K), dtype=torch.uint8, device="meta")
+            del t
+            out = torch.empty(MX.packed_bytes(N, K), dtype=torch.uint8, device=self.device)
+            check(lib().samd_gemm_pack_f4(_ptr(q), _ptr(e8), _ptr(out), N, K, current_stream()))
+            return out
         # packed_lm_head: a draft head shares the base model's lm_head, packed copy included
         layers = []
         for l in weights["layers"]:
+            if f4:
+                lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
+                for k in MX.PROJECTIONS:
+                    lp[k + "_f4"] = pack_f4(l, k)
+                layers.append(lp)
+                continue
             if f8:
                 lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
                 for k in F8.PROJECTIONS:
@@ -287,7 +327,7 @@ class LlamaRunner:
                         raise SamdError(f"{k} must be a contiguous {dtype} tensor on the GPU")
             self.epi = [epi(l, True) for l in weights["layers"]]
             self.epi_nobias = [epi(l, False) for l in weights["layers"]]
-        self.row_major_released = f8                             # (FP8: there are no row-major projections; prefill runs in 64-row chunks)
+        self.row_major_released = quant                          # (FP8 / MXFP4: there are no row-major projections; prefill runs in 64-row chunks)
         self._length_state(max_cache_len, kv)
         if os.environ.get("SAMD_RELEASE_ROW_MAJOR", "0") == "1":
             self.release_row_major()
@@ -310,9 +350,13 @@ class LlamaRunner:
                 for k in F8.PROJECTIONS:
                     rep["packed_" + k + "_f8"] = sum(nbytes(l[k + "_f8"][0]) for l in self.wp["layers"])
                 rep["fp8_scales"] = sum(nbytes(l[k + "_f8"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
+            if self.weight_format == "mxfp4":                    # one buffer per projection: 16 KiB of elements, then their 1 KiB of scales
+                for k in MX.PROJECTIONS:
+                    rep["packed_" + k + "_f4"] = sum(nbytes(l[k + "_f4"]) * 16 // 17 for l in self.wp["layers"])
+                rep["mxfp4_scales"] = sum(nbytes(l[k + "_f4"]) // 17 for l in self.wp["layers"] for k in MX.PROJECTIONS)
         rep["total"] = sum(rep.values())
-        if self.weight_format == "fp8":
-            rep["weight_format"] = "fp8"
+        if self.weight_format in ("fp8", "mxfp4"):
+            rep["weight_format"] = self.weight_format
         return rep
 
     def release_row_major(self):
@@ -406,15 +450,21 @@ class LlamaRunner:
         matrices -- saves one row-major copy of the model, but the caller's parameters become views of storage the runner owns
         (matters for save_pretrained / in-place edits), so it is opt-in and logged once.
         weight_format (default: env SAMD_WEIGHT_FORMAT, unset = the model dtype): "fp8" quantises the projections on load.  A module whose
-        projections already hold float8_e4m3fn weights with a `weight_scale` (per tensor, [N] or [N, 1]) is imported as it is (samd_hip/fp8.py)."""
+        projections already hold float8_e4m3fn weights with a `weight_scale` (per tensor, [N] or [N, 1]) is imported as it is (samd_hip/fp8.py).
+        "mxfp4" quantises them per block of 32 (no calibration: for benches and tests); a module whose projections hold float4_e2m1fn_x2 or uint8
+        weights [N, K/2] with an e8m0 `weight_scale` [N, K/32] is imported as it is (samd_hip/mxfp4.py)."""
         weight_format = _env_weight_format(weight_format)
         m = lm.model
         parts = (("self_attn", "q_proj"), ("self_attn", "k_proj"), ("self_attn", "v_proj"), ("self_attn", "o_proj"), ("mlp", "gate_proj"),
                  ("mlp", "up_proj"), ("mlp", "down_proj"))
-        ckpt_f8 = F8.checkpoint_is_fp8([(f"layers.{i}.{a}.{b}", getattr(getattr(lyr, a), b)) for i, lyr in enumerate(m.layers) for a, b in parts])
+        linears = [(f"layers.{i}.{a}.{b}", getattr(getattr(lyr, a), b)) for i, lyr in enumerate(m.layers) for a, b in parts]
+        ckpt_f8 = F8.checkpoint_is_fp8(linears)
+        ckpt_f4 = MX.checkpoint_is_mxfp4(linears)
         if F8.is_fp8_dtype(lm.lm_head.weight.dtype) or F8.is_fp8_dtype(m.embed_tokens.weight.dtype):
             raise SamdError("FP8 embedding / lm_head weights are not supported: they stay in the model dtype")
-        dtype = dtype or next(p.dtype for p in lm.parameters() if not F8.is_fp8_dtype(p.dtype))
+        if _is_f4_tensor(lm.lm_head.weight) or _is_f4_tensor(m.embed_tokens.weight):
+            raise SamdError("4-bit embedding / lm_head weights are not supported: they stay in the model dtype")
+        dtype = dtype or next(p.dtype for p in lm.parameters() if p.dtype.is_floating_point and p.dtype.itemsize >= 2)
         qkv_bias, qk_norm = cls._hf_layer_extras(m.layers)
         shape = LlamaShape(lm.config, qkv_bias=qkv_bias, qk_norm=qk_norm)
         dev = torch.device(device)
@@ -448,6 +498,12 @@ class LlamaRunner:
                 extra["bqkv"] = get(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias]))
             if qk_norm:
                 extra["q_norm"], extra["k_norm"] = get(a.q_norm.weight), get(a.k_norm.weight)
+            if ckpt_f4:                                          # (q, e8) as the checkpoint has them; the runner checks and packs them
+                lw = {}
+                for k, lins in (("wqkv", (a.q_proj, a.k_proj, a.v_proj)), ("wo", (a.o_proj,)), ("wgu", (f.gate_proj, f.up_proj)), ("wdown", (f.down_proj,))):
+                    lw[k], lw[k + "_e8"] = MX.fuse_mxfp4([MX.linear_mxfp4(x) for x in lins], dev)
+                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
+                continue
             if ckpt_f8:                                          # (q, scale) as the checkpoint has them; the runner packs them
                 lw = {}
                 for k, lins in (("wqkv", (a.q_proj, a.k_proj, a.v_proj)), ("wo", (a.o_proj,)), ("wgu", (f.gate_proj, f.up_proj)), ("wdown", (f.down_proj,))):
@@ -484,7 +540,9 @@ class LlamaRunner:
         def names_of(lyr):
             # an FP8 projection's scales may be parameters as well as buffers (fbgemm / compressed-tensors layers): the runner reads
             # weight_scale through samd_hip/fp8.py (input scales are not used: weight-only FP8), so they are not extra parameters
-            skip = {f"{n[:-len('.weight')]}.{sc}" for n, p in lyr.named_parameters() if n.endswith(".weight") and F8.is_fp8_dtype(p.dtype)
+            # (the same holds for an MXFP4 projection -- a float4_e2m1fn_x2 or uint8 weight -- and its e8m0 weight_scale)
+            skip = {f"{n[:-len('.weight')]}.{sc}" for n, p in lyr.named_parameters()
+                    if n.endswith(".weight") and (F8.is_fp8_dtype(p.dtype) or _is_f4_tensor(p))
                     for sc in ("weight_scale", "input_scale")}
             return {n for n, _ in lyr.named_parameters()} - skip
         names0 = names_of(layers[0])
@@ -534,9 +592,13 @@ class LlamaRunner:
 
     def weight_bytes(self):
         """bytes of weights one decode step streams from HBM (the embedding table is only gathered), tensor by tensor in its own format
-        (an FP8 projection: one byte per weight + its fp32 column scales)."""
+        (an FP8 projection: one byte per weight + its fp32 column scales; an MXFP4 projection: half a byte per weight + one scale byte per 32)."""
         nb = lambda t: t.numel() * t.element_size()
         n = nb(self.w["lm_head"]) + nb(self.w["norm"])
+        if self.weight_format == "mxfp4":
+            for l, lp in zip(self.w["layers"], self.wp["layers"]):
+                n += sum(nb(t) for k, t in l.items() if k not in MX.PROJECTIONS) + sum(nb(lp[k + "_f4"]) for k in MX.PROJECTIONS)
+            return n
         for l in self.w["layers"]:
             n += sum(nb(t) for t in l.values())
         if self.weight_format == "fp8":
@@ -601,10 +663,15 @@ class LlamaRunner:
             sp = 1 if (fused or is_head) else L.samd_gemm_splits(n, k, RP)
             return C.byref(Warm(wp.data_ptr(), n, k, sp, self.warm_kb, self.warm_delay, self.warm_where))
 
-        def gemm(a, w, wp, out, wg=None, f8=None):
+        def gemm(a, w, wp, out, wg=None, f8=None, f4=None):
             """out = a @ w.T (wp = w in the packed 128-column-tile layout, wg = w group-major: whichever exists; f8 = (packed e4m3fn, column
-            scales) of an FP8 runner); returns (operand for the consumer, n_partials, partial_stride)."""
+            scales) of an FP8 runner; f4 = the packed elements + block scales of an MXFP4 runner); returns (operand for the consumer,
+            n_partials, partial_stride)."""
             n, k = w.shape
+            if f4 is not None:                                    # (RP <= 64 here, as for FP8)
+                sp = L.samd_gemm_splits(n, k, RP)
+                check(L.samd_gemm_skinny_f4(_ptr(a), _ptr(f4), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
+                return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
             if f8 is not None:                                    # (RP <= 64 here: an FP8 runner has no library-GEMM path, see the check above)
                 sp = L.samd_gemm_splits(n, k, RP)
                 check(L.samd_gemm_skinny_f8(_ptr(a), _ptr(f8[0]), _ptr(f8[1]), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
@@ -654,7 +721,7 @@ class LlamaRunner:
                     _ptr(b["x"] if raw_in else b["h"]), _ptr(wp["wqkv64"]), RP, s.hidden, _ptr(b["cs"]), _ptr(d_L), _ptr(d_n),
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), s.heads, s.kv_heads, s.head_dim, self.max_len, dt, st))
             else:
-                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], f8=wp.get("wqkv_f8"))
+                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], f8=wp.get("wqkv_f8"), f4=wp.get("wqkv_f4"))
             if block:
                 # RoPE + K row / V^T column write + tree attention + merge of the tile partials: one launch (csrc/attn_kernels.hip)
                 check(L.samd_attention_block(_ptr(src), n_p, stride, _ptr(b["cs"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R,
@@ -686,15 +753,15 @@ class LlamaRunner:
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R, s.heads,
                     s.kv_heads, s.head_dim, self.max_len, _ptr(d_mask), _ptr(d_L), _ptr(d_n), self.scale,
                     _ptr(b["ws"]), b["ws_bytes"], hint(w["wo"], wp.get("wo")), st))
-            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"))
+            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"), f4=wp.get("wo_f4"))
             check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(src), _ptr(w["ln2"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, n_p, stride,
                                       None, st))           # (no warm-up hint: gate|up is packed group-major, the hint describes 128-column tiles)
             if self.fused_mlp and RP <= self.native_gemm_max_rows:
                 check(L.samd_gemm_pairs_silu(_ptr(b["h"]), _ptr(wp["wgu"]), RP, s.inter, s.hidden, _ptr(b["act"]), dt, st))
             else:
-                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"))     # wgu is only ever packed for the fused form (or FP8)
+                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"), f4=wp.get("wgu_f4"))     # wgu is only ever packed for the fused form (or FP8)
                 check(L.samd_silu_mul(_ptr(src), _ptr(b["act"]), R, s.inter, dt, n_p, stride, st))
-            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"))
+            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"), f4=wp.get("wdown_f4"))
         check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(delta), _ptr(self.w["norm"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, dn, dstride,
                                   hint(self.w["lm_head"], self.wp["lm_head"] if self.wp else None, is_head=True), st))
         # (for a draft head the call above only folds the last projection into the residual stream; its norm output is unused)

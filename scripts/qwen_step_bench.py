@@ -1,5 +1,5 @@
 """qwen_step_bench.py -- graph-replay time of one verify forward per row bucket (L = 800 cached keys) for random-init Llama-3-8B, Qwen2.5-7B and
-Qwen3-8B at full depth, in fp16 and with FP8 projections.  Qwen runs the eight-launch layer with samd_rope_kv_write_epi (q|k|v bias / q-k
+Qwen3-8B at full depth, in fp16 and with FP8 or MXFP4 projections (--formats fp16,fp8,mxfp4).  Qwen runs the eight-launch layer with samd_rope_kv_write_epi (q|k|v bias / q-k
 norm); Llama-3-8B is the yardstick.   usage: python scripts/qwen_step_bench.py [--reps 30] [--models llama3-8b,qwen2.5-7b,qwen3-8b]"""
 import argparse, gc, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,7 +32,13 @@ def step_ms(runner, sess, n, reps):
     for _ in range(reps):
         g.replay()
     torch.cuda.synchronize()
-    return R, (time.perf_counter() - t0) / reps * 1e3
+    mean = (time.perf_counter() - t0) / reps * 1e3
+    each = []                                                 # the same replays one by one: their spread is the margin between two formats
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); g.replay(); e1.record(); e1.synchronize()
+        each.append(e0.elapsed_time(e1))
+    return R, mean, max(each) - min(each)
 
 
 def main():
@@ -43,12 +49,16 @@ def main():
     a = ap.parse_args()
     for name in a.models.split(","):
         for fmt in a.formats.split(","):
-            runner = LlamaRunner.random_init(MODELS[name], 2048, torch.float16, seed=0, weight_format="fp8" if fmt == "fp8" else None)
+            if fmt not in ("fp16", "fp8", "mxfp4"):
+                raise SystemExit(f"--formats: unknown format {fmt!r} (fp16, fp8, mxfp4)")
+            runner = LlamaRunner.random_init(MODELS[name], 2048, torch.float16, seed=0, weight_format=fmt if fmt != "fp16" else None)
             sess = samd_hip.Session(4096)
             sess.reset()
             sizes = (1, 8, 16, 32, 48, 64) + ((128,) if runner.max_draft_rows() >= 128 else ())
-            res = {R: round(ms, 4) for R, ms in (step_ms(runner, sess, n, a.reps) for n in sizes)}
-            print(json.dumps(dict(model=name, format=fmt, epilogue=runner.qkv_epilogue, step_ms=res)), flush=True)
+            runs = [step_ms(runner, sess, n, a.reps) for n in sizes]
+            res = {R: round(ms, 4) for R, ms, _ in runs}
+            spread = {R: round(sp, 4) for R, _, sp in runs}
+            print(json.dumps(dict(model=name, format=fmt, epilogue=runner.qkv_epilogue, step_ms=res, spread_ms=spread)), flush=True)
             del runner, sess
             gc.collect(); torch.cuda.empty_cache()
 
