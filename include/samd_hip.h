@@ -661,6 +661,40 @@ int samd_gemm_skinny_f8(const void *d_A, const void *d_W8p, const float *d_scale
 int samd_gemm_pack_f4(const void *d_q, const void *d_e8, void *d_out, int32_t N, int32_t K, void *stream);
 int samd_gemm_skinny_f4(const void *d_A, const void *d_W4p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
                         int32_t dtype, void *stream);
+/* Mixture-of-experts MLP (Qwen3-MoE; HF Qwen3MoeSparseMoeBlock) at rows_pad in {16, 32, 48, 64}, hidden % 256 == 0, moe_inter % 256 == 0,
+ * n_experts <= 256, top_k <= min(8, n_experts), f16 / bf16.  Every launch has a fixed grid and reads its counts from device memory, so the
+ * three calls of a sparse layer can be captured.  norm_topk is a flag (Qwen3-MoE's norm_topk_prob), not a model name.
+ *   samd_moe_workspace     bytes of d_ws: the routing lists (n_active, the active experts in ascending order, per active expert its
+ *                          count and its entries p = row * top_k + slot in ascending order) followed by the down products
+ *                          y [rows_pad * top_k][hidden] in the model dtype.
+ *   samd_moe_workspace_layout  where the routing lists lie, in int32 words from the head of d_ws (for tests and profiling; the kernels'
+ *                          own constants): field 0 = first word of the active experts, 1 = of their counts, 2 = of the entry lists,
+ *                          3 = words per entry list, 4 = words of the whole routing part; word 0 is n_active.  Another field: -1.
+ *   samd_moe_pack_experts  n_experts row-major [N][K] matrices laid end to end -> the 128-column tile layout of samd_gemm_pack_weights per
+ *                          expert, end to end.  gate_up != 0: N = 2 * moe_inter and each tile holds 64 gate rows and the 64 up rows they
+ *                          multiply (HF's fused gate_up_proj [E][2 I][H]); gate_up == 0: HF's down_proj [E][H][I] as it is.
+ *   samd_moe_route         router of d_h [rows_pad][hidden] against d_router [n_experts][hidden] (model dtype): logits accumulated and KEPT
+ *                          in fp32 (HF's low-precision F.linear rounds them, which manufactures exact ties), fp32 softmax, top-k by value
+ *                          with ties to the lower expert, renormalised over the selection when norm_topk, weights rounded once to the model
+ *                          dtype.  Writes d_topk_idx int32 [rows_pad][top_k], d_topk_w [rows_pad][top_k] and the lists in d_ws.  Rows
+ *                          >= *d_n get index -1, weight 0 and appear in no list.
+ *   samd_moe_lists         the lists alone, from a given d_topk_idx (entries of rows >= *d_n or outside [0, n_experts), and a
+ *                          repetition of an expert within a row, are ignored by the lists AND by the combine: they add nothing).
+ *   samd_moe_gate_up_silu  d_act [rows_pad * top_k][moe_inter]: row p = silu(gate_e(h_row)) * up_e(h_row) for every list entry, with HF's
+ *                          roundings; the A rows are gathered through the lists.  Grid (moe_inter / 64, min(n_experts, rows_pad * top_k)).
+ *   samd_moe_down_combine  y[p] = down_e(act[p]) rounded to the model dtype, each entry in its own row (no atomics), then in a second
+ *                          kernel of the same call d_out [rows_pad][hidden] = sum_j w[row][j] * y[row * top_k + j], j ascending, fp32, one
+ *                          rounding; rows >= *d_n are zero.  A row's output has the same bits whatever other rows share the launch. */
+int32_t samd_moe_workspace_layout(int32_t field);
+int64_t samd_moe_workspace(int32_t rows_pad, int32_t hidden, int32_t n_experts, int32_t top_k, int32_t dtype);
+int samd_moe_pack_experts(const void *d_W, void *d_packed, int32_t n_experts, int32_t N, int32_t K, int32_t gate_up, void *stream);
+int samd_moe_route(const void *d_h, const void *d_router, const int32_t *d_n, int32_t rows_pad, int32_t hidden, int32_t n_experts, int32_t top_k,
+                   int32_t norm_topk, int32_t *d_topk_idx, void *d_topk_w, void *d_ws, int32_t dtype, void *stream);
+int samd_moe_lists(const int32_t *d_topk_idx, const int32_t *d_n, int32_t rows_pad, int32_t n_experts, int32_t top_k, void *d_ws, void *stream);
+int samd_moe_gate_up_silu(const void *d_h, const void *d_Wgu, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
+                          int32_t top_k, void *d_act, int32_t dtype, void *stream);
+int samd_moe_down_combine(const void *d_act, const void *d_Wdown, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                          int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream);
 
 /* ---- scripted verifier (tests, smoke and bench only): replaces the LM arg-max of every draft node by
  * the next token of a target stream while the node's context (committed history + root->node path) is a

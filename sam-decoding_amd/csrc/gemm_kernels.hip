@@ -1632,3 +1632,485 @@ int samd_gemm_skinny_f4(const void *d_A, const void *d_W4p, int32_t rows_pad, in
 }
 
 }  // extern "C"
+
+// ================================================================================================
+// Mixture-of-experts MLP (Qwen3-MoE: HF Qwen3MoeSparseMoeBlock): router, gathered expert gate|up + SiLU, gathered expert down + combine.
+// A sparse layer streams a data-dependent subset of E small matrices, each for its own subset of rows; the choice is made on the device
+// and every launch has a fixed grid, so a decode step stays one hipGraph replay.
+//   samd_moe_route         k_moe_route (one 16-wave workgroup per row, four experts in flight per wave: fp32 router logits, fp32 softmax, top-k by value with ties to the lower
+//                          expert, renormalisation, ONE rounding of the weights), then k_moe_lists (one workgroup): the compacted list of
+//                          active experts in ascending order and, per active expert, its (row, slot) entries in ascending order -- fixed
+//                          orders, no atomics, so the lists do not depend on which workgroup ran first.
+//   samd_moe_gate_up_silu  grid (I / 64 column tiles, min(E, rows * k) active slots); workgroups past the active count exit at once.  The
+//                          stream is k_gemm_skinny's with EPI 1 (tile = 64 gate | 64 up columns of ONE expert; expert e's packed matrix at
+//                          e * 2 I * H elements); the A tile is GATHERED: tile row r is row lists[a][r] / k of h (an indirection on the
+//                          LDS-DMA's per-lane source address, no copy); act row lists[a][r] = row * k + slot receives silu(gate) * up.
+//   samd_moe_down_combine  the same stream with EPI 0 over the expert's act rows; y[row * k + slot] gets its own row (no atomics), then
+//                          k_moe_combine adds a row's k products in slot order in fp32, weighted, and rounds once.
+// Row independence: tile row r of a workgroup depends on A row r and the expert's weights only, the k order is the chunk order (no
+// split-K), and the combine's order is the slot order -- a row's output has the same bits whatever else shares the launch, whichever
+// tile row or row bucket it lands in.
+//   ROUTING WORKSPACE (int32 words at the head of d_ws): [0] n_active; [16 + a] expert of active slot a; [272 + a] its entry count;
+//   [528 + 64 a + q] its q-th entry p = row * k + slot.  The down products y [rows * k][hidden] (model dtype) follow at MOE_WS_Y_OFF bytes.
+// Tile rows past an expert's count read its first entry's row again (their sums are not written); entries are < rows * k by construction.
+// ================================================================================================
+#define MOE_MAX_E 256
+#define MOE_MAX_K 8
+#define MOE_MAX_ROWS 64
+#define MOE_WS_ACTIVE 16
+#define MOE_WS_COUNT (MOE_WS_ACTIVE + MOE_MAX_E)
+#define MOE_WS_LIST (MOE_WS_COUNT + MOE_MAX_E)
+#define MOE_WS_INTS (MOE_WS_LIST + MOE_MAX_E * MOE_MAX_ROWS)
+#define MOE_WS_Y_OFF (((MOE_WS_INTS * 4 + 255) / 256) * 256)
+
+// Router logits stay in fp32 (HF's low-precision F.linear rounds them to the model dtype, which manufactures exact ties: a documented
+// difference).  Rows >= *d_n get index -1 and weight 0: they route nowhere.
+// 16 waves per row; a wave takes FOUR experts at a time (e0 = 4 w, 4 w + 64, ...), so the h unit and four independent weight units of every
+// step are in flight together: Qwen3-30B-A3B (E = 128, H = 2048) is two rounds of four steps per wave instead of 32 experts one after another.
+// Every expert's sum keeps one order (k ascending per lane, then a fixed shuffle tree), whatever group it falls in.
+#define MOE_ROUTE_WAVES 16
+template <typename E>
+__global__ __launch_bounds__(64 * MOE_ROUTE_WAVES) void k_moe_route(const E *__restrict__ h, const E *__restrict__ Wr, const int *__restrict__ d_n, int hidden, int n_exp, int top_k,
+                                                   int norm_topk, int *__restrict__ topk_idx, E *__restrict__ topk_w) {
+    __shared__ float logit[MOE_MAX_E];
+    const int row = blockIdx.x, tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+    if (row >= d_n[0]) {
+        if (tid < top_k) { topk_idx[row * top_k + tid] = -1; topk_w[row * top_k + tid] = (E)0.f; }
+        return;
+    }
+    const uint4 *hx = reinterpret_cast<const uint4 *>(h + (size_t)row * hidden);
+    for (int e0 = 4 * w; e0 < n_exp; e0 += 4 * MOE_ROUTE_WAVES) {    // 16-byte loads, fp32 sums, a fixed reduction tree
+        const uint4 *wx[4];
+        float s[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { const int e = e0 + i < n_exp ? e0 + i : n_exp - 1; wx[i] = reinterpret_cast<const uint4 *>(Wr + (size_t)e * hidden); s[i] = 0.f; }
+#pragma unroll 4
+        for (int u = l; u < hidden / 8; u += 64) {               // (unrolled: the loads of four steps x four experts are requested together)
+            const uint4 a = hx[u];
+            uint4 b[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) b[i] = wx[i][u];
+            const E *ae = reinterpret_cast<const E *>(&a);
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const E *be = reinterpret_cast<const E *>(&b[i]);
+#pragma unroll
+                for (int j = 0; j < 8; j++) s[i] = fmaf((float)ae[j], (float)be[j], s[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
+            if (l == 0 && e0 + i < n_exp) logit[e0 + i] = s[i];
+        }
+    }
+    __syncthreads();
+    if (w != 0) return;
+    constexpr float NINF = -__builtin_huge_valf();
+    float v[MOE_MAX_E / 64];
+    float mx = NINF;
+#pragma unroll
+    for (int i = 0; i < MOE_MAX_E / 64; i++) { const int e = l + 64 * i; v[i] = e < n_exp ? logit[e] : NINF; mx = fmaxf(mx, v[i]); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    float se = 0.f;
+#pragma unroll
+    for (int i = 0; i < MOE_MAX_E / 64; i++) se += (l + 64 * i < n_exp) ? expf(v[i] - mx) : 0.f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+    float sel_p[MOE_MAX_K];
+    int sel_i[MOE_MAX_K];
+    float sum_sel = 0.f;
+#pragma unroll
+    for (int j = 0; j < MOE_MAX_K; j++) {
+        sel_p[j] = 0.f; sel_i[j] = -1;
+        if (j >= top_k) continue;
+        float bv = NINF; int bi = 0x7fffffff;                    // the largest remaining logit; ties go to the lower expert
+#pragma unroll
+        for (int i = 0; i < MOE_MAX_E / 64; i++) { const int e = l + 64 * i; if (e < n_exp && (v[i] > bv || (v[i] == bv && e < bi && v[i] > NINF))) { bv = v[i]; bi = e; } }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+#pragma unroll
+        for (int i = 0; i < MOE_MAX_E / 64; i++) if (bi == l + 64 * i) v[i] = NINF;
+        if (bi < n_exp) { sel_i[j] = bi; sel_p[j] = expf(bv - mx) / se; sum_sel += sel_p[j]; }
+    }
+    if (l == 0) {
+#pragma unroll
+        for (int j = 0; j < MOE_MAX_K; j++) {
+            if (j >= top_k) continue;
+            topk_idx[row * top_k + j] = sel_i[j];
+            topk_w[row * top_k + j] = (E)(norm_topk ? sel_p[j] / sum_sel : sel_p[j]);
+        }
+    }
+}
+
+// the lists of samd_moe_route from topk_idx [rows][k] (also on its own: samd_moe_lists, for routing that was decided elsewhere).  Entries of
+// rows >= *d_n, indices outside [0, n_exp) and anything past 64 entries of one expert are left out.
+__global__ __launch_bounds__(MOE_MAX_E) void k_moe_lists(const int *__restrict__ topk_idx, const int *__restrict__ d_n, int rows, int n_exp, int top_k, int *__restrict__ ws) {
+    // one bitmap of entries per expert (bit p of expert e: entry p = row * k + slot routes to e), set with LDS bit-or -- whatever order the
+    // threads arrive in, the bitmap is the same -- then every expert's thread walks ITS bits in ascending order: work goes by an expert's own
+    // count, not by the rows * k entries
+    constexpr int WORDS = MOE_MAX_ROWS * MOE_MAX_K / 32;
+    __shared__ unsigned bits[MOE_MAX_E][WORDS + 1];              // (+1: the experts' rows fall on different banks)
+    __shared__ int wave_active[MOE_MAX_E / 64];
+    const int tid = threadIdx.x, total = rows * top_k;
+    int n = d_n[0];
+    n = n < 0 ? 0 : (n > rows ? rows : n);
+#pragma unroll
+    for (int i = 0; i < WORDS; i++) bits[tid][i] = 0u;
+    __syncthreads();
+    for (int p = tid; p < total; p += MOE_MAX_E) {
+        const int r = p / top_k;
+        int e = r < n ? topk_idx[p] : -1;
+        if (e >= n_exp) e = -1;
+        for (int q = r * top_k; q < p; q++) if (topk_idx[q] == e) e = -1;        // an expert counts once per row: its first slot
+        if (e >= 0) atomicOr(&bits[e][p >> 5], 1u << (p & 31));
+    }
+    __syncthreads();
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < WORDS; i++) c += __popc(bits[tid][i]);
+    if (c > MOE_MAX_ROWS) c = MOE_MAX_ROWS;                      // (cannot happen with one slot per row and <= 64 rows: a guard for the list's size)
+    // this expert's place among the active ones (ascending expert order): the wave's ballot below this lane + the waves before it
+    const unsigned long long act = __ballot(c > 0);
+    if ((tid & 63) == 0) wave_active[tid >> 6] = __popcll(act);
+    __syncthreads();
+    int a = __popcll(act & ((1ull << (tid & 63)) - 1ull));
+    for (int w = 0; w < (tid >> 6); w++) a += wave_active[w];
+    if (c > 0) {
+        ws[MOE_WS_ACTIVE + a] = tid;
+        ws[MOE_WS_COUNT + a] = c;
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < WORDS; i++) {
+            unsigned m = bits[tid][i];
+            while (m && q < MOE_MAX_ROWS) { ws[MOE_WS_LIST + MOE_MAX_ROWS * a + q++] = 32 * i + (__ffs(m) - 1); m &= m - 1u; }
+        }
+    }
+    if (tid == MOE_MAX_E - 1) ws[0] = a + (c > 0);
+}
+
+// One expert's share of a projection: k_gemm_skinny's stream (GEMM_KC chunks, 8 waves x 16 columns, hand-issued nt weight loads with counted
+// vmcnt, LDS-DMA'd A tiles with the XOR swizzle on the source address, two chunks in flight) with a gathered A tile.  The load destinations
+// are single values defined once and every load is an in-out operand of that value, as in k_gemm_skinny_f4.
+// GU: W = gate|up tiles (64 gate | 64 up columns), A = h, epilogue silu(gate) * up -> out[p][N / 2]; otherwise W = down tiles, A = act,
+// out[p][N] = the product rounded to the model dtype.
+template <typename TT, int RT, bool GU>
+__device__ __forceinline__ void moe_expert_gemm(const typename TT::elem *__restrict__ A, const typename TT::elem *__restrict__ W, const int *__restrict__ ws,
+                                                typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
+    typedef typename TT::elem E;
+    typedef typename TT::vec8 V8;
+    constexpr int DEPTH = 2;
+    constexpr int R = 16 * RT;
+    constexpr int NT = 64 * GEMM_WAVES;
+    constexpr int XV = (R * 32) / NT;
+    constexpr int NB = DEPTH + 1;
+    constexpr int PC = 8 + XV;                     // memory operations per thread and chunk
+    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
+    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
+    __shared__ int lst[MOE_MAX_ROWS];
+
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
+    const int slot_a = blockIdx.y;
+    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts
+    const int expert = ws[MOE_WS_ACTIVE + slot_a];
+    int cnt = ws[MOE_WS_COUNT + slot_a];
+    cnt = cnt > R ? R : cnt;
+    if (tid < MOE_MAX_ROWS) lst[tid] = ws[MOE_WS_LIST + MOE_MAX_ROWS * slot_a + (tid < cnt ? tid : 0)];
+    __syncthreads();
+    // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
+    int srow[XV];
+#pragma unroll
+    for (int i = 0; i < XV; i++) { const int p = lst[(tid >> 5) + 16 * i]; srow[i] = GU ? p / top_k : p; }
+
+    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    const char *wtile = reinterpret_cast<const char *>(W) + ((size_t)expert * (N / GEMM_COLS) + blockIdx.x) * n_chunks * 65536;
+    const uint32_t wlane = (uint32_t)tid * 16;
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
+
+    floatx4 acc[RT];
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    u32x4 wr[DEPTH][4][2];
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) asm volatile("" : "=v"(wr[d][b][0]), "=v"(wr[d][b][1]));
+    auto load_wb = [&](u32x4 (&dst)[4][2], int c, int b) {
+        const char *p = wtile + (size_t)c * 65536;
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+            asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[b][j]) : "v"(wlane), "s"(p + 8192 * (2 * b + j)) : "memory");
+    };
+    auto stage_xi = [&](int c, int buf, int i) {
+        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
+        const E *src = A + (size_t)srow[i] * K + (size_t)c * GEMM_KC + 8 * unit;
+        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        asm volatile("" ::: "memory");
+    };
+    auto load_w = [&](u32x4 (&dst)[4][2], int c) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) load_wb(dst, c, b);
+    };
+    auto stage_x = [&](int c, int buf) {
+#pragma unroll
+        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
+    };
+    auto phase = [&](u32x4 (&cur)[4][2], int c, int buf) {
+        gemm_wait_younger<DEPTH, PC>(n_chunks - 1 - c);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
+            u32x4 r[RT][2];
+            gemm_f4_read_a<RT>(r, a0, a1);
+            // re-defined behind the counted wait (volatile asm keeps its order): no use can be scheduled above it
+            asm volatile("" : "+v"(cur[b][0]), "+v"(cur[b][1]) : : "memory");
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++) {
+                acc[mt] = TT::mfma(__builtin_bit_cast(V8, r[mt][0]), __builtin_bit_cast(V8, cur[b][0]), acc[mt]);
+                acc[mt] = TT::mfma(__builtin_bit_cast(V8, r[mt][1]), __builtin_bit_cast(V8, cur[b][1]), acc[mt]);
+            }
+            if (RT >= 3 && c + DEPTH < n_chunks) {             // 48 / 64 rows: refill per k block (see k_gemm_skinny)
+                load_wb(cur, c + DEPTH, b);
+                if (b < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, b);
+            }
+        }
+        if (RT < 3 && c + DEPTH < n_chunks) { load_w(cur, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
+    };
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++)
+        if (d < n_chunks) { load_w(wr[d], d); stage_x(d, d); }
+    int buf = 0;
+    for (int c = 0; c < n_chunks; c += DEPTH) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++)
+            if (c + d < n_chunks) { phase(wr[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+    }
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n
+    if constexpr (GU) {
+        float *ex = reinterpret_cast<float *>(gemm_lds);            // [R][64] up values; the A tiles are dead by now
+        __syncthreads();
+        if (w >= 4) {
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) ex[(16 * mt + 4 * g + r) * 64 + 16 * (w - 4) + n] = acc[mt][r];
+        }
+        __syncthreads();
+        if (w < 4) {
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int m = 16 * mt + 4 * g + r;
+                    if (m >= cnt) continue;
+                    // the roundings of HF's act_fn(gate) * up in the model dtype (same as k_gemm_skinny EPI 1 / k_silu_mul)
+                    const float gf = (float)(E)acc[mt][r], uf = (float)(E)ex[m * 64 + 16 * w + n];
+                    const E sv = (E)(gf / (1.f + __expf(-gf)));
+                    out[(size_t)lst[m] * (N / 2) + blockIdx.x * 64 + 16 * w + n] = (E)((float)sv * uf);
+                }
+        }
+    } else {
+#pragma unroll
+        for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int m = 16 * mt + 4 * g + r;
+                if (m < cnt) out[(size_t)lst[m] * N + n0 + n] = (E)acc[mt][r];
+            }
+    }
+}
+
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 ? 2 : GEMM_WAVES / 2) void k_moe_gate_up_silu(const typename TT::elem *__restrict__ h, const typename TT::elem *__restrict__ W,
+                                                                                                    const int *__restrict__ ws, typename TT::elem *__restrict__ act,
+                                                                                                    int K, int N, int n_chunks, int top_k) {
+    moe_expert_gemm<TT, RT, true>(h, W, ws, act, K, N, n_chunks, top_k);
+}
+
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 ? 2 : GEMM_WAVES / 2) void k_moe_down(const typename TT::elem *__restrict__ act, const typename TT::elem *__restrict__ W,
+                                                                                            const int *__restrict__ ws, typename TT::elem *__restrict__ y,
+                                                                                            int K, int N, int n_chunks, int top_k) {
+    moe_expert_gemm<TT, RT, false>(act, W, ws, y, K, N, n_chunks, top_k);
+}
+
+// out[row] = sum_j w[row][j] * y[row * k + j], j = 0 .. k - 1 in order, fp32, one rounding; rows >= *d_n and slots without a valid expert (or repeating an earlier slot's) add nothing
+template <typename E>
+__global__ __launch_bounds__(256) void k_moe_combine(const E *__restrict__ y, const int *__restrict__ topk_idx, const E *__restrict__ topk_w, const int *__restrict__ d_n,
+                                                     E *__restrict__ out, int hidden, int top_k, int n_exp) {
+    const int row = blockIdx.y, u = blockIdx.x * 256 + threadIdx.x;
+    if (u >= hidden / 8) return;
+    float acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) acc[i] = 0.f;
+    if (row < d_n[0]) {
+        for (int j = 0; j < top_k; j++) {
+            const int e = topk_idx[row * top_k + j];
+            bool skip = e < 0 || e >= n_exp;                     // what k_moe_lists left out has no product: it adds nothing
+            for (int q = 0; q < j; q++) skip = skip || topk_idx[row * top_k + q] == e;
+            if (skip) continue;
+            const float wj = (float)topk_w[row * top_k + j];
+            const uint4 v = reinterpret_cast<const uint4 *>(y + (size_t)(row * top_k + j) * hidden)[u];
+            const E *ve = reinterpret_cast<const E *>(&v);
+#pragma unroll
+            for (int i = 0; i < 8; i++) acc[i] += wj * (float)ve[i];
+        }
+    }
+    uint4 o;
+    E *oe = reinterpret_cast<E *>(&o);
+#pragma unroll
+    for (int i = 0; i < 8; i++) oe[i] = (E)acc[i];
+    reinterpret_cast<uint4 *>(out + (size_t)row * hidden)[u] = o;
+}
+
+// E experts of row-major [N][K] each, end to end -> each in k_gemm_pack's 128-column tile layout, end to end.  half > 0 (gate|up, half = I):
+// packed row 128 t + q is gate row 64 t + q for q < 64 and up row 64 t + q - 64 otherwise, so that a tile holds matching columns.
+__global__ __launch_bounds__(256) void k_moe_pack(const uint4 *__restrict__ W, uint4 *__restrict__ out, int N, int K, int half, long long total) {
+    const long long ug = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (ug >= total) return;
+    const long long per = (long long)N * K / 8, e = ug / per, u = ug % per;
+    const int n_chunks = K / GEMM_KC;
+    const long long blk = u >> 12;
+    const int in = (int)(u & 4095), jj = in >> 9, tid = in & 511, w = tid >> 6, g = (tid >> 4) & 3, n = tid & 15;
+    const int t = (int)(blk / n_chunks), c = (int)(blk % n_chunks), b = jj >> 1, j = jj & 1;
+    const int q = 16 * w + n;
+    const long long row = half ? (q < 64 ? 64LL * t + q : (long long)half + 64LL * t + q - 64) : 128LL * t + q;
+    const long long col = 256LL * c + 64 * b + 16 * g + 8 * j;
+    out[ug] = W[e * per + (row * K + col) / 8];
+}
+
+template <typename TT, int RT, bool GU>
+static hipError_t moe_gemm_launch(dim3 grid, hipStream_t st, const void *A, const void *W, const int *ws, void *out, int K, int N, int top_k) {
+    typedef typename TT::elem E;
+    constexpr int lds = 3 * 16 * RT * GEMM_KC * 2;
+    if constexpr (GU) {
+        if constexpr (lds > 65536) {
+            static unsigned long long done = 0ull;
+            const hipError_t attr = samd_reserve_lds((const void *)k_moe_gate_up_silu<TT, RT>, lds, &done);
+            if (attr != hipSuccess) return attr;
+        }
+        hipLaunchKernelGGL((k_moe_gate_up_silu<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, K / GEMM_KC, top_k);
+    } else {
+        if constexpr (lds > 65536) {
+            static unsigned long long done = 0ull;
+            const hipError_t attr = samd_reserve_lds((const void *)k_moe_down<TT, RT>, lds, &done);
+            if (attr != hipSuccess) return attr;
+        }
+        hipLaunchKernelGGL((k_moe_down<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, K / GEMM_KC, top_k);
+    }
+    return hipSuccess;
+}
+
+template <bool GU>
+static hipError_t moe_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W, const int *ws, void *out, int K, int N, int top_k) {
+#define GO(TT, RT) return moe_gemm_launch<TT, RT, GU>(grid, st, A, W, ws, out, K, N, top_k)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
+}
+
+static bool moe_shape_ok(int rows_pad, int hidden, int moe_inter, int n_experts, int top_k, int dtype) {
+    return (rows_pad == 16 || rows_pad == 32 || rows_pad == 48 || rows_pad == 64) && hidden >= GEMM_KC && hidden % GEMM_KC == 0 &&
+           moe_inter >= GEMM_KC && moe_inter % GEMM_KC == 0 && n_experts >= 1 && n_experts <= MOE_MAX_E && top_k >= 1 && top_k <= MOE_MAX_K &&
+           top_k <= n_experts && (dtype == SAMD_F16 || dtype == SAMD_BF16);
+}
+#define MOE_SHAPE_MSG "unsupported shape (rows 16/32/48/64, hidden %% 256 == 0, moe_intermediate %% 256 == 0, experts <= 256, top-k <= 8, f16/bf16) or null pointer"
+
+extern "C" {
+
+int32_t samd_moe_workspace_layout(int32_t field) {
+    switch (field) {
+    case 0: return MOE_WS_ACTIVE;
+    case 1: return MOE_WS_COUNT;
+    case 2: return MOE_WS_LIST;
+    case 3: return MOE_MAX_ROWS;
+    case 4: return MOE_WS_INTS;
+    default: return -1;
+    }
+}
+
+int64_t samd_moe_workspace(int32_t rows_pad, int32_t hidden, int32_t n_experts, int32_t top_k, int32_t dtype) {
+    (void)n_experts; (void)dtype;
+    return (int64_t)MOE_WS_Y_OFF + (int64_t)rows_pad * top_k * hidden * 2;
+}
+
+int samd_moe_pack_experts(const void *d_W, void *d_packed, int32_t n_experts, int32_t N, int32_t K, int32_t gate_up, void *stream) {
+    if (!d_W || !d_packed || d_W == d_packed || n_experts < 1 || N < GEMM_COLS || N % GEMM_COLS != 0 || K < GEMM_KC || K % GEMM_KC != 0) {
+        samd_set_error("samd_moe_pack_experts: needs N %% 128 == 0, K %% 256 == 0 and distinct buffers"); return SAMD_E_INVALID;
+    }
+    const long long total = (long long)n_experts * N * K / 8;
+    hipLaunchKernelGGL(k_moe_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)d_W, (uint4 *)d_packed, N, K,
+                       gate_up ? N / 2 : 0, total);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_moe_lists(const int32_t *d_topk_idx, const int32_t *d_n, int32_t rows_pad, int32_t n_experts, int32_t top_k, void *d_ws, void *stream) {
+    if (!d_topk_idx || !d_n || !d_ws || !moe_shape_ok(rows_pad, GEMM_KC, GEMM_KC, n_experts, top_k, SAMD_F16)) {
+        samd_set_error("samd_moe_lists: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
+    }
+    hipLaunchKernelGGL(k_moe_lists, dim3(1), dim3(MOE_MAX_E), 0, (hipStream_t)stream, d_topk_idx, d_n, rows_pad, n_experts, top_k, (int *)d_ws);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_moe_route(const void *d_h, const void *d_router, const int32_t *d_n, int32_t rows_pad, int32_t hidden, int32_t n_experts, int32_t top_k, int32_t norm_topk,
+                   int32_t *d_topk_idx, void *d_topk_w, void *d_ws, int32_t dtype, void *stream) {
+    if (!d_h || !d_router || !d_n || !d_topk_idx || !d_topk_w || !d_ws || !moe_shape_ok(rows_pad, hidden, GEMM_KC, n_experts, top_k, dtype)) {
+        samd_set_error("samd_moe_route: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == SAMD_F16)
+        hipLaunchKernelGGL(k_moe_route<_Float16>, dim3(rows_pad), dim3(64 * MOE_ROUTE_WAVES), 0, st, (const _Float16 *)d_h, (const _Float16 *)d_router, d_n, hidden, n_experts, top_k, norm_topk,
+                           d_topk_idx, (_Float16 *)d_topk_w);
+    else
+        hipLaunchKernelGGL(k_moe_route<__bf16>, dim3(rows_pad), dim3(64 * MOE_ROUTE_WAVES), 0, st, (const __bf16 *)d_h, (const __bf16 *)d_router, d_n, hidden, n_experts, top_k, norm_topk,
+                           d_topk_idx, (__bf16 *)d_topk_w);
+    LAUNCHCHK();
+    return samd_moe_lists(d_topk_idx, d_n, rows_pad, n_experts, top_k, d_ws, stream);
+}
+
+int samd_moe_gate_up_silu(const void *d_h, const void *d_Wgu, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k,
+                          void *d_act, int32_t dtype, void *stream) {
+    if (!d_h || !d_Wgu || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
+        samd_set_error("samd_moe_gate_up_silu: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
+    }
+    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const hipError_t e = moe_gemm_dispatch<true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu, (const int *)d_ws, d_act, hidden,
+                                                 2 * moe_inter, top_k);
+    if (e != hipSuccess) { samd_set_error("samd_moe_gate_up_silu: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_moe_down_combine(const void *d_act, const void *d_Wdown, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws, int32_t rows_pad,
+                          int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream) {
+    if (!d_act || !d_Wdown || !d_topk_idx || !d_topk_w || !d_n || !d_ws || !d_out || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
+        samd_set_error("samd_moe_down_combine: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    void *y = (char *)d_ws + MOE_WS_Y_OFF;
+    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const hipError_t e = moe_gemm_dispatch<false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown, (const int *)d_ws, y, moe_inter, hidden, top_k);
+    if (e != hipSuccess) { samd_set_error("samd_moe_down_combine: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
+    if (dtype == SAMD_F16)
+        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
+    else
+        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+}  // extern "C"

@@ -245,6 +245,18 @@ def _base_has_qkv_epilogue(lm, runner):
         return False
 
 
+def _base_is_moe(lm, runner):
+    """True for a base model with sparse MLP layers (Qwen3-MoE), given as a runner or as the HF module itself"""
+    shape = getattr(runner, "shape", None)
+    if shape is not None and hasattr(shape, "moe"):
+        return bool(shape.moe)
+    layers = getattr(getattr(lm, "model", None), "layers", None)
+    if layers is None:
+        return False
+    from samd_hip.llama import LlamaRunner
+    return any(LlamaRunner._hf_sparse_layers(layers))
+
+
 class Eagle2(TreeModel):
     """TreeModel plugin over Eagle2Head (reference wrapper: eagle2.py:12-70)."""
     fused = False
@@ -269,6 +281,9 @@ class Eagle2(TreeModel):
         """the head on the library's kernels when the base model runs on them too (a samd_hip LlamaRunner, possibly wrapped);
         SAMD_EAGLE_DEVICE_HEAD=0 keeps the PyTorch forward"""
         runner = lm if hasattr(lm, "forward_rows") else getattr(lm, "runner", None)
+        if _base_is_moe(lm, runner):
+            from samd_hip import SamdError
+            raise SamdError("EAGLE / EAGLE-2 draft heads are not supported on mixture-of-experts base models")
         if _base_has_qkv_epilogue(lm, runner):
             from samd_hip import SamdError
             raise SamdError("EAGLE / EAGLE-2 draft heads are supported on Llama base models only (this base model has a q|k|v bias or q / k norm)")

@@ -19,6 +19,7 @@ from . import (F16, BF16, MAX_DRAFT, TILE_ROWS, QkvEpilogue, SamdError, Session,
                torch_dtype_code)
 from . import fp8 as F8
 from . import mxfp4 as MX
+from . import moe as MOE
 
 
 def _env_weight_format(weight_format):
@@ -58,11 +59,13 @@ def _cfg_get(cfg, name, default=None):
 
 
 class LlamaShape:
-    """the architecture numbers the runner needs (subset of transformers.LlamaConfig, Qwen2Config, Qwen3Config).
+    """the architecture numbers the runner needs (subset of transformers.LlamaConfig, Qwen2Config, Qwen3Config, Qwen3MoeConfig).
 
     qkv_bias: q|k|v carry a bias (Qwen2 / Qwen2.5); qk_norm: q and k go through a per-head RMSNorm before the RoPE (Qwen3).  Both default to
     what the config's model_type implies; from_hf passes what the module actually holds.  Raises SamdError for what the runner does not run:
-    sliding-window layers, an o_proj bias, MLP biases, head_dim != 128."""
+    sliding-window layers, an o_proj bias, MLP biases, head_dim != 128.
+    model_type "qwen3_moe" (which implies qk_norm): n_experts, top_k, moe_inter, norm_topk and `sparse`, the per-layer map of which MLPs are
+    sparse blocks, decided from mlp_only_layers / decoder_sparse_step exactly as Qwen3MoeDecoderLayer.__init__ decides it; `moe` = any."""
 
     def __init__(self, cfg, qkv_bias=None, qk_norm=None):
         self.hidden = int(_cfg_get(cfg, "hidden_size"))
@@ -93,7 +96,20 @@ class LlamaShape:
         if _cfg_get(cfg, "mlp_bias", False):
             raise SamdError("MLP projection biases (mlp_bias=True) are not supported")
         self.qkv_bias = (self.model_type == "qwen2") if qkv_bias is None else bool(qkv_bias)
-        self.qk_norm = (self.model_type == "qwen3") if qk_norm is None else bool(qk_norm)
+        self.qk_norm = (self.model_type in ("qwen3", "qwen3_moe")) if qk_norm is None else bool(qk_norm)
+        # Qwen3-MoE: the layers whose MLP is a sparse block of n_experts experts, top_k of them per token (samd_hip/moe.py)
+        self.n_experts = self.top_k = self.moe_inter = 0
+        self.norm_topk = False
+        self.sparse = [False] * self.layers
+        if self.model_type == "qwen3_moe":
+            self.n_experts = int(_cfg_get(cfg, "num_experts", 0) or 0)
+            self.top_k = int(_cfg_get(cfg, "num_experts_per_tok", 0) or 0)
+            self.moe_inter = int(_cfg_get(cfg, "moe_intermediate_size", 0) or 0)
+            self.norm_topk = bool(_cfg_get(cfg, "norm_topk_prob", False))
+            self.sparse = MOE.sparse_layer_map(self.layers, self.n_experts, _cfg_get(cfg, "mlp_only_layers"), _cfg_get(cfg, "decoder_sparse_step", 1))
+        self.moe = any(self.sparse)
+        if self.moe:
+            MOE.check_shape(self.hidden, self.moe_inter, self.n_experts, self.top_k)
 
     def inv_freq(self):
         """rotary inverse frequencies incl. the 'llama3' scaling rule (what HF's ROPE_INIT_FUNCTIONS computes)."""
@@ -128,7 +144,10 @@ class LlamaRunner:
     BUCKETS = (1, 8, 16, 32, 48, 64, 128)
 
     def __init__(self, shape, weights, max_cache_len, dtype=torch.float16, device="cuda", kv=None, native_gemm=True, packed_lm_head=None,
-                 attention=None, weight_format=None):
+                 attention=None, weight_format=None, draft_head=False):
+        if shape.moe:                                            # (before any device work)
+            MOE.reject_unsupported(_weight_format(weight_format, weights, dtype), native_gemm, draft_head)
+        self.draft_head = bool(draft_head)                       # the decoder is an EAGLE head (forward_rows)
         require_gpu()
         self.shape, self.dtype, self.device = shape, dtype, torch.device(device)
         self.dt = torch_dtype_code(dtype)
@@ -151,7 +170,11 @@ class LlamaRunner:
         # does not fit (say a fine-tune's 32001-row lm_head) goes to the library GEMM on its own, the others keep the kernel
         streams = lambda t: bool(native_gemm) and t.shape[0] % 128 == 0 and t.shape[1] % 256 == 0
         self.native_gemm_max_rows = int(os.environ.get("SAMD_NATIVE_GEMM_MAX_ROWS", 64))     # tuning knob; see forward_rows
-        if quant:
+        # Qwen3-MoE: the experts of a sparse layer exist only packed (samd_hip/moe.py), so the runner behaves like a quantised one: every
+        # bucket up to 64 rows streams, the prompt runs in 64-row chunks, the 128-row bucket is unavailable
+        moe = shape.moe
+        self.route_log = None            # a list: the eager forward_rows appends (layer, n_rows, topk_idx, topk_w) per sparse layer (ignored under capture)
+        if quant or moe:
             self.native_gemm_max_rows = TILE_ROWS            # (no library GEMM to hand rows to: every bucket up to 64 rows streams)
         # L2 warm-up (csrc/warm_device.h): the glue launch in front of a projection also reads the first KiB of every workgroup's
         # weight stream into the consuming XCD's L2 while HBM idles.  KiB per projection workgroup; 0 = off, the default: measured
@@ -280,12 +303,25 @@ class LlamaRunner:
                     lp[k + "_f8"] = pack_f8(l, k)
                 layers.append(lp)
                 continue
-            lp = dict(wgu=pack_gate_up(l["wgu"]), wqkv64=pack_qkv64(l["wqkv"]))
+            sparse = "experts_gu" in l
+            lp = dict(wgu=None if sparse else pack_gate_up(l["wgu"]), wqkv64=pack_qkv64(l["wqkv"]))
             # the 128-column packed q|k|v (split-K projection + samd_rope_kv_write_cs) only where the fused tile form does not exist:
             # with it, no launch of this runner ever reads the other (3.2 GB of a 7B model)
             lp["wqkv"] = pack(l["wqkv"]) if lp["wqkv64"] is None else None
             # the norm-fold forward (include/samd_hip.h: samd_gemm_cs_residual ...) needs the fused q|k|v and gate|up forms
-            fold = (lp["wqkv64"] is not None and lp["wgu"] is not None and s.hidden <= 8192 and os.environ.get("SAMD_NORM_FOLD", "1") != "0")
+            fold = (lp["wqkv64"] is not None and lp["wgu"] is not None and s.hidden <= 8192 and os.environ.get("SAMD_NORM_FOLD", "1") != "0"
+                    and not moe)
+            if sparse:
+                # the experts packed once (per expert the 128-column tiles of the streaming GEMM, gate | up interleaved); no row-major copy stays
+                if tuple(l["router"].shape) != (s.n_experts, s.hidden) or tuple(l["experts_gu"].shape) != (s.n_experts, 2 * s.moe_inter, s.hidden):
+                    raise SamdError(f"sparse layer weights of shapes {tuple(l['router'].shape)}, {tuple(l['experts_gu'].shape)} do not match the shape")
+                lp["moe_gu"], lp["moe_down"] = MOE.pack_experts(l["experts_gu"], l["experts_down"])
+                for k in ("experts_gu", "experts_down"):
+                    l[k] = torch.empty(l[k].shape, dtype=l[k].dtype, device="meta")
+                lp["wo_g"], lp["wdown_g"], lp["wdown"] = pack_groups(l["wo"], fold), None, None
+                lp["wo"] = pack(l["wo"])
+                layers.append(lp)
+                continue
             lp["wo_g"], lp["wdown_g"] = pack_groups(l["wo"], fold), pack_groups(l["wdown"], fold)
             # o_proj / down_proj: the split-K kernel of the 32 / 48 / 64-row buckets can stream the norm-fold forward's group-major copy as well
             # (samd_gemm_skinny_groups, round 6; bit-identical), which makes the 128-column-tile copy redundant: -4 GB of a 7B replica for
@@ -300,7 +336,8 @@ class LlamaRunner:
         self.native_gemm = self.wp["lm_head"] is not None or any(v is not None for l in self.wp["layers"] for v in l.values())
         if not self.native_gemm:
             self.wp = None
-        self.fused_mlp = self.wp is not None and all(l["wgu"] is not None for l in self.wp["layers"])
+        # (a dense layer's decision; forward_rows makes it per layer, sparse layers have their own launches)
+        self.fused_mlp = self.wp is not None and all(l["wgu"] is not None for l in self.wp["layers"] if "moe_gu" not in l)
         # norm-fold forward at <= 16 rows: RMSNorm applied by the consuming projection, residual add by the producing one (6 launches per
         # layer instead of 8, no split-K partials): scripts/norm_fold_bench.py, profiles/r03_norm_fold.md
         self.norm_fold = (self.wp is not None and self.attention == "split"
@@ -327,7 +364,15 @@ class LlamaRunner:
                         raise SamdError(f"{k} must be a contiguous {dtype} tensor on the GPU")
             self.epi = [epi(l, True) for l in weights["layers"]]
             self.epi_nobias = [epi(l, False) for l in weights["layers"]]
-        self.row_major_released = quant                          # (FP8 / MXFP4: there are no row-major projections; prefill runs in 64-row chunks)
+        self.row_major_released = quant or moe                   # (FP8 / MXFP4 / experts: no row-major projections; prefill runs in 64-row chunks)
+        if moe and self.wp:
+            # no launch of an MoE runner reads a row-major projection that has a packed form (every bucket streams): only their shapes stay
+            for l, lp in zip(self.w["layers"], self.wp["layers"]):
+                for k in ("wqkv", "wo", "wgu", "wdown"):
+                    packed = lp.get(k) is not None or lp.get(k + "_g") is not None or (k == "wqkv" and lp.get("wqkv64") is not None)
+                    if k in l and packed and l[k].device.type != "meta":
+                        l[k] = torch.empty(l[k].shape, dtype=l[k].dtype, device="meta")
+            torch.cuda.empty_cache()
         self._length_state(max_cache_len, kv)
         if os.environ.get("SAMD_RELEASE_ROW_MAJOR", "0") == "1":
             self.release_row_major()
@@ -338,8 +383,12 @@ class LlamaRunner:
         def nbytes(t):
             return 0 if t is None or t.device.type == "meta" else t.numel() * t.element_size()
         epi_keys = ("bqkv", "q_norm", "k_norm")
-        rep = dict(row_major=sum(nbytes(t) for l in self.w["layers"] for k, t in l.items() if k not in epi_keys) + nbytes(self.w["lm_head"])
-                   + nbytes(self.w["embed"]))
+        rep = dict(row_major=sum(nbytes(t) for l in self.w["layers"] for k, t in l.items() if k not in epi_keys and k != "router")
+                   + nbytes(self.w["lm_head"]) + nbytes(self.w["embed"]))
+        if self.shape.moe:                                       # routers (model dtype, [E, H]) and the packed experts of the sparse layers
+            rep["moe_router"] = sum(nbytes(l.get("router")) for l in self.w["layers"])
+            for k in ("moe_gu", "moe_down"):
+                rep["packed_" + k] = sum(nbytes(l.get(k)) for l in (self.wp["layers"] if self.wp else ()))
         if self.qkv_epilogue:                                    # Qwen2 q|k|v biases, Qwen3 q / k norm weights (model dtype, read by the RoPE launch)
             rep["qkv_epilogue"] = sum(nbytes(l.get(k)) for l in self.w["layers"] for k in epi_keys)
         if self.wp:
@@ -457,7 +506,8 @@ class LlamaRunner:
         m = lm.model
         parts = (("self_attn", "q_proj"), ("self_attn", "k_proj"), ("self_attn", "v_proj"), ("self_attn", "o_proj"), ("mlp", "gate_proj"),
                  ("mlp", "up_proj"), ("mlp", "down_proj"))
-        linears = [(f"layers.{i}.{a}.{b}", getattr(getattr(lyr, a), b)) for i, lyr in enumerate(m.layers) for a, b in parts]
+        linears = [(f"layers.{i}.{a}.{b}", getattr(getattr(lyr, a), b)) for i, lyr in enumerate(m.layers) for a, b in parts
+                   if hasattr(getattr(lyr, a), b)]               # (a sparse layer's MLP has no gate / up / down projections of its own)
         ckpt_f8 = F8.checkpoint_is_fp8(linears)
         ckpt_f4 = MX.checkpoint_is_mxfp4(linears)
         if F8.is_fp8_dtype(lm.lm_head.weight.dtype) or F8.is_fp8_dtype(m.embed_tokens.weight.dtype):
@@ -467,6 +517,13 @@ class LlamaRunner:
         dtype = dtype or next(p.dtype for p in lm.parameters() if p.dtype.is_floating_point and p.dtype.itemsize >= 2)
         qkv_bias, qk_norm = cls._hf_layer_extras(m.layers)
         shape = LlamaShape(lm.config, qkv_bias=qkv_bias, qk_norm=qk_norm)
+        sparse = cls._hf_sparse_layers(m.layers)
+        if any(sparse) or shape.moe:
+            if sparse != list(shape.sparse):
+                raise SamdError(f"the module's sparse MLP layers {[i for i, x in enumerate(sparse) if x]} are not the ones its config implies "
+                                f"{[i for i, x in enumerate(shape.sparse) if x]} (model_type '{shape.model_type}')")
+            MOE.reject_unsupported("fp8" if ckpt_f8 else ("mxfp4" if ckpt_f4 else weight_format), kw.get("native_gemm", True),
+                                   kw.get("draft_head", False))
         dev = torch.device(device)
 
         def get(t):
@@ -510,6 +567,12 @@ class LlamaRunner:
                     lw[k], lw[k + "_scale"] = F8.fuse_fp8([F8.linear_fp8(x) for x in lins], dev)
                 layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
                 continue
+            if sparse[len(layers)]:                              # router + HF's fused expert tensors [E, 2 I, H] / [E, H, I]
+                layers.append(dict(
+                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj)), wo=get(a.o_proj.weight), router=get(f.gate.weight),
+                    experts_gu=get(f.experts.gate_up_proj), experts_down=get(f.experts.down_proj),
+                    ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
+                continue
             layers.append(dict(
                 wqkv=fuse((a.q_proj, a.k_proj, a.v_proj)),
                 wo=get(a.o_proj.weight),
@@ -534,7 +597,9 @@ class LlamaRunner:
         """(qkv_bias, qk_norm) of an HF decoder stack (Llama, Qwen2, Qwen3).  Every layer's named parameters must be exactly the set the runner
         consumes: the Llama ones, plus q|k|v biases, plus q / k norm weights, the same in every layer (an FP8 projection's weight_scale /
         input_scale count as its own, whether buffers or parameters).  Anything else -- an o_proj or MLP bias, a parameter the runner would
-        not read -- raises instead of being dropped."""
+        not read -- raises instead of being dropped.  A Qwen3-MoE layer whose MLP is a sparse block holds, instead of the three MLP projections,
+        the router `mlp.gate.weight` and the fused expert tensors `mlp.experts.gate_up_proj` / `mlp.experts.down_proj` (dense and sparse layers
+        may alternate); a shared expert or any other MLP parameter raises by name."""
         if len(layers) == 0:
             raise SamdError("the model has no decoder layers")
         def names_of(lyr):
@@ -549,10 +614,18 @@ class LlamaRunner:
         qkv_bias = any(n in names0 for n in cls._QKV_BIAS)
         qk_norm = any(n in names0 for n in cls._QK_NORM)
         want = set(cls._LAYER_PARAMS) | (set(cls._QKV_BIAS) if qkv_bias else set()) | (set(cls._QK_NORM) if qk_norm else set())
+        want_sparse = (want - set(MOE.DENSE_MLP_PARAMS)) | set(MOE.SPARSE_MLP_PARAMS)
         for i, lyr in enumerate(layers):
             names = names_of(lyr)
             if names == want:
                 continue
+            if any(n.startswith("mlp.experts.") or n == "mlp.gate.weight" for n in names):      # a sparse (Qwen3-MoE) layer
+                if names == want_sparse:
+                    continue
+                if any("shared_expert" in n for n in names):
+                    raise SamdError(f"layer {i}: a shared expert is not supported (parameters {sorted(n for n in names if 'shared_expert' in n)})")
+                raise SamdError(f"layer {i}: sparse MLP parameters the runner does not consume {sorted(names - want_sparse)}, or lacks "
+                                f"{sorted(want_sparse - names)} (it reads mlp.gate.weight and the fused mlp.experts.gate_up_proj / down_proj)")
             extra, missing = sorted(names - want), sorted(want - names)
             if "self_attn.o_proj.bias" in extra:
                 raise SamdError(f"layer {i}: o_proj bias is not supported (q|k|v biases are)")
@@ -561,6 +634,11 @@ class LlamaRunner:
             raise SamdError(f"layer {i}: parameters the runner does not consume {extra}, or lacks {missing} "
                             f"(it reads the Llama layer, q|k|v biases (Qwen2) and q / k norm weights (Qwen3))")
         return qkv_bias, qk_norm
+
+    @classmethod
+    def _hf_sparse_layers(cls, layers):
+        """per decoder layer: does its MLP hold experts (an HF Qwen3MoeSparseMoeBlock)?"""
+        return [any(n.startswith("mlp.experts.") for n, _ in lyr.named_parameters()) for lyr in layers]
 
     @classmethod
     def random_init(cls, cfg, max_cache_len, dtype=torch.float16, device="cuda", seed=0, std=0.02, weight_format=None, **kw):
@@ -573,9 +651,17 @@ class LlamaRunner:
             return (torch.randn(size, generator=g, device=device, dtype=torch.float32) * std).to(dtype)
         s = shape
         qkv_out = (s.heads + 2 * s.kv_heads) * s.head_dim
-        layers = [dict(wqkv=rnd(qkv_out, s.hidden), wo=rnd(s.hidden, s.heads * s.head_dim), wgu=rnd(2 * s.inter, s.hidden),
-                       wdown=rnd(s.hidden, s.inter), ln1=torch.ones(s.hidden, dtype=dtype, device=device),
-                       ln2=torch.ones(s.hidden, dtype=dtype, device=device)) for _ in range(s.layers)]
+        if s.moe:
+            MOE.reject_unsupported(_env_weight_format(weight_format), kw.get("native_gemm", True), kw.get("draft_head", False))
+
+        def mlp(i):                                              # a sparse layer: router + fused experts, as from_hf reads them
+            if s.sparse[i]:
+                return dict(router=rnd(s.n_experts, s.hidden), experts_gu=rnd(s.n_experts, 2 * s.moe_inter, s.hidden),
+                            experts_down=rnd(s.n_experts, s.hidden, s.moe_inter))
+            return dict(wgu=rnd(2 * s.inter, s.hidden), wdown=rnd(s.hidden, s.inter))
+        layers = [dict(wqkv=rnd(qkv_out, s.hidden), wo=rnd(s.hidden, s.heads * s.head_dim), **mlp(i),
+                       ln1=torch.ones(s.hidden, dtype=dtype, device=device),
+                       ln2=torch.ones(s.hidden, dtype=dtype, device=device)) for i in range(s.layers)]
 
         def norm_w():                                            # +-[0.5, 2]: a weight on the wrong channel or a skipped norm shows
             mag = 0.5 + 1.5 * torch.rand(s.head_dim, generator=g, device=device)
@@ -590,10 +676,13 @@ class LlamaRunner:
                        lm_head=rnd(s.vocab, s.hidden))
         return cls(shape, weights, max_cache_len, dtype, device, weight_format=_env_weight_format(weight_format), **kw)
 
-    def weight_bytes(self):
+    def weight_bytes(self, experts=None):
         """bytes of weights one decode step streams from HBM (the embedding table is only gathered), tensor by tensor in its own format
-        (an FP8 projection: one byte per weight + its fp32 column scales; an MXFP4 projection: half a byte per weight + one scale byte per 32)."""
-        nb = lambda t: t.numel() * t.element_size()
+        (an FP8 projection: one byte per weight + its fp32 column scales; an MXFP4 projection: half a byte per weight + one scale byte per 32).
+        A sparse (mixture-of-experts) layer counts `experts` of its experts (default: num_experts_per_tok, what the 1-row step streams; a
+        wider step streams the experts its rows are routed to, at most all of them: pass experts=shape.n_experts for that bound)."""
+        n_act = self.shape.top_k if experts is None else int(experts)
+        nb = lambda t: t.numel() * t.element_size() if t.dim() != 3 else t[0].numel() * t.element_size() * min(n_act, t.shape[0])
         n = nb(self.w["lm_head"]) + nb(self.w["norm"])
         if self.weight_format == "mxfp4":
             for l, lp in zip(self.w["layers"], self.wp["layers"]):
@@ -606,10 +695,13 @@ class LlamaRunner:
         return n
 
     # ------------------------------------------------------------------------------------------------
+    def _rows_pad(self, R):
+        return max(R, 16) if self.native_gemm else R             # the skinny GEMM reads 16 / 32 / 64 rows (pad rows are zero)
+
     def _buffers(self, R):
         if R not in self._buf:
             s, dt, dev = self.shape, self.dtype, self.device
-            RP = max(R, 16) if self.native_gemm else R           # the skinny GEMM reads 16 / 32 / 64 rows (pad rows are zero)
+            RP = self._rows_pad(R)
             z = lambda r, *sz: torch.zeros((max(r, RP),) + sz, dtype=dt, device=dev)
             ws_bytes = max(lib().samd_tree_attention_workspace(R, s.heads, s.head_dim), lib().samd_tree_attention_rope_workspace(R, s.heads, s.head_dim))
             part_elems = 0
@@ -626,6 +718,8 @@ class LlamaRunner:
                                 ws=torch.zeros(ws_bytes, dtype=torch.uint8, device=dev), ws_bytes=ws_bytes,
                                 cs=torch.zeros((MAX_DRAFT, s.head_dim), dtype=torch.float32, device=dev),
                                 ssq=torch.zeros((max(s.hidden // 16, 1), 16), dtype=torch.float32, device=dev))
+            if s.moe:
+                self._buf[R]["moe"] = MOE.MoeBuffers(RP, s.hidden, s.moe_inter, s.n_experts, s.top_k, dt, self.dt, dev)
         return self._buf[R]
 
     def max_draft_rows(self):
@@ -646,11 +740,13 @@ class LlamaRunner:
         (logits [R, V], argmax int32[64] with rows < n valid).  x_in [R, hidden]: the rows' input states instead of the
         token embedding (EAGLE draft heads feed fc([embed ; hidden])).  With `self.draft_head` the decoder is an EAGLE head:
         layer 0 has no input norm and lm_head reads the residual stream itself (b["x"] = the head's output states)."""
-        L, s, b, dt, st = lib(), self.shape, self._buffers(R), self.dt, current_stream()
-        RP, part = b["rows_pad"], b["part"]
-        if RP > self.native_gemm_max_rows and self.row_major_released:
+        if self.shape.moe:
+            MOE.reject_unsupported(draft_head=getattr(self, "draft_head", False))     # (an attribute set after construction)
+        if self._rows_pad(R) > self.native_gemm_max_rows and self.row_major_released:      # (before the bucket's buffers exist)
             raise SamdError(f"a {R}-row forward needs the row-major projection matrices (released: SAMD_RELEASE_ROW_MAJOR / release_row_major()); "
                             f"drafts above {self.native_gemm_max_rows} nodes and the library-GEMM path are unavailable on this runner")
+        L, s, b, dt, st = lib(), self.shape, self._buffers(R), self.dt, current_stream()
+        RP, part = b["rows_pad"], b["part"]
         if (self.norm_fold and RP == 16 and x_in is None and d_vis is None and not getattr(self, "draft_head", False)
                 and RP <= self.native_gemm_max_rows):
             return self._forward_rows_fold(R, b, d_tokens, d_relpos, d_mask, d_L, d_n)
@@ -695,6 +791,8 @@ class LlamaRunner:
             if x_in.data_ptr() != b["x"].data_ptr():              # a caller may stage the rows in the bucket's own buffer
                 b["x"][:rows_in].copy_(x_in[:rows_in])            # rows past d_n are never consumed
         head = getattr(self, "draft_head", False)
+        # route_log is for tests and profiling of the eager forward: a captured launch sequence cannot clone to the host's list, so it is ignored there
+        log_routes = s.moe and self.route_log is not None and not torch.cuda.is_current_stream_capturing()
         block = self.attention == "block"
         vt = self.v_transposed and not block          # the split launches over a transposed V cache (round 6)
         if self.attention != "split3":
@@ -756,7 +854,16 @@ class LlamaRunner:
             src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"), f4=wp.get("wo_f4"))
             check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(src), _ptr(w["ln2"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, n_p, stride,
                                       None, st))           # (no warm-up hint: gate|up is packed group-major, the hint describes 128-column tiles)
-            if self.fused_mlp and RP <= self.native_gemm_max_rows:
+            if "moe_gu" in wp:
+                # sparse layer: route -> gathered expert gate|up + SiLU -> gathered expert down + combine (csrc/gemm_kernels.hip, samd_hip/moe.py)
+                mb = b["moe"]
+                mb.route(b["h"], w["router"], d_n, s.norm_topk)
+                if log_routes:
+                    idx = mb.topk_idx.clone()
+                    self.route_log.append((li, int((idx[:, 0] >= 0).sum()), idx, mb.topk_w.clone()))
+                delta, dn, dstride = mb.experts(b["h"], wp["moe_gu"], wp["moe_down"], d_n), 0, 0
+                continue
+            if wp.get("wgu") is not None and RP <= self.native_gemm_max_rows:
                 check(L.samd_gemm_pairs_silu(_ptr(b["h"]), _ptr(wp["wgu"]), RP, s.inter, s.hidden, _ptr(b["act"]), dt, st))
             else:
                 src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"), f4=wp.get("wgu_f4"))     # wgu is only ever packed for the fused form (or FP8)

@@ -114,9 +114,9 @@ def _tables():
     # patch_dict: what SamdModel swaps the LM's forward for (its own decoder loop, samd_hip.llama.LlamaRunner);
     # attn_patch_dict: a forward with HF's LlamaAttention signature for callers that keep driving the HF module themselves
     patches = {LlamaForCausalLM: [("forward", _runner_for)]}
-    # Qwen2 / Qwen2.5 (q|k|v bias) and Qwen3 (per-head q / k RMSNorm): the same runner, with its q|k|v epilogue; skipped where the installed
-    # transformers lacks them
-    for mod, name in (("qwen2", "Qwen2ForCausalLM"), ("qwen3", "Qwen3ForCausalLM")):
+    # Qwen2 / Qwen2.5 (q|k|v bias), Qwen3 (per-head q / k RMSNorm) and Qwen3-MoE (Qwen3 with sparse MLP layers): the same runner, with its
+    # q|k|v epilogue and its expert launches; skipped where the installed transformers lacks them
+    for mod, name in (("qwen2", "Qwen2ForCausalLM"), ("qwen3", "Qwen3ForCausalLM"), ("qwen3_moe", "Qwen3MoeForCausalLM")):
         try:
             import importlib
             patches[getattr(importlib.import_module(f"transformers.models.{mod}.modeling_{mod}"), name)] = [("forward", _runner_for)]

@@ -9,7 +9,7 @@ forms share one device state:
   * prefill() / decode() / update_state(): the granular form with the reference's intermediate tensors
     (sample_p, Candidates, best_candidate, accept_length), for tools that drive the steps themselves.
 
-`lm` may be a transformers LlamaForCausalLM, Qwen2ForCausalLM or Qwen3ForCausalLM (its weights are walked by samd_hip.llama.LlamaRunner), a LlamaRunner, or
+`lm` may be a transformers LlamaForCausalLM, Qwen2ForCausalLM, Qwen3ForCausalLM or Qwen3MoeForCausalLM (its weights are walked by samd_hip.llama.LlamaRunner), a LlamaRunner, or
 any verifier object with prefill/verify/compact/bucket (samd_hip.engine.ScriptedVerifier in tests).
 """
 import os
@@ -88,7 +88,7 @@ class SamdModel(nn.Module):
                 self._runner_factory = dict(entries)["forward"]
         if self.verifier is None and self._runner_factory is None:
             raise samd_hip.SamdError(f"SamdModel: unsupported lm type {type(self.lm).__name__} "
-                                     "(expected transformers.LlamaForCausalLM, Qwen2ForCausalLM, Qwen3ForCausalLM, samd_hip.llama.LlamaRunner or a verifier)")
+                                     "(expected transformers.LlamaForCausalLM, Qwen2ForCausalLM, Qwen3ForCausalLM, Qwen3MoeForCausalLM, samd_hip.llama.LlamaRunner or a verifier)")
 
     def init_seq_position_ids(self):
         return torch.arange(0, self.samd_config.max_predicts, dtype=torch.long, device=self.device).unsqueeze(0)

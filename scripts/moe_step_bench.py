@@ -1,0 +1,146 @@
+"""moe_step_bench.py -- what the mixture-of-experts path costs on Qwen3-30B-A3B geometry (hidden 2048, moe_intermediate 768, 128 experts, top-8),
+random-init weights, per row bucket 1 / 8 / 16 / 64.
+
+  experts  per bucket: distinct experts touched per layer, bytes streamed by the three launches (route, gate|up + SiLU, down + combine) divided
+           by their graph-replay time, and beside it the SAME number of bytes streamed by the dense samd_gemm_pairs_silu + samd_gemm_skinny on
+           an MLP of equal weight size, in the same process -- the yardstick (never the new kernels against themselves).  --layers distinct
+           weight sets are visited per replay so that no replay finds its weights in the Infinity Cache.
+  step     graph-replay time of one verify forward per bucket for a --depth layer Qwen3-30B-A3B stack, and its ratio to the 1-row
+           (autoregressive) step.
+
+Without --step every step runs as a child process of its own under its own time limit, and nothing more is started after a step that failed.
+--buckets 1 keeps a profiler's per-kernel statistics to one bucket: rocprofv3 --kernel-trace --stats -- python scripts/moe_step_bench.py --step experts --buckets 1
+usage: python scripts/moe_step_bench.py [--step experts|step] [--reps 30] [--layers 4] [--depth 12] [--buckets 1,8,16,64]"""
+import argparse, json, os, subprocess, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "sam-decoding_amd")]
+
+A3B = dict(model_type="qwen3_moe", hidden_size=2048, intermediate_size=6144, moe_intermediate_size=768, num_attention_heads=32, num_key_value_heads=4,
+           head_dim=128, vocab_size=151936, max_position_embeddings=40960, rms_norm_eps=1e-6, rope_theta=1e6, num_experts=128, num_experts_per_tok=8,
+           norm_topk_prob=True, decoder_sparse_step=1, mlp_only_layers=[])
+BUCKETS = (1, 8, 16, 64)
+STEP_LIMITS = {"experts": 420, "step": 420}        # seconds per child process
+
+
+def replay_us(fn, reps):
+    import torch
+    fn(); torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    g.replay(); torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        g.replay()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e6
+
+
+def step_experts(a):
+    import torch
+    import samd_hip
+    from samd_hip import moe as MOE, _ptr, check, current_stream, lib
+    H, I, E, k = A3B["hidden_size"], A3B["moe_intermediate_size"], A3B["num_experts"], A3B["num_experts_per_tok"]
+    dt, L = torch.bfloat16, lib()
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *s: (torch.randn(s, generator=g, device="cuda") * 0.02).to(dt)
+    sets = []
+    for _ in range(a.layers):
+        sets.append((rnd(E, H) * 50, *MOE.pack_experts(rnd(E, 2 * I, H), rnd(E, H, I))))
+    for n in a.buckets:
+        RP = max(16, n)
+        h = torch.randn((RP, H), generator=g, device="cuda").to(dt)
+        d_n = torch.tensor([n], dtype=torch.int32, device="cuda")
+        bufs = [MOE.MoeBuffers(RP, H, I, E, k, dt, samd_hip.BF16, "cuda") for _ in sets]
+
+        def moe():
+            for (router, pgu, pd), b in zip(sets, bufs):
+                b.route(h, router, d_n, True)
+                b.experts(h, pgu, pd, d_n)
+        t_moe = replay_us(moe, a.reps) / a.layers
+        active = [b.routing_state()[0] for b in bufs]
+        # the three calls on their own (each over all the weight sets, so the weights stay cold); lists = the second kernel of the route call
+        L_ = lib()
+        parts = dict(
+            route=lambda: [b.route(h, r, d_n, True) for (r, _, _), b in zip(sets, bufs)],
+            lists=lambda: [b.lists(d_n) for b in bufs],
+            gate_up=lambda: [check(L_.samd_moe_gate_up_silu(_ptr(h), _ptr(pgu), _ptr(b.ws), RP, H, I, E, k, _ptr(b.act), samd_hip.BF16, current_stream()))
+                             for (_, pgu, _), b in zip(sets, bufs)],
+            down_combine=lambda: [check(L_.samd_moe_down_combine(_ptr(b.act), _ptr(pd), _ptr(b.topk_idx), _ptr(b.topk_w), _ptr(d_n), _ptr(b.ws), RP, H, I, E, k,
+                                                                 _ptr(b.out), samd_hip.BF16, current_stream())) for (_, _, pd), b in zip(sets, bufs)])
+        part_us = {name: round(replay_us(fn, a.reps) / a.layers, 1) for name, fn in parts.items()}
+        act_mean = sum(active) / len(active)
+        nbytes = act_mean * 3 * H * I * 2
+        # the dense yardstick: one MLP whose gate|up and down matrices hold as many bytes (intermediate = active experts x 768, a multiple of 128)
+        Id = int(round(act_mean)) * I
+        dense = []
+        for _ in sets:
+            wgu, wd = rnd(2 * Id, H), rnd(H, Id)
+            pgu, pdn = torch.empty_like(wgu), torch.empty_like(wd)
+            check(L.samd_gemm_pack_groups(_ptr(wgu), _ptr(pgu), 2 * Id, H, current_stream()))
+            check(L.samd_gemm_pack_weights(_ptr(wd), _ptr(pdn), H, Id, current_stream()))
+            dense.append((pgu, pdn))
+            del wgu, wd
+        act = torch.zeros((RP, Id), dtype=dt, device="cuda")
+        out = torch.zeros((RP, H), dtype=dt, device="cuda")
+        sp = L.samd_gemm_splits(H, Id, RP)
+        part = torch.zeros(max(sp * RP * H, 1), dtype=torch.float32, device="cuda")
+
+        def mlp():
+            for pgu, pdn in dense:
+                check(L.samd_gemm_pairs_silu(_ptr(h), _ptr(pgu), RP, Id, H, _ptr(act), samd_hip.BF16, current_stream()))
+                check(L.samd_gemm_skinny(_ptr(act), _ptr(pdn), RP, H, Id, sp, _ptr(part), _ptr(out), samd_hip.BF16, current_stream()))
+        t_dense = replay_us(mlp, a.reps) / a.layers
+        print(json.dumps(dict(step="experts", rows=n, bucket=RP, experts_touched=active, mbytes=round(nbytes / 1e6, 1), moe_us=round(t_moe, 1), calls_us=part_us,
+                              moe_tb_s=round(nbytes / t_moe / 1e6, 3), dense_us=round(t_dense, 1), dense_tb_s=round(nbytes / t_dense / 1e6, 3),
+                              moe_over_dense=round(t_moe / t_dense, 2))), flush=True)
+        del dense, bufs, act, out, part
+        torch.cuda.empty_cache()
+
+
+def step_forward(a):
+    import torch
+    import samd_hip
+    from samd_hip.llama import LlamaRunner
+    runner = LlamaRunner.random_init(dict(A3B, num_hidden_layers=a.depth), 2048, torch.bfloat16, seed=0)
+    sess = samd_hip.Session(4096)
+    sess.reset()
+    res, touched = {}, {}
+    for n in a.buckets:
+        toks = torch.arange(5, 5 + n, dtype=torch.int32, device="cuda"); par = torch.arange(-1, n - 1, dtype=torch.int32, device="cuda")
+        sess.set_draft(toks, par, n)
+        sess.set_cache_length(800)
+        R = runner.bucket(n)
+        runner.warm(R)
+        runner.route_log = []
+        runner.verify(sess, R); torch.cuda.synchronize()
+        touched[n] = round(sum(len(set(e[2][:e[1]].flatten().tolist())) for e in runner.route_log) / max(len(runner.route_log), 1), 1)
+        runner.route_log = None
+        res[n] = round(replay_us(lambda: runner.verify(sess, R), a.reps) / 1e3, 4)
+    print(json.dumps(dict(step="step", depth=a.depth, step_ms=res, experts_touched_per_layer=touched,
+                          ratio_to_1_row={n: round(res[n] / res[1], 3) for n in a.buckets if 1 in res})), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--step", choices=("experts", "step"))
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--layers", type=int, default=4)
+    ap.add_argument("--depth", type=int, default=12)
+    ap.add_argument("--buckets", default=",".join(map(str, BUCKETS)), help="row counts, comma separated")
+    a = ap.parse_args()
+    a.buckets = tuple(int(b) for b in a.buckets.split(","))
+    if a.step == "experts":
+        return step_experts(a)
+    if a.step == "step":
+        return step_forward(a)
+    for name, limit in STEP_LIMITS.items():        # a fresh process per step, each under its own limit; a failure ends the run
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(a.reps), "--layers", str(a.layers),
+               "--depth", str(a.depth), "--buckets", ",".join(map(str, a.buckets))]
+        rc = subprocess.run(cmd).returncode
+        if rc != 0:
+            raise SystemExit(f"step {name} ended with status {rc}; nothing more is started")
+
+
+if __name__ == "__main__":
+    main()
