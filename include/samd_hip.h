@@ -695,6 +695,20 @@ int samd_moe_gate_up_silu(const void *d_h, const void *d_Wgu, const void *d_ws, 
                           int32_t top_k, void *d_act, int32_t dtype, void *stream);
 int samd_moe_down_combine(const void *d_act, const void *d_Wdown, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
                           int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream);
+/* The same two expert launches over MXFP4 experts (e2m1 elements, one e8m0 scale per 32 along k; samd_hip/mxfp4.py has the numeric contract:
+ * W = fp4(q) * 2^(e8 - 127), exact in the model dtype, fp32 accumulation in chunk order, the epilogues' roundings unchanged).  Routing, the
+ * workspace, samd_moe_route / samd_moe_lists and the combine are the calls above; shapes, grids and errors are theirs; both are capturable.
+ *   d_Wgu4 / d_Wdown4      the E experts laid end to end as ONE matrix of E * N rows in samd_gemm_pack_f4's layout (N = 2 * moe_inter, K =
+ *                          hidden for gate|up; N = hidden, K = moe_inter for down): E * N * K / 2 + E * N * K / 32 bytes, expert e's tile t
+ *                          being tile e * N / 128 + t.  For gate|up the rows are permuted BEFORE packing so that a tile holds matching
+ *                          columns: packed row 128 t + r of an expert is its gate row 64 t + r for r < 64 and its up row
+ *                          moe_inter + 64 t + r - 64 otherwise (samd_moe_pack_experts' interleave; samd_hip/moe.py: pack_experts_mxfp4).
+ *   samd_moe_gate_up_silu_f4   as samd_moe_gate_up_silu.
+ *   samd_moe_down_combine_f4   as samd_moe_down_combine: the 4-bit down launch, then the same combine kernel. */
+int samd_moe_gate_up_silu_f4(const void *d_h, const void *d_Wgu4, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
+                             int32_t top_k, void *d_act, int32_t dtype, void *stream);
+int samd_moe_down_combine_f4(const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                             int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream);
 
 /* ---- scripted verifier (tests, smoke and bench only): replaces the LM arg-max of every draft node by
  * the next token of a target stream while the node's context (committed history + root->node path) is a

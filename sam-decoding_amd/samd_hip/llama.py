@@ -144,9 +144,22 @@ class LlamaRunner:
     BUCKETS = (1, 8, 16, 32, 48, 64, 128)
 
     def __init__(self, shape, weights, max_cache_len, dtype=torch.float16, device="cuda", kv=None, native_gemm=True, packed_lm_head=None,
-                 attention=None, weight_format=None, draft_head=False):
-        if shape.moe:                                            # (before any device work)
+                 attention=None, weight_format=None, draft_head=False, expert_format=MOE.AUTO):
+        # expert_format "mxfp4": the experts of every sparse layer, and nothing else, as MXFP4 (samd_hip/moe.py); the default takes env
+        # SAMD_EXPERT_FORMAT, and 4-bit expert tensors in `weights` make the runner "mxfp4" by themselves.  A knob of its own: weight_format
+        # means the four dense projections and stays rejected for models with sparse layers
+        experts4 = [MOE.is_4bit(l["experts_gu"]) or MOE.is_4bit(l["experts_down"]) for l in weights["layers"] if "experts_gu" in l]
+        self.expert_format = MOE.resolve_expert_format(expert_format, any(experts4), shape.moe)      # (before any device work, as the next)
+        if shape.moe:
             MOE.reject_unsupported(_weight_format(weight_format, weights, dtype), native_gemm, draft_head)
+        if any(experts4):
+            if not all(experts4):
+                raise SamdError(f"a mix of 4-bit and model-dtype sparse layers ({sum(experts4)} of {len(experts4)} carry MXFP4 experts): "
+                                "the runner takes the experts of all sparse layers in one format")
+            for i, l in enumerate(weights["layers"]):
+                if "experts_gu" in l:
+                    MOE.check_quantised_experts(l["experts_gu"], l.get("experts_gu_scale"), l["experts_down"], l.get("experts_down_scale"), dtype,
+                                                f"layer {i} experts")
         self.draft_head = bool(draft_head)                       # the decoder is an EAGLE head (forward_rows)
         require_gpu()
         self.shape, self.dtype, self.device = shape, dtype, torch.device(device)
@@ -313,11 +326,24 @@ class LlamaRunner:
                     and not moe)
             if sparse:
                 # the experts packed once (per expert the 128-column tiles of the streaming GEMM, gate | up interleaved); no row-major copy stays
-                if tuple(l["router"].shape) != (s.n_experts, s.hidden) or tuple(l["experts_gu"].shape) != (s.n_experts, 2 * s.moe_inter, s.hidden):
+                gu_cols = s.hidden // 2 if MOE.is_4bit(l["experts_gu"]) else s.hidden
+                if tuple(l["router"].shape) != (s.n_experts, s.hidden) or tuple(l["experts_gu"].shape) != (s.n_experts, 2 * s.moe_inter, gu_cols):
                     raise SamdError(f"sparse layer weights of shapes {tuple(l['router'].shape)}, {tuple(l['experts_gu'].shape)} do not match the shape")
-                lp["moe_gu"], lp["moe_down"] = MOE.pack_experts(l["experts_gu"], l["experts_down"])
-                for k in ("experts_gu", "experts_down"):
-                    l[k] = torch.empty(l[k].shape, dtype=l[k].dtype, device="meta")
+                if self.expert_format == "mxfp4":
+                    # the experts as e2m1 + e8m0 (the checkpoint's own, already checked, or quantised here), packed once; only shapes stay
+                    ekeys = ("experts_gu", "experts_gu_scale", "experts_down", "experts_down_scale")
+                    if MOE.is_4bit(l["experts_gu"]):
+                        quad = tuple(MX._bytes(l[k]).to(self.device).contiguous() for k in ekeys)
+                    else:
+                        quad = MOE.quantize_experts(l["experts_gu"], l["experts_down"], dtype, f"layer {len(layers)} experts")
+                    lp["moe_gu"], lp["moe_down"] = MOE.pack_experts_mxfp4(*quad)
+                    for k, t in zip(ekeys, quad):
+                        l[k] = torch.empty(t.shape, dtype=torch.uint8, device="meta")
+                    del quad
+                else:
+                    lp["moe_gu"], lp["moe_down"] = MOE.pack_experts(l["experts_gu"], l["experts_down"])
+                    for k in ("experts_gu", "experts_down"):
+                        l[k] = torch.empty(l[k].shape, dtype=l[k].dtype, device="meta")
                 lp["wo_g"], lp["wdown_g"], lp["wdown"] = pack_groups(l["wo"], fold), None, None
                 lp["wo"] = pack(l["wo"])
                 layers.append(lp)
@@ -406,6 +432,7 @@ class LlamaRunner:
         rep["total"] = sum(rep.values())
         if self.weight_format in ("fp8", "mxfp4"):
             rep["weight_format"] = self.weight_format
+        rep["expert_format"] = self.expert_format                # None: experts (if any) in the model dtype; packed_moe_* are the bytes held
         return rep
 
     def release_row_major(self):
@@ -493,7 +520,7 @@ class LlamaRunner:
 
     # ------------------------------------------------------------------------------------------------
     @classmethod
-    def from_hf(cls, lm, max_cache_len, dtype=None, device="cuda", share_weights=None, weight_format=None, **kw):
+    def from_hf(cls, lm, max_cache_len, dtype=None, device="cuda", share_weights=None, weight_format=None, expert_format=MOE.AUTO, **kw):
         """weights of a transformers LlamaForCausalLM (what the reference passes as `lm`).  share_weights (default: env
         SAMD_SHARE_HF_WEIGHTS, off): re-point the HF module's q/k/v and gate/up weights at row slices of the runner's concatenated
         matrices -- saves one row-major copy of the model, but the caller's parameters become views of storage the runner owns
@@ -501,7 +528,11 @@ class LlamaRunner:
         weight_format (default: env SAMD_WEIGHT_FORMAT, unset = the model dtype): "fp8" quantises the projections on load.  A module whose
         projections already hold float8_e4m3fn weights with a `weight_scale` (per tensor, [N] or [N, 1]) is imported as it is (samd_hip/fp8.py).
         "mxfp4" quantises them per block of 32 (no calibration: for benches and tests); a module whose projections hold float4_e2m1fn_x2 or uint8
-        weights [N, K/2] with an e8m0 `weight_scale` [N, K/32] is imported as it is (samd_hip/mxfp4.py)."""
+        weights [N, K/2] with an e8m0 `weight_scale` [N, K/32] is imported as it is (samd_hip/mxfp4.py).
+        expert_format (default: env SAMD_EXPERT_FORMAT, unset = the model dtype; models with sparse layers only): "mxfp4" quantises the EXPERTS
+        of every sparse layer on load (uncalibrated: for benches and tests); router, attention, dense MLP layers, embedding and lm_head stay in
+        the model dtype.  A module whose sparse layers carry 4-bit expert tensors with their block scales (samd_hip/moe.py has the convention)
+        is imported as it is and makes the runner "mxfp4" by itself; an explicit expert_format=None against such a module raises."""
         weight_format = _env_weight_format(weight_format)
         m = lm.model
         parts = (("self_attn", "q_proj"), ("self_attn", "k_proj"), ("self_attn", "v_proj"), ("self_attn", "o_proj"), ("mlp", "gate_proj"),
@@ -524,6 +555,20 @@ class LlamaRunner:
                                 f"{[i for i, x in enumerate(shape.sparse) if x]} (model_type '{shape.model_type}')")
             MOE.reject_unsupported("fp8" if ckpt_f8 else ("mxfp4" if ckpt_f4 else weight_format), kw.get("native_gemm", True),
                                    kw.get("draft_head", False))
+        # 4-bit experts: decided and checked on the module's own tensors, before anything moves to the device (the runner resolves the
+        # format again from the weights it is given)
+        experts4 = [cls._hf_experts_are_4bit(lyr, i) for i, lyr in enumerate(m.layers) if sparse[i]]
+        MOE.resolve_expert_format(expert_format, any(experts4), any(sparse) or shape.moe)
+        if any(experts4):
+            if not all(experts4):
+                plain = [i for i, sp in enumerate(sparse) if sp and not cls._hf_experts_are_4bit(m.layers[i], i)][:3]
+                raise SamdError(f"a mix of 4-bit and model-dtype sparse layers ({sum(experts4)} of {len(experts4)} carry MXFP4 experts; e.g. "
+                                f"layers {plain} do not): the runner takes the experts of all sparse layers in one format")
+            for i, lyr in enumerate(m.layers):
+                if sparse[i]:
+                    ex = lyr.mlp.experts
+                    MOE.check_quantised_experts(ex.gate_up_proj.detach(), getattr(ex, "gate_up_proj_scale", None), ex.down_proj.detach(),
+                                                getattr(ex, "down_proj_scale", None), dtype, f"layers.{i}.mlp.experts")
         dev = torch.device(device)
 
         def get(t):
@@ -567,6 +612,14 @@ class LlamaRunner:
                     lw[k], lw[k + "_scale"] = F8.fuse_fp8([F8.linear_fp8(x) for x in lins], dev)
                 layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
                 continue
+            if sparse[len(layers)] and any(experts4):            # router + the 4-bit expert tensors and their block scales, as they are
+                ex, raw = f.experts, lambda t: MX._bytes(t.detach()).to(dev).contiguous()
+                layers.append(dict(
+                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj)), wo=get(a.o_proj.weight), router=get(f.gate.weight),
+                    experts_gu=raw(ex.gate_up_proj), experts_gu_scale=raw(ex.gate_up_proj_scale),
+                    experts_down=raw(ex.down_proj), experts_down_scale=raw(ex.down_proj_scale),
+                    ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
+                continue
             if sparse[len(layers)]:                              # router + HF's fused expert tensors [E, 2 I, H] / [E, H, I]
                 layers.append(dict(
                     wqkv=fuse((a.q_proj, a.k_proj, a.v_proj)), wo=get(a.o_proj.weight), router=get(f.gate.weight),
@@ -584,7 +637,17 @@ class LlamaRunner:
             import logging
             logging.getLogger("samd_hip").info("LlamaRunner.from_hf: %d fused projection groups now back the HF module's q/k/v and gate/up "
                                                "weights (share_weights); its parameters are views of the runner's matrices", shared[0])
-        return cls(shape, weights, max_cache_len, dtype, device, weight_format=weight_format, **kw)
+        return cls(shape, weights, max_cache_len, dtype, device, weight_format=weight_format, expert_format=expert_format, **kw)
+
+    @classmethod
+    def _hf_experts_are_4bit(cls, lyr, i):
+        """does sparse layer i carry pre-quantised experts?  Both fused tensors 4-bit: True; neither: False; one of them raises by name"""
+        ex = lyr.mlp.experts
+        gu, dn = MOE.is_4bit(ex.gate_up_proj), MOE.is_4bit(ex.down_proj)
+        if gu != dn:
+            raise SamdError(f"layers.{i}.mlp.experts: gate_up_proj is {ex.gate_up_proj.dtype} and down_proj {ex.down_proj.dtype}; "
+                            "4-bit experts need both tensors 4-bit")
+        return gu
 
     # the parameters of a decoder layer that from_hf reads (named_parameters; FP8 checkpoints' weight_scale tensors are buffers)
     _LAYER_PARAMS = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
@@ -609,7 +672,11 @@ class LlamaRunner:
             skip = {f"{n[:-len('.weight')]}.{sc}" for n, p in lyr.named_parameters()
                     if n.endswith(".weight") and (F8.is_fp8_dtype(p.dtype) or _is_f4_tensor(p))
                     for sc in ("weight_scale", "input_scale")}
-            return {n for n, _ in lyr.named_parameters()} - skip
+            # the block scales of 4-bit expert tensors (samd_hip/moe.py), which the runner reads; beside plain experts they are extra
+            params = dict(lyr.named_parameters())
+            if any(MOE.is_4bit(params.get(n)) for n in MOE.SPARSE_MLP_PARAMS[1:]):
+                skip |= set(MOE.EXPERT_SCALE_PARAMS)
+            return set(params) - skip
         names0 = names_of(layers[0])
         qkv_bias = any(n in names0 for n in cls._QKV_BIAS)
         qk_norm = any(n in names0 for n in cls._QK_NORM)
@@ -641,10 +708,12 @@ class LlamaRunner:
         return [any(n.startswith("mlp.experts.") for n, _ in lyr.named_parameters()) for lyr in layers]
 
     @classmethod
-    def random_init(cls, cfg, max_cache_len, dtype=torch.float16, device="cuda", seed=0, std=0.02, weight_format=None, **kw):
-        """random-init weights of the given architecture, created directly in HBM (no checkpoint on the box).  weight_format: as from_hf's."""
+    def random_init(cls, cfg, max_cache_len, dtype=torch.float16, device="cuda", seed=0, std=0.02, weight_format=None, expert_format=MOE.AUTO, **kw):
+        """random-init weights of the given architecture, created directly in HBM (no checkpoint on the box).  weight_format, expert_format:
+        as from_hf's."""
         require_gpu()
         shape = LlamaShape(cfg)
+        MOE.resolve_expert_format(expert_format, False, shape.moe)
         g = torch.Generator(device=device).manual_seed(seed)
 
         def rnd(*size):
@@ -674,13 +743,14 @@ class LlamaRunner:
                 l["q_norm"], l["k_norm"] = norm_w(), norm_w()
         weights = dict(embed=rnd(s.vocab, s.hidden), layers=layers, norm=torch.ones(s.hidden, dtype=dtype, device=device),
                        lm_head=rnd(s.vocab, s.hidden))
-        return cls(shape, weights, max_cache_len, dtype, device, weight_format=_env_weight_format(weight_format), **kw)
+        return cls(shape, weights, max_cache_len, dtype, device, weight_format=_env_weight_format(weight_format), expert_format=expert_format, **kw)
 
     def weight_bytes(self, experts=None):
         """bytes of weights one decode step streams from HBM (the embedding table is only gathered), tensor by tensor in its own format
         (an FP8 projection: one byte per weight + its fp32 column scales; an MXFP4 projection: half a byte per weight + one scale byte per 32).
-        A sparse (mixture-of-experts) layer counts `experts` of its experts (default: num_experts_per_tok, what the 1-row step streams; a
-        wider step streams the experts its rows are routed to, at most all of them: pass experts=shape.n_experts for that bound)."""
+        A sparse (mixture-of-experts) layer counts `experts` of its experts in the format they are held in (MXFP4 experts: elements + block
+        scales; default: num_experts_per_tok, what the 1-row step streams; a wider step streams the experts its rows are routed to, at most
+        all of them: pass experts=shape.n_experts for that bound)."""
         n_act = self.shape.top_k if experts is None else int(experts)
         nb = lambda t: t.numel() * t.element_size() if t.dim() != 3 else t[0].numel() * t.element_size() * min(n_act, t.shape[0])
         n = nb(self.w["lm_head"]) + nb(self.w["norm"])
@@ -861,7 +931,7 @@ class LlamaRunner:
                 if log_routes:
                     idx = mb.topk_idx.clone()
                     self.route_log.append((li, int((idx[:, 0] >= 0).sum()), idx, mb.topk_w.clone()))
-                delta, dn, dstride = mb.experts(b["h"], wp["moe_gu"], wp["moe_down"], d_n), 0, 0
+                delta, dn, dstride = mb.experts(b["h"], wp["moe_gu"], wp["moe_down"], d_n, self.expert_format), 0, 0
                 continue
             if wp.get("wgu") is not None and RP <= self.native_gemm_max_rows:
                 check(L.samd_gemm_pairs_silu(_ptr(b["h"]), _ptr(wp["wgu"]), RP, s.inter, s.hidden, _ptr(b["act"]), dt, st))

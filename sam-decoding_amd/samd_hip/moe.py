@@ -4,16 +4,42 @@ samd_moe_down_combine).
 
 A sparse layer holds `mlp.gate.weight` [E, H] (the router), `mlp.experts.gate_up_proj` [E, 2 I, H] and `mlp.experts.down_proj` [E, H, I] (this
 transformers' fused form).  The experts are packed once at load -- per expert the 128-column tile layout of the dense streaming GEMM, gate
-and up interleaved in groups of 64 so that a tile holds matching columns, experts end to end -- and no row-major copy is kept."""
+and up interleaved in groups of 64 so that a tile holds matching columns, experts end to end -- and no row-major copy is kept.
+
+expert_format "mxfp4" (EXPERT_FORMATS) keeps the EXPERTS, and nothing else, as MXFP4 (samd_hip/mxfp4.py: e2m1 elements, one e8m0 scale per 32
+along k): q [E, N, K/2] + e8 [E, N, K/32] per fused tensor, packed by samd_gemm_pack_f4 as one matrix of E * N rows and streamed by
+samd_moe_gate_up_silu_f4 / samd_moe_down_combine_f4.  Router, attention, dense MLP layers, embedding and lm_head stay in the model dtype.
+transformers has no quantised form of its fused Qwen3-MoE expert module, so the pre-quantised convention is this project's own: a sparse
+layer's `mlp.experts.gate_up_proj` [E, 2 I, H/2] and `mlp.experts.down_proj` [E, H, I/2] as uint8 or float4_e2m1fn_x2 (low nibble = the even
+element), with `mlp.experts.gate_up_proj_scale` [E, 2 I, H/32] and `mlp.experts.down_proj_scale` [E, H, I/32] as uint8 or float8_e8m0fnu,
+parameters or buffers; in a raw weights dict: experts_gu, experts_gu_scale, experts_down, experts_down_scale."""
+import os
+
 import torch
 
 from . import SamdError, _ptr, check, current_stream, lib
+from . import mxfp4 as MX
 
 MAX_EXPERTS = 256
 MAX_TOPK = 8
 # the parameters of a sparse layer's MLP that the runner reads (named_parameters of an HF Qwen3MoeDecoderLayer)
 SPARSE_MLP_PARAMS = ("mlp.gate.weight", "mlp.experts.gate_up_proj", "mlp.experts.down_proj")
 DENSE_MLP_PARAMS = ("mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+# the block scales of pre-quantised (4-bit) expert tensors: consumed only beside 4-bit expert tensors
+EXPERT_SCALE_PARAMS = ("mlp.experts.gate_up_proj_scale", "mlp.experts.down_proj_scale")
+# what the experts of the sparse layers may be held in: None = the model dtype
+EXPERT_FORMATS = (None, "mxfp4")
+
+
+class _Auto:
+    """the default of `expert_format`: the environment's SAMD_EXPERT_FORMAT, else what the weights carry.  A sentinel, so that an explicit
+    expert_format=None (experts in the model dtype, an error against 4-bit expert tensors) can be told from no argument"""
+
+    def __repr__(self):
+        return "AUTO"
+
+
+AUTO = _Auto()
 
 
 def sparse_layer_map(n_layers, n_experts, mlp_only_layers, decoder_sparse_step):
@@ -41,6 +67,103 @@ def reject_unsupported(weight_format=None, native_gemm=True, draft_head=False):
         raise SamdError("mixture-of-experts layers exist only in the streaming kernels' packed form: native_gemm=False is not available")
     if draft_head:
         raise SamdError("mixture-of-experts layers are not supported on an EAGLE draft head")
+
+
+def resolve_expert_format(expert_format, carries_4bit, has_sparse):
+    """None or "mxfp4" from the argument (AUTO: env SAMD_EXPERT_FORMAT, for callers that cannot pass one) and from what the weights carry:
+    4-bit expert tensors make the runner "mxfp4" by themselves.  Raises before any device work."""
+    explicit = expert_format is not AUTO
+    if not explicit:
+        expert_format = os.environ.get("SAMD_EXPERT_FORMAT") or None
+    if expert_format not in EXPERT_FORMATS:
+        raise SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS)}")
+    if expert_format is not None and not has_sparse:
+        raise SamdError(f"expert_format '{expert_format}' on a model without mixture-of-experts (sparse) layers: it covers the experts only; "
+                        "weight_format covers the dense projections")
+    if carries_4bit:
+        if explicit and expert_format is None:
+            raise SamdError("the sparse layers carry 4-bit (MXFP4) expert tensors; expert_format=None would need them dequantised "
+                            "(leave it out or pass 'mxfp4')")
+        return "mxfp4"
+    return expert_format
+
+
+def is_4bit(t):
+    return t is not None and (t.dtype == torch.uint8 or MX.is_fp4_dtype(t.dtype))
+
+
+def gate_up_tile_order(moe_inter, device=None):
+    """source row of every packed gate|up row: packed row 128 t + r is gate row 64 t + r for r < 64 and up row I + 64 t + r - 64 otherwise,
+    so that a 128-column tile holds 64 gate columns and the 64 up columns they meet (k_moe_pack's interleave)"""
+    p = torch.arange(2 * moe_inter, device=device)
+    t, r = p // 128, p % 128
+    return torch.where(r < 64, 64 * t + r, moe_inter + 64 * t + r - 64)
+
+
+def check_quantised_experts(q_gu, e8_gu, q_down, e8_down, dtype, name="experts"):
+    """the shapes, dtypes and block-scale codes of 4-bit expert tensors; raises SamdError by tensor name.  Plain torch, any device."""
+    for what, q, e8 in ((f"{name}.gate_up_proj", q_gu, e8_gu), (f"{name}.down_proj", q_down, e8_down)):
+        if e8 is None:
+            raise SamdError(f"{what}: 4-bit expert tensor without its block scales ({what}_scale)")
+        if not is_4bit(q) or q.dim() != 3:
+            raise SamdError(f"{what}: expected uint8 / float4_e2m1fn_x2 [E, N, K/2], got {q.dtype} {tuple(q.shape)}")
+        if not (e8.dtype == torch.uint8 or (MX._E8 is not None and e8.dtype == MX._E8)):
+            raise SamdError(f"{what}_scale of dtype {e8.dtype}; MXFP4 block scales are e8m0 (float8_e8m0fnu or uint8)")
+        E, N, Kh = q.shape
+        if (2 * Kh) % MX.BLOCK != 0 or tuple(e8.shape) != (E, N, 2 * Kh // MX.BLOCK):
+            raise SamdError(f"{what}_scale of shape {tuple(e8.shape)} for [{E}, {N}, {2 * Kh}] experts; MXFP4 has one scale per 32 elements "
+                            f"along K: [{E}, {N}, {2 * Kh // MX.BLOCK}]")
+        MX.check_exponents(e8, dtype, f"{what}_scale")
+    E, N2, Hh = q_gu.shape
+    if tuple(q_down.shape) != (E, 2 * Hh, N2 // 4):
+        raise SamdError(f"{name}: 4-bit expert tensors of shapes {tuple(q_gu.shape)} and {tuple(q_down.shape)} do not belong together "
+                        f"(gate_up_proj [E, 2 I, H/2], down_proj [E, H, I/2])")
+
+
+def quantize_experts(gate_up, down, dtype, name="experts"):
+    """(q_gu [E, 2 I, H/2], e8_gu [E, 2 I, H/32], q_down [E, H, I/2], e8_down [E, H, I/32]), all uint8, of HF's fused expert tensors
+    [E, 2 I, H] / [E, H, I]: mxfp4.quantize_blocks on every row (round to nearest, no calibration: for benches and tests), the exponents
+    clamped to and checked against the range in which fp4 * 2^e is exact in `dtype`."""
+    E, N2, H = gate_up.shape
+    if tuple(down.shape) != (E, H, N2 // 2):
+        raise SamdError(f"{name}: expert tensors of shapes {tuple(gate_up.shape)} and {tuple(down.shape)} do not belong together")
+    out = []
+    for what, t in (("gate_up_proj", gate_up), ("down_proj", down)):
+        _, N, K = t.shape
+        q = torch.empty((E, N, K // 2), dtype=torch.uint8, device=t.device)
+        e8 = torch.empty((E, N, K // MX.BLOCK), dtype=torch.uint8, device=t.device)
+        for e in range(E):                                       # (expert by expert: the fp32 temporaries stay small)
+            q[e], e8[e] = MX.quantize_blocks(t[e], dtype)
+        MX.check_exponents(e8, dtype, f"{name}.{what}")
+        out += [q, e8]
+    return tuple(out)
+
+
+def dequantize_experts(q, e8, dtype=None):
+    """fp4(q) * 2^(e8 - 127), [E, N, K] in fp32 (or `dtype`, exact over mxfp4.EXPONENT_RANGE): the weights the 4-bit expert kernels multiply by"""
+    qb, eb = MX._bytes(q), MX._bytes(e8)
+    E, N, Kh = qb.shape
+    w = MX.dequantize_blocks(qb.reshape(E * N, Kh), eb.reshape(E * N, -1)).reshape(E, N, 2 * Kh)
+    return w if dtype is None else w.to(dtype)
+
+
+def pack_experts_mxfp4(q_gu, e8_gu, q_down, e8_down):
+    """(packed gate|up, packed down): uint8 buffers of E * N * K / 2 + E * N * K / 32 bytes each in samd_gemm_pack_f4's layout, the experts
+    end to end as one matrix of E * N rows (tile e * N / 128 + t is expert e's tile t).  The gate|up rows are permuted first
+    (gate_up_tile_order; MX blocks run along k, so whole blocks move).  Tensors already on the GPU."""
+    E, N2, Hh = q_gu.shape
+    I, H = N2 // 2, 2 * Hh
+    if tuple(q_down.shape) != (E, H, I // 2) or tuple(e8_gu.shape) != (E, N2, H // MX.BLOCK) or tuple(e8_down.shape) != (E, H, I // MX.BLOCK):
+        raise SamdError(f"4-bit expert tensors of shapes {tuple(q_gu.shape)}, {tuple(e8_gu.shape)}, {tuple(q_down.shape)}, {tuple(e8_down.shape)} "
+                        "do not belong together")
+    order = gate_up_tile_order(I, q_gu.device)
+    out = []
+    for q, e8, N, K in ((MX._bytes(q_gu)[:, order], MX._bytes(e8_gu)[:, order], N2, H), (MX._bytes(q_down), MX._bytes(e8_down), H, I)):
+        q, e8 = q.contiguous(), e8.contiguous()
+        buf = torch.empty(E * MX.packed_bytes(N, K), dtype=torch.uint8, device=q.device)
+        check(lib().samd_gemm_pack_f4(_ptr(q), _ptr(e8), _ptr(buf), E * N, K, current_stream()))
+        out.append(buf)
+    return tuple(out)
 
 
 def pack_experts(gate_up, down):
@@ -75,8 +198,23 @@ class MoeBuffers:
         """the routing lists from self.topk_idx as it stands (routing decided elsewhere)"""
         check(lib().samd_moe_lists(_ptr(self.topk_idx), _ptr(d_n), self.rows_pad, self.n_experts, self.top_k, _ptr(self.ws), current_stream()))
 
-    def experts(self, h, wgu_packed, wdown_packed, d_n):
+    def experts(self, h, wgu_packed, wdown_packed, d_n, expert_format=None):
+        """the two expert launches over buffers of pack_experts (expert_format None) or pack_experts_mxfp4 ("mxfp4")"""
         L, st = lib(), current_stream()
+        if expert_format not in EXPERT_FORMATS:
+            raise SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS)}")
+        if expert_format == "mxfp4":
+            for t, want in ((wgu_packed, self.n_experts * MX.packed_bytes(2 * self.moe_inter, self.hidden)),
+                            (wdown_packed, self.n_experts * MX.packed_bytes(self.hidden, self.moe_inter))):
+                if t.dtype != torch.uint8 or t.numel() != want:
+                    raise SamdError(f"MXFP4 expert buffer of {t.numel()} {t.dtype} elements; pack_experts_mxfp4 gives {want} bytes for this shape")
+            check(L.samd_moe_gate_up_silu_f4(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts,
+                                             self.top_k, _ptr(self.act), self.dt, st))
+            check(L.samd_moe_down_combine_f4(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws),
+                                             self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k, _ptr(self.out), self.dt, st))
+            return self.out
+        if wgu_packed.dtype == torch.uint8 or wdown_packed.dtype == torch.uint8:
+            raise SamdError("uint8 expert buffers are MXFP4 ones: pass expert_format='mxfp4'")
         check(L.samd_moe_gate_up_silu(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k,
                                       _ptr(self.act), self.dt, st))
         check(L.samd_moe_down_combine(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws),

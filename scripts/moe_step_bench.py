@@ -8,9 +8,15 @@ random-init weights, per row bucket 1 / 8 / 16 / 64.
   step     graph-replay time of one verify forward per bucket for a --depth layer Qwen3-30B-A3B stack, and its ratio to the 1-row
            (autoregressive) step.
 
+  formats  (--expert-format mxfp4, step "experts") the MXFP4 expert launches against the model-dtype ones of the same build on the same routing:
+           gate|up + SiLU, down + combine and the whole three-call layer, each captured once over --layers weight sets and replayed ALTERNATELY
+           (model dtype, mxfp4, model dtype, ...), every single replay between two hipEvents after a warm-up; median, 10th / 90th percentile and
+           the achieved weight rate (bytes of the experts touched over the median of the two expert launches).  With --step step the forward is
+           built with expert_format="mxfp4".
+
 Without --step every step runs as a child process of its own under its own time limit, and nothing more is started after a step that failed.
 --buckets 1 keeps a profiler's per-kernel statistics to one bucket: rocprofv3 --kernel-trace --stats -- python scripts/moe_step_bench.py --step experts --buckets 1
-usage: python scripts/moe_step_bench.py [--step experts|step] [--reps 30] [--layers 4] [--depth 12] [--buckets 1,8,16,64]"""
+usage: python scripts/moe_step_bench.py [--step experts|step] [--reps 30] [--layers 4] [--depth 12] [--buckets 1,8,16,64] [--expert-format none|mxfp4]"""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "sam-decoding_amd")]
@@ -98,11 +104,91 @@ def step_experts(a):
         torch.cuda.empty_cache()
 
 
+def step_formats(a):
+    import torch
+    import samd_hip
+    from samd_hip import moe as MOE, _ptr, check, current_stream, lib
+    H, I, E, k = A3B["hidden_size"], A3B["moe_intermediate_size"], A3B["num_experts"], A3B["num_experts_per_tok"]
+    dt, L, BF = torch.bfloat16, lib(), samd_hip.BF16
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *s: (torch.randn(s, generator=g, device="cuda") * 0.02).to(dt)
+    sets = []
+    for _ in range(a.layers):
+        router, gu, dn = rnd(E, H) * 50, rnd(E, 2 * I, H), rnd(E, H, I)
+        sets.append((router, MOE.pack_experts(gu, dn), MOE.pack_experts_mxfp4(*MOE.quantize_experts(gu, dn, dt))))
+        del gu, dn
+    per_expert = {"model": 3 * H * I * 2, "mxfp4": 3 * H * I // 2 + 3 * H * I // 32}
+
+    def graph(fn):
+        fn(); torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            fn()
+        for _ in range(3):                                       # warm-up replays
+            gr.replay()
+        torch.cuda.synchronize()
+        return gr
+
+    def alternate(graphs, reps):
+        """single replays of the graphs in turn, each between two events -> {name: sorted us per layer}"""
+        ev = {name: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)] for name in graphs}
+        for r in range(reps):
+            for name, gr in graphs.items():
+                ev[name][r][0].record(); gr.replay(); ev[name][r][1].record()
+        torch.cuda.synchronize()
+        return {name: sorted(e0.elapsed_time(e1) * 1e3 / a.layers for e0, e1 in ev[name]) for name in graphs}
+
+    for n in a.buckets:
+        RP = max(16, n)
+        h = torch.randn((RP, H), generator=g, device="cuda").to(dt)
+        d_n = torch.tensor([n], dtype=torch.int32, device="cuda")
+        bufs = [MOE.MoeBuffers(RP, H, I, E, k, dt, BF, "cuda") for _ in sets]
+        for (router, _, _), b in zip(sets, bufs):
+            b.route(h, router, d_n, True)
+        torch.cuda.synchronize()
+        active = [b.routing_state()[0] for b in bufs]
+        act_mean = sum(active) / len(active)
+        st = current_stream
+
+        def gate_up(fmt):
+            f = L.samd_moe_gate_up_silu_f4 if fmt == "mxfp4" else L.samd_moe_gate_up_silu
+            for (_, pm, p4), b in zip(sets, bufs):
+                check(f(_ptr(h), _ptr((p4 if fmt == "mxfp4" else pm)[0]), _ptr(b.ws), RP, H, I, E, k, _ptr(b.act), BF, st()))
+
+        def down(fmt):
+            f = L.samd_moe_down_combine_f4 if fmt == "mxfp4" else L.samd_moe_down_combine
+            for (_, pm, p4), b in zip(sets, bufs):
+                check(f(_ptr(b.act), _ptr((p4 if fmt == "mxfp4" else pm)[1]), _ptr(b.topk_idx), _ptr(b.topk_w), _ptr(d_n), _ptr(b.ws), RP, H, I, E, k,
+                        _ptr(b.out), BF, st()))
+
+        def layer(fmt):
+            for (router, pm, p4), b in zip(sets, bufs):
+                b.route(h, router, d_n, True)
+                b.experts(h, *(p4 if fmt == "mxfp4" else pm), d_n, expert_format="mxfp4" if fmt == "mxfp4" else None)
+        out = dict(step="formats", rows=n, bucket=RP, experts_touched=active, reps=a.reps, layers=a.layers)
+        med = {}
+        for what, fn in (("gate_up", gate_up), ("down_combine", down), ("layer", layer)):
+            times = alternate({fmt: graph(lambda fmt=fmt: fn(fmt)) for fmt in ("model", "mxfp4")}, a.reps)
+            for fmt, t in times.items():
+                med[what, fmt] = t[len(t) // 2]
+                out[f"{what}_{fmt}_us"] = dict(median=round(t[len(t) // 2], 2), p10=round(t[len(t) // 10], 2), p90=round(t[(9 * len(t)) // 10], 2),
+                                               min=round(t[0], 2), max=round(t[-1], 2))
+            out[f"{what}_mxfp4_over_model"] = round(med[what, "mxfp4"] / med[what, "model"], 3)
+        for fmt in ("model", "mxfp4"):
+            nbytes = act_mean * per_expert[fmt]
+            out[f"{fmt}_mbytes"] = round(nbytes / 1e6, 2)
+            out[f"{fmt}_weight_tb_s"] = round(nbytes / (med["gate_up", fmt] + med["down_combine", fmt]) / 1e6, 3)
+        print(json.dumps(out), flush=True)
+        del bufs
+        torch.cuda.empty_cache()
+
+
 def step_forward(a):
     import torch
     import samd_hip
     from samd_hip.llama import LlamaRunner
-    runner = LlamaRunner.random_init(dict(A3B, num_hidden_layers=a.depth), 2048, torch.bfloat16, seed=0)
+    runner = LlamaRunner.random_init(dict(A3B, num_hidden_layers=a.depth), 2048, torch.bfloat16, seed=0,
+                                     expert_format="mxfp4" if a.expert_format == "mxfp4" else None)
     sess = samd_hip.Session(4096)
     sess.reset()
     res, touched = {}, {}
@@ -117,7 +203,7 @@ def step_forward(a):
         touched[n] = round(sum(len(set(e[2][:e[1]].flatten().tolist())) for e in runner.route_log) / max(len(runner.route_log), 1), 1)
         runner.route_log = None
         res[n] = round(replay_us(lambda: runner.verify(sess, R), a.reps) / 1e3, 4)
-    print(json.dumps(dict(step="step", depth=a.depth, step_ms=res, experts_touched_per_layer=touched,
+    print(json.dumps(dict(step="step", depth=a.depth, expert_format=runner.expert_format, step_ms=res, experts_touched_per_layer=touched,
                           ratio_to_1_row={n: round(res[n] / res[1], 3) for n in a.buckets if 1 in res})), flush=True)
 
 
@@ -128,15 +214,16 @@ def main():
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--buckets", default=",".join(map(str, BUCKETS)), help="row counts, comma separated")
+    ap.add_argument("--expert-format", default="none", choices=("none", "mxfp4"), help="mxfp4: the MXFP4 expert kernels against the model-dtype ones")
     a = ap.parse_args()
     a.buckets = tuple(int(b) for b in a.buckets.split(","))
     if a.step == "experts":
-        return step_experts(a)
+        return step_formats(a) if a.expert_format == "mxfp4" else step_experts(a)
     if a.step == "step":
         return step_forward(a)
     for name, limit in STEP_LIMITS.items():        # a fresh process per step, each under its own limit; a failure ends the run
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(a.reps), "--layers", str(a.layers),
-               "--depth", str(a.depth), "--buckets", ",".join(map(str, a.buckets))]
+               "--depth", str(a.depth), "--buckets", ",".join(map(str, a.buckets)), "--expert-format", a.expert_format]
         rc = subprocess.run(cmd).returncode
         if rc != 0:
             raise SystemExit(f"step {name} ended with status {rc}; nothing more is started")
