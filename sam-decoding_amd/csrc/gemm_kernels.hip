@@ -1634,6 +1634,264 @@ int samd_gemm_skinny_f4(const void *d_A, const void *d_W4p, int32_t rows_pad, in
 }  // extern "C"
 
 // ================================================================================================
+// INT4 (AWQ / GPTQ: unsigned 4-bit codes, one scale and one 4-bit zero point per 128 elements along k) weight-only projection:
+// out[m][n] = sum_k A[m][k] * W[n][k], W[n][k] = rne_dtype((q[n][k] - z[n][k/128]) * s[n][k/128]), A and s in the model dtype
+// (samd_hip/int4.py has the numeric contract).  Grid, A staging by LDS-DMA, A-side swizzle, counted waits, in-out load destinations and
+// MFMA sequence are k_gemm_skinny_f4's; the weight block and the widening differ: integer arithmetic with a zero point and a scale that
+// is no power of two, which v_cvt_scalef32_pk_*_fp4 cannot do.
+//   PACKED LAYOUT (samd_gemm_pack_i4): block (tile t = 128 columns, chunk c = 256 k) is 17 KiB contiguous at (t * K/256 + c) * 17408 bytes:
+//   16 KiB of elements, then 1 KiB of group data.  Element unit j * 512 + tid (16 bytes, j = 0, 1) holds the 32 codes
+//   q[128 t + 16 w + n][256 c + 128 j + 32 g .. +31] for tid = 64 w + 16 g + n: all inside ONE 128-group, 2 c + j.  dword i of a unit
+//   holds the codes k + 8 i .. + 7 (the 8-element MFMA operand, so the A-side reads unit (16 j + 4 g + i) ^ n of row n, as f4 does) with
+//   the nibbles permuted: nibble p (bits 4p .. 4p + 3) is element 2 (p & 3) + (p >> 2), so that (x >> 4 i) & 0x000f000f is the k pair
+//   (2 i, 2 i + 1) of the operand as two 16-bit lanes.  Group data: the 8 bytes at 16384 + 8 (16 w + n) are, as four 16-bit words,
+//   s[row][2 c], s[row][2 c + 1], zb[row][2 c], zb[row][2 c + 1] -- s the scale's bits in the model dtype, zb the zero point pre-biased
+//   as the dtype's bits of 1024 + z (fp16: 0x6400 | z) or 128 + z (bf16: 0x4300 | z).  A lane fetches them in one 8-byte nt load per chunk
+//   (the four g lanes of a row read the same 8 bytes): 3 + XV memory operations per chunk, as f4.
+// WIDENING, one rounding: fp16: 0x6400 | q is 1024 + q; v_pk_add_f16 by -(1024 + z) is exact (integers below 2048), v_pk_mul_f16 by s rounds
+// once (fp16 denormals on).  bf16: (q << 16) | 0x43000000 is the fp32 128 + q; subtract the fp32 128 + z (exact), multiply by float(s)
+// (exact in fp32: 5 x 8 significant bits), v_cvt_pk_bf16_f32 rounds once -- gfx950 has no packed bf16 arithmetic; this is the only new
+// inline assembly besides the 8-byte sibling of the nt loads.  The conversion sits behind the counted wait, as f4's.
+// DEPTH: k_gemm_skinny_f4's table (16 rows 8, 32 rows 4, 48 rows 5, 64 rows 3): the group data costs one more VGPR per chunk in flight than
+// f4's scales, and no instantiation spills (tests/test_int4_codeobject_cpu.py reads it from the code object's metadata).
+// ================================================================================================
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+
+template <typename TT> struct I4Widen;
+template <> struct I4Widen<GF16> {
+    struct G { half2v s, zb; };
+    static __device__ __forceinline__ G group(u32x2 gd, int j) {
+        const unsigned s = (gd[0] >> (16 * j)) & 0xffffu, z = (gd[1] >> (16 * j)) & 0xffffu;
+        return {__builtin_bit_cast(half2v, s | (s << 16)), __builtin_bit_cast(half2v, z | (z << 16))};
+    }
+    static __device__ __forceinline__ half8 cvt(unsigned x, G g) {
+        u32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const half2v q = __builtin_bit_cast(half2v, ((x >> (4 * i)) & 0x000f000fu) | 0x64006400u);      // (1024 + q_2i, 1024 + q_2i+1)
+            r[i] = __builtin_bit_cast(unsigned, (q - g.zb) * g.s);
+        }
+        return __builtin_bit_cast(half8, r);
+    }
+};
+template <> struct I4Widen<GBF16> {
+    struct G { float s, zb; };
+    static __device__ __forceinline__ G group(u32x2 gd, int j) {
+        return {__builtin_bit_cast(float, (gd[0] >> (16 * j)) << 16), __builtin_bit_cast(float, (gd[1] >> (16 * j)) << 16)};
+    }
+    static __device__ __forceinline__ bf16x8 cvt(unsigned x, G g) {
+        u32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const unsigned t = x >> (4 * i);
+            const float lo = __builtin_bit_cast(float, ((t << 16) & 0x000f0000u) | 0x43000000u);           // 128 + q_2i
+            const float hi = __builtin_bit_cast(float, (t & 0x000f0000u) | 0x43000000u);                   // 128 + q_2i+1
+            const float a = (lo - g.zb) * g.s, b = (hi - g.zb) * g.s;
+            unsigned p;
+            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p) : "v"(a), "v"(b));
+            r[i] = p;
+        }
+        return __builtin_bit_cast(bf16x8, r);
+    }
+};
+
+template <typename TT, int RT, int DEPTH>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4,
+                                                                     float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
+                                                                     int n_chunks, int n_splits) {
+    typedef typename TT::elem E;
+    constexpr int R = 16 * RT;
+    constexpr int NT = 64 * GEMM_WAVES;
+    constexpr int XV = (R * 32) / NT;              // 16-byte units per thread to stage one A chunk (as k_gemm_skinny)
+    constexpr int NB = DEPTH + 1;
+    constexpr int PC = 3 + XV;                     // memory operations per thread and chunk: 2 element loads + 1 group-data load + the A staging
+    constexpr size_t WCH = 17408, WU = 8192, WS = 16384;   // bytes of one (tile, chunk) block; of one j row inside it; offset of its group data
+    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
+    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
+
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
+    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    const int split = blockIdx.y;
+    const int c0 = (int)((long long)split * n_chunks / n_splits), c1 = (int)((long long)(split + 1) * n_chunks / n_splits);
+    const char *wtile = reinterpret_cast<const char *>(W4) + (size_t)blockIdx.x * n_chunks * WCH;
+    const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)(16 * w + n) * 8;
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
+
+    floatx4 acc[RT];
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+
+    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
+    u32x4 wr[DEPTH][2];
+    u32x2 ws[DEPTH];                               // the chunk's group data of this lane's row: {s0 | s1 << 16, zb0 | zb1 << 16}
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(ws[d]));
+    auto load_wj = [&](u32x4 (&dst)[2], int c, int j) {
+        const char *p = wtile + (size_t)c * WCH;
+        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[j]) : "v"(wlane), "s"(p + WU * j) : "memory");
+    };
+    auto load_s = [&](u32x2 &dst, int c) {
+        const char *p = wtile + (size_t)c * WCH + WS;
+        asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
+    };
+    auto stage_xi = [&](int c, int buf, int i) {
+        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
+        const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
+        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        asm volatile("" ::: "memory");
+    };
+    auto load_w = [&](u32x4 (&dst)[2], u32x2 &sdst, int c) {
+        load_wj(dst, c, 0); load_wj(dst, c, 1); load_s(sdst, c);
+    };
+    auto stage_x = [&](int c, int buf) {
+#pragma unroll
+        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
+    };
+    auto phase = [&](u32x4 (&cur)[2], u32x2 &cs, int c, int buf) {
+        gemm_wait_younger_deep<DEPTH, PC>(c1 - 1 - c);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
+        // the widening is ordinary VALU code on the loaded registers: re-define them here, behind the counted wait (volatile asm keeps its
+        // order), so that no conversion can be scheduled above the wait while the load is still in flight
+        asm volatile("" : "+v"(cs) : : "memory");
+        const u32x2 gd = cs;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            asm volatile("" : "+v"(cur[j]) : : "memory");
+            const auto grp = I4Widen<TT>::group(gd, j);
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int u = 16 * j + 4 * g + 2 * h;
+                const uint32_t a0 = xbase + (uint32_t)(u ^ n) * 16, a1 = xbase + (uint32_t)((u + 1) ^ n) * 16;
+                u32x4 r[RT][2];
+                gemm_f4_read_a<RT>(r, a0, a1);
+                const auto lo = I4Widen<TT>::cvt(cur[j][2 * h], grp), hi = I4Widen<TT>::cvt(cur[j][2 * h + 1], grp);
+#pragma unroll
+                for (int mt = 0; mt < RT; mt++) {
+                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
+                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, acc[mt]);
+                }
+            }
+            if (RT >= 3 && c + DEPTH < c1) {       // 48 / 64 rows: refill per unit (see k_gemm_skinny)
+                load_wj(cur, c + DEPTH, j);
+                if (j == 1) load_s(cs, c + DEPTH);
+#pragma unroll
+                for (int i = 2 * j; i < 2 * j + 2; i++)
+                    if (i < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, i);
+            }
+        }
+        if (RT < 3 && c + DEPTH < c1) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
+    };
+    if (c0 < c1) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++)
+            if (c0 + d < c1) { load_w(wr[d], ws[d], c0 + d); stage_x(c0 + d, d); }
+        int buf = 0;
+        for (int c = c0; c < c1; c += DEPTH) {
+#pragma unroll
+            for (int d = 0; d < DEPTH; d++)
+                if (c + d < c1) { phase(wr[d], ws[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+        }
+    }
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n; scale and zero point went in with the widening, so ONE rounding and nothing else
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int m = 16 * mt + 4 * g + r;
+            const float v = acc[mt][r];
+            if (out) out[(size_t)m * N + n0 + n] = (E)v;
+            else __hip_atomic_store(&partial[((size_t)split * R + m) * N + n0 + n], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// row-major q [N][K/2] bytes, z [N][K/128] bytes, s [N][K/128] 16-bit words -> the packed blocks of k_gemm_skinny_i4; one thread moves one
+// 16-byte unit (nibbles permuted inside each dword), the g == 0 thread of a row also its half of the row's group data
+__global__ __launch_bounds__(256) void k_gemm_pack_i4(const uint4 *__restrict__ q, const unsigned char *__restrict__ z, const unsigned short *__restrict__ s,
+                                                      unsigned char *__restrict__ out, int N, int K, unsigned zbias) {
+    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;          // element unit: 32 codes of one row
+    const long long total = (long long)N * K / 32;
+    if (u >= total) return;
+    const int n_chunks = K / GEMM_KC;
+    const long long blk = u >> 10;                                          // 1024 element units per block
+    const int in = (int)(u & 1023), j = in >> 9, tid = in & 511, w = tid >> 6, g = (tid >> 4) & 3, n = tid & 15;
+    const int t = (int)(blk / n_chunks), c = (int)(blk % n_chunks);
+    const long long row = 128LL * t + 16 * w + n, ub = 8LL * c + 4 * j + g;       // weight row; its 32-code unit along k
+    unsigned char *dst = out + blk * 17408;
+    const uint4 v = q[row * (K / 32) + ub];
+    const unsigned src[4] = {v.x, v.y, v.z, v.w};
+    unsigned d[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        unsigned o = 0;
+#pragma unroll
+        for (int p = 0; p < 8; p++) o |= ((src[i] >> (4 * (2 * (p & 3) + (p >> 2)))) & 15u) << (4 * p);
+        d[i] = o;
+    }
+    reinterpret_cast<uint4 *>(dst)[in] = make_uint4(d[0], d[1], d[2], d[3]);
+    if (g == 0) {
+        const long long grp = row * (K / 128) + 2 * c + j;
+        unsigned short *gdst = reinterpret_cast<unsigned short *>(dst + 16384 + 8 * (16 * w + n));
+        gdst[j] = s[grp];
+        gdst[2 + j] = (unsigned short)(zbias | (z[grp] & 15u));
+    }
+}
+
+template <typename TT, int RT, int DEPTH>
+static hipError_t gemm_i4_launch(dim3 grid, hipStream_t st, const void *A, const void *W4, float *partial, void *out, int K, int N, int splits) {
+    constexpr int lds = (DEPTH + 1) * 16 * RT * GEMM_KC * 2;
+    if constexpr (lds > 65536) {
+        static unsigned long long done = 0ull;                     // per-device (samd_common.h)
+        const hipError_t attr = samd_reserve_lds((const void *)k_gemm_skinny_i4<TT, RT, DEPTH>, lds, &done);
+        if (attr != hipSuccess) return attr;
+    }
+    hipLaunchKernelGGL((k_gemm_skinny_i4<TT, RT, DEPTH>), grid, dim3(64 * GEMM_WAVES), lds, st, (const typename TT::elem *)A, (const unsigned char *)W4,
+                       partial, (typename TT::elem *)out, K, N, K / GEMM_KC, splits);
+    return hipSuccess;
+}
+
+extern "C" {
+
+int samd_gemm_pack_i4(const void *d_q, const void *d_z, const void *d_s, void *d_out, int32_t N, int32_t K, int32_t dtype, void *stream) {
+    if (!d_q || !d_z || !d_s || !d_out || d_q == d_out || d_z == d_out || d_s == d_out || N < GEMM_COLS || N % GEMM_COLS != 0 || K < GEMM_KC ||
+        K % GEMM_KC != 0 || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("samd_gemm_pack_i4: needs N %% 128 == 0, K %% 256 == 0, dtype fp16 or bf16 and distinct buffers"); return SAMD_E_INVALID;
+    }
+    const long long units = (long long)N * K / 32;
+    hipLaunchKernelGGL(k_gemm_pack_i4, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)d_q,
+                       (const unsigned char *)d_z, (const unsigned short *)d_s, (unsigned char *)d_out, N, K, dtype == SAMD_F16 ? 0x6400u : 0x4300u);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_gemm_skinny_i4(const void *d_A, const void *d_W4p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
+                        int32_t dtype, void *stream) {
+    if (!d_A || !d_W4p || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS || N % GEMM_COLS != 0 ||
+        K < GEMM_KC || K % GEMM_KC != 0 || splits < 1 || splits > K / GEMM_KC || (splits == 1 ? !d_out : !d_partial) || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("samd_gemm_skinny_i4: unsupported shape (rows 16/32/48/64, N %% 128 == 0, K %% 256 == 0) or null pointer"); return SAMD_E_INVALID;
+    }
+    const dim3 grid(N / GEMM_COLS, splits);
+    const hipStream_t st = (hipStream_t)stream;
+    float *part = splits == 1 ? nullptr : d_partial;
+    void *out = splits == 1 ? d_out : nullptr;
+#define GO(TT, RT, D) e = gemm_i4_launch<TT, RT, D>(grid, st, d_A, d_W4p, part, out, K, N, splits)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1, 8); else if (rows_pad == 32) GO(TT, 2, 4); else if (rows_pad == 48) GO(TT, 3, 5); else GO(TT, 4, 3); } while (0)
+    hipError_t e;
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
+    if (e != hipSuccess) { samd_set_error("samd_gemm_skinny_i4: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================
 // Mixture-of-experts MLP (Qwen3-MoE: HF Qwen3MoeSparseMoeBlock): router, gathered expert gate|up + SiLU, gathered expert down + combine.
 // A sparse layer streams a data-dependent subset of E small matrices, each for its own subset of rows; the choice is made on the device
 // and every launch has a fixed grid, so a decode step stays one hipGraph replay.

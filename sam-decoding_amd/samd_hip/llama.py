@@ -19,6 +19,7 @@ from . import (F16, BF16, MAX_DRAFT, TILE_ROWS, QkvEpilogue, SamdError, Session,
                torch_dtype_code)
 from . import fp8 as F8
 from . import mxfp4 as MX
+from . import int4 as I4
 from . import moe as MOE
 
 
@@ -28,23 +29,29 @@ def _env_weight_format(weight_format):
 
 
 def _weight_format(weight_format, weights, dtype):
-    """"fp8", "mxfp4" or None (the model dtype).  Projections that arrive as float8_e4m3fn (an FP8 checkpoint) or as packed e2m1 bytes (an
-    MXFP4 checkpoint: uint8 / float4_e2m1fn_x2 [N, K/2]) make the runner FP8 / MXFP4 by themselves."""
+    """"fp8", "mxfp4", "int4g128" or None (the model dtype; the plain word "int4" stays an unknown format: the name carries the group size).  Projections that arrive as float8_e4m3fn (an FP8 checkpoint), as packed e2m1 bytes
+    (an MXFP4 checkpoint: uint8 / float4_e2m1fn_x2 [N, K/2]) or as 4-bit codes with zero points and group scales (an AWQ / GPTQ checkpoint:
+    uint8 [N, K/2] beside k + "_z" and k + "_s") make the runner FP8 / MXFP4 / INT4 by themselves."""
     has_f8 = any(l[k].dtype == torch.float8_e4m3fn for l in weights["layers"] for k in F8.PROJECTIONS if k in l)
-    has_f4 = any(_is_f4_tensor(l[k]) for l in weights["layers"] for k in MX.PROJECTIONS if k in l)
+    has_i4 = any(k + "_z" in l for l in weights["layers"] for k in I4.PROJECTIONS)
+    has_f4 = any(_is_f4_tensor(l[k]) and k + "_z" not in l for l in weights["layers"] for k in MX.PROJECTIONS if k in l)
     names = {torch.float16: ("fp16", "float16", "half"), torch.bfloat16: ("bf16", "bfloat16")}.get(dtype, ())
     if weight_format is None:
-        fmt = "fp8" if has_f8 else ("mxfp4" if has_f4 else None)
-    elif weight_format in ("fp8", "mxfp4"):
+        fmt = "fp8" if has_f8 else ("mxfp4" if has_f4 else ("int4g128" if has_i4 else None))
+    elif weight_format in ("fp8", "mxfp4", "int4g128"):
         fmt = weight_format
     elif weight_format == dtype or (isinstance(weight_format, str) and weight_format.lower() in names):
         fmt = None
     else:
-        raise SamdError(f"weight_format {weight_format!r}: expected None, 'fp8', 'mxfp4' or the model dtype ({dtype})")
+        hint = " (the AWQ / GPTQ format is spelled 'int4g128': 4-bit codes in groups of 128, the only group size the kernel has)" \
+            if weight_format == "int4" else ""
+        raise SamdError(f"weight_format {weight_format!r}: expected None, 'fp8', 'mxfp4', 'int4g128' or the model dtype ({dtype}){hint}")
     if has_f8 and fmt != "fp8":
         raise SamdError(f"the weights carry float8_e4m3fn projections; weight_format {weight_format!r} would need them dequantised (pass None or 'fp8')")
     if has_f4 and fmt != "mxfp4":
         raise SamdError(f"the weights carry MXFP4 projections; weight_format {weight_format!r} would need them dequantised (pass None or 'mxfp4')")
+    if has_i4 and fmt != "int4g128":
+        raise SamdError(f"the weights carry INT4 (AWQ / GPTQ) projections; weight_format {weight_format!r} would need them dequantised (pass None or 'int4g128')")
     return fmt
 
 
@@ -171,12 +178,16 @@ class LlamaRunner:
         self.weight_format = _weight_format(weight_format, weights, dtype)
         # weight_format "mxfp4": the same four projections as e2m1 elements with one e8m0 scale per 32 along K (samd_hip/mxfp4.py), streamed by
         # samd_gemm_skinny_f4 only; everything FP8 implies for the runner holds here too (quant)
-        f8, f4 = self.weight_format == "fp8", self.weight_format == "mxfp4"
-        quant = f8 or f4
+        # weight_format "int4g128": the same four projections as AWQ / GPTQ 4-bit codes with one scale (model dtype) and one zero point per 128 along
+        # K (samd_hip/int4.py), streamed by samd_gemm_skinny_i4 only; again everything FP8 implies holds
+        f8, f4, i4 = self.weight_format == "fp8", self.weight_format == "mxfp4", self.weight_format == "int4g128"
+        quant = f8 or f4 or i4
         if f8 and not native_gemm:
             raise SamdError("FP8 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'fp8'")
         if f4 and not native_gemm:
             raise SamdError("MXFP4 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'mxfp4'")
+        if i4 and not native_gemm:
+            raise SamdError("INT4 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'int4g128'")
         s = shape
         self.w = weights
         # samd_gemm_skinny streams the weights itself where the shape allows (N % 128 == 0, K % 256 == 0); a projection that
@@ -301,9 +312,33 @@ class LlamaRunner:
             out = torch.empty(MX.packed_bytes(N, K), dtype=torch.uint8, device=self.device)
             check(lib().samd_gemm_pack_f4(_ptr(q), _ptr(e8), _ptr(out), N, K, current_stream()))
             return out
+        def pack_i4(l, k):
+            """projection k in samd_gemm_pack_i4's form (4-bit codes with their group scales and zero points inline): quantised on load per
+            group of 128 (uncalibrated) unless the checkpoint brought its own (q, z, s), whose scales are taken in the model dtype (a bf16
+            runner rounds fp16 scales once) and checked; the model-dtype matrix is dropped as soon as it is packed"""
+            t = l[k]
+            if k + "_z" in l:
+                q, z, sc = I4.fuse_int4([(t, l.pop(k + "_z"), l.pop(k + "_s"))], self.device, dtype)
+            else:
+                if t.shape[0] % 128 != 0 or t.shape[1] % 256 != 0:
+                    raise SamdError(f"INT4 projection {k} of shape {tuple(t.shape)}: the INT4 kernel needs N % 128 == 0 and K % 256 == 0")
+                q, z, sc = I4.quantize_groups(t, dtype)
+            I4.check_groups(q, z, sc, dtype, k)
+            N, K = q.shape[0], 2 * q.shape[1]
+            l[k] = torch.empty((N, K), dtype=torch.uint8, device="meta")
+            del t
+            out = torch.empty(I4.packed_bytes(N, K), dtype=torch.uint8, device=self.device)
+            check(lib().samd_gemm_pack_i4(_ptr(q), _ptr(z), _ptr(sc), _ptr(out), N, K, self.dt, current_stream()))
+            return out
         # packed_lm_head: a draft head shares the base model's lm_head, packed copy included
         layers = []
         for l in weights["layers"]:
+            if i4:
+                lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
+                for k in I4.PROJECTIONS:
+                    lp[k + "_i4"] = pack_i4(l, k)
+                layers.append(lp)
+                continue
             if f4:
                 lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
                 for k in MX.PROJECTIONS:
@@ -429,8 +464,12 @@ class LlamaRunner:
                 for k in MX.PROJECTIONS:
                     rep["packed_" + k + "_f4"] = sum(nbytes(l[k + "_f4"]) * 16 // 17 for l in self.wp["layers"])
                 rep["mxfp4_scales"] = sum(nbytes(l[k + "_f4"]) // 17 for l in self.wp["layers"] for k in MX.PROJECTIONS)
+            if self.weight_format == "int4g128":                     # one buffer per projection: 16 KiB of codes, then their 1 KiB of group data
+                for k in I4.PROJECTIONS:
+                    rep["packed_" + k + "_i4"] = sum(nbytes(l[k + "_i4"]) * 16 // 17 for l in self.wp["layers"])
+                rep["int4_group_data"] = sum(nbytes(l[k + "_i4"]) // 17 for l in self.wp["layers"] for k in I4.PROJECTIONS)
         rep["total"] = sum(rep.values())
-        if self.weight_format in ("fp8", "mxfp4"):
+        if self.weight_format in ("fp8", "mxfp4", "int4g128"):
             rep["weight_format"] = self.weight_format
         rep["expert_format"] = self.expert_format                # None: experts (if any) in the model dtype; packed_moe_* are the bytes held
         return rep
@@ -529,6 +568,10 @@ class LlamaRunner:
         projections already hold float8_e4m3fn weights with a `weight_scale` (per tensor, [N] or [N, 1]) is imported as it is (samd_hip/fp8.py).
         "mxfp4" quantises them per block of 32 (no calibration: for benches and tests); a module whose projections hold float4_e2m1fn_x2 or uint8
         weights [N, K/2] with an e8m0 `weight_scale` [N, K/32] is imported as it is (samd_hip/mxfp4.py).
+        "int4g128" quantises them per group of 128 with a zero point (no calibration: for benches and tests); a module whose projections are AWQ
+        ("GEMM") or GPTQ modules -- int32 `qweight` / `qzeros` and a floating `scales` -- is imported as it is, by the layout its
+        config.quantization_config names, and makes the runner "int4g128" by itself (samd_hip/int4.py: group sizes, zero-point conventions and what
+        raises).  A bf16 runner rounds the checkpoint's fp16 scales once to bf16.
         expert_format (default: env SAMD_EXPERT_FORMAT, unset = the model dtype; models with sparse layers only): "mxfp4" quantises the EXPERTS
         of every sparse layer on load (uncalibrated: for benches and tests); router, attention, dense MLP layers, embedding and lm_head stay in
         the model dtype.  A module whose sparse layers carry 4-bit expert tensors with their block scales (samd_hip/moe.py has the convention)
@@ -539,8 +582,10 @@ class LlamaRunner:
                  ("mlp", "up_proj"), ("mlp", "down_proj"))
         linears = [(f"layers.{i}.{a}.{b}", getattr(getattr(lyr, a), b)) for i, lyr in enumerate(m.layers) for a, b in parts
                    if hasattr(getattr(lyr, a), b)]               # (a sparse layer's MLP has no gate / up / down projections of its own)
-        ckpt_f8 = F8.checkpoint_is_fp8(linears)
-        ckpt_f4 = MX.checkpoint_is_mxfp4(linears)
+        ckpt_i4 = I4.checkpoint_is_int4(linears)                 # AWQ / GPTQ modules (qweight / qzeros / scales, no `weight`)
+        ckpt_f8 = (not ckpt_i4) and F8.checkpoint_is_fp8(linears)
+        ckpt_f4 = (not ckpt_i4) and MX.checkpoint_is_mxfp4(linears)
+        qcfg = I4.quant_config(getattr(lm, "config", None))
         if F8.is_fp8_dtype(lm.lm_head.weight.dtype) or F8.is_fp8_dtype(m.embed_tokens.weight.dtype):
             raise SamdError("FP8 embedding / lm_head weights are not supported: they stay in the model dtype")
         if _is_f4_tensor(lm.lm_head.weight) or _is_f4_tensor(m.embed_tokens.weight):
@@ -553,7 +598,7 @@ class LlamaRunner:
             if sparse != list(shape.sparse):
                 raise SamdError(f"the module's sparse MLP layers {[i for i, x in enumerate(sparse) if x]} are not the ones its config implies "
                                 f"{[i for i, x in enumerate(shape.sparse) if x]} (model_type '{shape.model_type}')")
-            MOE.reject_unsupported("fp8" if ckpt_f8 else ("mxfp4" if ckpt_f4 else weight_format), kw.get("native_gemm", True),
+            MOE.reject_unsupported("int4g128" if ckpt_i4 else "fp8" if ckpt_f8 else ("mxfp4" if ckpt_f4 else weight_format), kw.get("native_gemm", True),
                                    kw.get("draft_head", False))
         # 4-bit experts: decided and checked on the module's own tensors, before anything moves to the device (the runner resolves the
         # format again from the weights it is given)
@@ -600,6 +645,14 @@ class LlamaRunner:
                 extra["bqkv"] = get(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias]))
             if qk_norm:
                 extra["q_norm"], extra["k_norm"] = get(a.q_norm.weight), get(a.k_norm.weight)
+            if ckpt_i4:                                          # canonical (q, z, s) of the AWQ / GPTQ modules; the runner checks and packs them
+                lw = {}
+                for k, names in (("wqkv", ("q_proj", "k_proj", "v_proj")), ("wo", ("o_proj",)), ("wgu", ("gate_proj", "up_proj")), ("wdown", ("down_proj",))):
+                    own = a if k in ("wqkv", "wo") else f
+                    lw[k], lw[k + "_z"], lw[k + "_s"] = I4.fuse_int4(
+                        [I4.linear_int4(getattr(own, x), f"layers.{len(layers)}.{x}", config=qcfg) for x in names], dev, dtype)
+                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
+                continue
             if ckpt_f4:                                          # (q, e8) as the checkpoint has them; the runner checks and packs them
                 lw = {}
                 for k, lins in (("wqkv", (a.q_proj, a.k_proj, a.v_proj)), ("wo", (a.o_proj,)), ("wgu", (f.gate_proj, f.up_proj)), ("wdown", (f.down_proj,))):
@@ -674,6 +727,16 @@ class LlamaRunner:
                     for sc in ("weight_scale", "input_scale")}
             # the block scales of 4-bit expert tensors (samd_hip/moe.py), which the runner reads; beside plain experts they are extra
             params = dict(lyr.named_parameters())
+            # an AWQ / GPTQ projection holds qweight / qzeros / scales (/ g_idx) and maybe a bias, as buffers or parameters, in place of a
+            # `weight`: it counts as that weight, and its bias counts as a bias
+            for n, mod in lyr.named_modules():
+                if n and I4.is_int4_module(mod):
+                    for own in list(params):
+                        if own.startswith(n + "."):
+                            del params[own]
+                    params[n + ".weight"] = None
+                    if getattr(mod, "bias", None) is not None:
+                        params[n + ".bias"] = None
             if any(MOE.is_4bit(params.get(n)) for n in MOE.SPARSE_MLP_PARAMS[1:]):
                 skip |= set(MOE.EXPERT_SCALE_PARAMS)
             return set(params) - skip
@@ -747,16 +810,18 @@ class LlamaRunner:
 
     def weight_bytes(self, experts=None):
         """bytes of weights one decode step streams from HBM (the embedding table is only gathered), tensor by tensor in its own format
-        (an FP8 projection: one byte per weight + its fp32 column scales; an MXFP4 projection: half a byte per weight + one scale byte per 32).
+        (an FP8 projection: one byte per weight + its fp32 column scales; an MXFP4 projection: half a byte per weight + one scale byte per 32; an
+        INT4 projection: half a byte per weight + 4 bytes of scale and zero point per 128).
         A sparse (mixture-of-experts) layer counts `experts` of its experts in the format they are held in (MXFP4 experts: elements + block
         scales; default: num_experts_per_tok, what the 1-row step streams; a wider step streams the experts its rows are routed to, at most
         all of them: pass experts=shape.n_experts for that bound)."""
         n_act = self.shape.top_k if experts is None else int(experts)
         nb = lambda t: t.numel() * t.element_size() if t.dim() != 3 else t[0].numel() * t.element_size() * min(n_act, t.shape[0])
         n = nb(self.w["lm_head"]) + nb(self.w["norm"])
-        if self.weight_format == "mxfp4":
+        if self.weight_format in ("mxfp4", "int4g128"):
+            sfx = "_f4" if self.weight_format == "mxfp4" else "_i4"
             for l, lp in zip(self.w["layers"], self.wp["layers"]):
-                n += sum(nb(t) for k, t in l.items() if k not in MX.PROJECTIONS) + sum(nb(lp[k + "_f4"]) for k in MX.PROJECTIONS)
+                n += sum(nb(t) for k, t in l.items() if k not in MX.PROJECTIONS) + sum(nb(lp[k + sfx]) for k in MX.PROJECTIONS)
             return n
         for l in self.w["layers"]:
             n += sum(nb(t) for t in l.values())
@@ -829,11 +894,15 @@ class LlamaRunner:
             sp = 1 if (fused or is_head) else L.samd_gemm_splits(n, k, RP)
             return C.byref(Warm(wp.data_ptr(), n, k, sp, self.warm_kb, self.warm_delay, self.warm_where))
 
-        def gemm(a, w, wp, out, wg=None, f8=None, f4=None):
+        def gemm(a, w, wp, out, wg=None, f8=None, f4=None, i4=None):
             """out = a @ w.T (wp = w in the packed 128-column-tile layout, wg = w group-major: whichever exists; f8 = (packed e4m3fn, column
-            scales) of an FP8 runner; f4 = the packed elements + block scales of an MXFP4 runner); returns (operand for the consumer,
+            scales) of an FP8 runner; f4 = the packed elements + block scales of an MXFP4 runner; i4 = the packed codes + group data of an INT4 runner); returns (operand for the consumer,
             n_partials, partial_stride)."""
             n, k = w.shape
+            if i4 is not None:                                    # (RP <= 64 here, as for FP8; the INT4 runner's own packed buffer)
+                sp = L.samd_gemm_splits(n, k, RP)
+                check(L.samd_gemm_skinny_i4(_ptr(a), _ptr(i4), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
+                return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
             if f4 is not None:                                    # (RP <= 64 here, as for FP8)
                 sp = L.samd_gemm_splits(n, k, RP)
                 check(L.samd_gemm_skinny_f4(_ptr(a), _ptr(f4), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
@@ -889,7 +958,7 @@ class LlamaRunner:
                     _ptr(b["x"] if raw_in else b["h"]), _ptr(wp["wqkv64"]), RP, s.hidden, _ptr(b["cs"]), _ptr(d_L), _ptr(d_n),
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), s.heads, s.kv_heads, s.head_dim, self.max_len, dt, st))
             else:
-                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], f8=wp.get("wqkv_f8"), f4=wp.get("wqkv_f4"))
+                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], f8=wp.get("wqkv_f8"), f4=wp.get("wqkv_f4"), i4=wp.get("wqkv_i4"))
             if block:
                 # RoPE + K row / V^T column write + tree attention + merge of the tile partials: one launch (csrc/attn_kernels.hip)
                 check(L.samd_attention_block(_ptr(src), n_p, stride, _ptr(b["cs"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R,
@@ -921,7 +990,7 @@ class LlamaRunner:
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R, s.heads,
                     s.kv_heads, s.head_dim, self.max_len, _ptr(d_mask), _ptr(d_L), _ptr(d_n), self.scale,
                     _ptr(b["ws"]), b["ws_bytes"], hint(w["wo"], wp.get("wo")), st))
-            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"), f4=wp.get("wo_f4"))
+            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"), f4=wp.get("wo_f4"), i4=wp.get("wo_i4"))
             check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(src), _ptr(w["ln2"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, n_p, stride,
                                       None, st))           # (no warm-up hint: gate|up is packed group-major, the hint describes 128-column tiles)
             if "moe_gu" in wp:
@@ -936,9 +1005,9 @@ class LlamaRunner:
             if wp.get("wgu") is not None and RP <= self.native_gemm_max_rows:
                 check(L.samd_gemm_pairs_silu(_ptr(b["h"]), _ptr(wp["wgu"]), RP, s.inter, s.hidden, _ptr(b["act"]), dt, st))
             else:
-                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"), f4=wp.get("wgu_f4"))     # wgu is only ever packed for the fused form (or FP8)
+                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"), f4=wp.get("wgu_f4"), i4=wp.get("wgu_i4"))     # wgu is only ever packed for the fused form (or FP8)
                 check(L.samd_silu_mul(_ptr(src), _ptr(b["act"]), R, s.inter, dt, n_p, stride, st))
-            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"), f4=wp.get("wdown_f4"))
+            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"), f4=wp.get("wdown_f4"), i4=wp.get("wdown_i4"))
         check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(delta), _ptr(self.w["norm"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, dn, dstride,
                                   hint(self.w["lm_head"], self.wp["lm_head"] if self.wp else None, is_head=True), st))
         # (for a draft head the call above only folds the last projection into the residual stream; its norm output is unused)
