@@ -127,6 +127,9 @@ def pinned(case, R, E, k, g):
     ("random", 32, 4, 512, 512, 32, 20),
 ])
 def test_expert_gemms_with_pinned_routing(dtype, case, E, k, H, I, RP, n):
+    """the expert launches against HF's own experts at workload statistics (randn inputs): error <= 1.5 x HF's + 0.02 x max|out|.  That bar
+    says how the kernels compare with HF, not that they are exact: what every launch must store, bit for bit, is held by
+    tests/test_gpu_moe_exact.py"""
     gc = torch.Generator().manual_seed(E * k + n)
     g = torch.Generator(device="cuda").manual_seed(E * k + n)
     gate_up = (torch.randn((E, 2 * I, H), generator=g, device="cuda") * 0.05).to(dtype)

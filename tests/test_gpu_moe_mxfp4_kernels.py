@@ -56,6 +56,9 @@ def quantised_experts(E, H, I, g, dtype):
     ("random", 32, 4, 512, 512, 32, 20),
 ])
 def test_4bit_expert_gemms_with_pinned_routing(dtype, case, E, k, H, I, RP, n):
+    """the expert launches against HF's own experts at workload statistics (randn inputs): error <= 1.5 x HF's + 0.02 x max|out|.  That bar
+    says how the kernels compare with HF, not that they are exact: what every launch must store, bit for bit, is held by
+    tests/test_gpu_moe_exact.py"""
     gc = torch.Generator().manual_seed(E * k + n)
     g = torch.Generator(device="cuda").manual_seed(E * k + n)
     p_gu, p_down, w_gu, w_down = quantised_experts(E, H, I, g, dtype)
