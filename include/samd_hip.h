@@ -726,6 +726,21 @@ int samd_moe_gate_up_silu_f4(const void *d_h, const void *d_Wgu4, const void *d_
                              int32_t top_k, void *d_act, int32_t dtype, void *stream);
 int samd_moe_down_combine_f4(const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
                              int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream);
+/* The same two expert launches over INT4 (AWQ / GPTQ) experts: unsigned 4-bit codes with one scale (model dtype) and one 4-bit zero point per
+ * 128 along k.  The numeric contract is samd_hip/int4.py's, as for samd_gemm_skinny_i4: W = rne_dtype((q - z) * s) -- ONE rounding, to the
+ * model dtype -- fp32 accumulation in chunk order, the epilogues' roundings unchanged.  Routing, the workspace, samd_moe_route /
+ * samd_moe_lists and the combine are the calls above; shapes, grids and errors are those of the _f4 calls; both are capturable.
+ *   d_Wgu4 / d_Wdown4      the E experts laid end to end as ONE matrix of E * N rows in samd_gemm_pack_i4's layout (samd_gemm_pack_i4 with
+ *                          N := E * N; N = 2 * moe_inter, K = hidden for gate|up; N = hidden, K = moe_inter for down): E * N * K / 2 +
+ *                          E * N * K / 32 bytes, expert e's tile t being tile e * N / 128 + t.  For gate|up the rows (codes, zero points and
+ *                          scales: groups run along k) are permuted BEFORE packing exactly as for the _f4 call (samd_hip/moe.py:
+ *                          pack_experts_int4).  The buffer is specific to the dtype it was packed for.
+ *   samd_moe_gate_up_silu_i4   as samd_moe_gate_up_silu.
+ *   samd_moe_down_combine_i4   as samd_moe_down_combine: the 4-bit down launch, then the same combine kernel. */
+int samd_moe_gate_up_silu_i4(const void *d_h, const void *d_Wgu4, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
+                             int32_t top_k, void *d_act, int32_t dtype, void *stream);
+int samd_moe_down_combine_i4(const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                             int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream);
 
 /* ---- scripted verifier (tests, smoke and bench only): replaces the LM arg-max of every draft node by
  * the next token of a target stream while the node's context (committed history + root->node path) is a

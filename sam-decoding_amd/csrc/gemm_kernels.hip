@@ -2620,3 +2620,253 @@ int samd_moe_down_combine_f4(const void *d_act, const void *d_Wdown4, const int3
 }
 
 }  // extern "C"
+
+// ================================================================================================
+// Mixture-of-experts MLP with INT4 (AWQ / GPTQ) experts: the gathered expert GEMMs over k_gemm_skinny_i4's 4.25-bit weight stream.
+//   samd_moe_gate_up_silu_i4 / samd_moe_down_combine_i4: the fixed grid (N / 128, min(E, rows_pad * top_k)), the early exit of slots
+//   >= ws[0], the list in static LDS, the gathered LDS-DMA A tile (srow), the A-side unit order (16 j + 4 g + i) ^ n, the counted waits
+//   with in-out load destinations, both epilogues (HF's roundings; rows >= cnt not stored) and k_moe_combine are moe4_expert_gemm's,
+//   statement for statement; the weight side is k_gemm_skinny_i4's: 17 KiB (tile, chunk) blocks, two 16-byte nt element loads and ONE
+//   8-byte nt group-data load per lane and chunk (slane = (16 w + n) * 8: the four g lanes of a row read the same 8 bytes),
+//   I4Widen<TT>::group / cvt behind the counted wait -- W = rne_dtype((q - z) * s), one rounding, fp32 accumulation in chunk order.  No
+//   split-K, no atomics: a row's output has the same bits whatever shares the launch.
+//   A function of its own, not a weight-side policy of moe4_expert_gemm: the MXFP4 expert kernels are left textually alone, so their
+//   gfx950 ISA cannot move.
+//   PACKED LAYOUT: the experts laid end to end are ONE matrix of E * N rows in samd_gemm_pack_i4's layout (the pack call with N := E * N);
+//   expert e's tile t is global tile e * N / 128 + t, at ((e * N / 128 + t) * K / 256 + c) * 17408 bytes for chunk c.  gate|up: the rows
+//   are permuted before packing as for MXFP4 (samd_hip/moe.py: gate_up_tile_order; groups run along k, so whole rows move with their
+//   zero points and scales).  The buffer is dtype-specific (the scales and the pre-biased zero points are in the model dtype).
+//   DEPTH per row tile: Moe4Depth's table (16 rows 8, 32 rows 3, 48 rows 2, 64 rows 3) under the same three constraints -- (DEPTH - 1) *
+//   PC <= 63 (28, 10, 6, 14), (DEPTH + 1) A buffers of R * 512 bytes + the list inside 160 KiB for the intended workgroups per CU (72 KiB
+//   x 2, 64 KiB x 2, 72 KiB x 2, 128 KiB x 1), no spills: the group data costs one VGPR per chunk in flight more than MXFP4's scales (8
+//   more at 16 rows) and every instantiation still compiles without scratch (tests/test_moe_int4_cpu.py reads it from the code object's
+//   metadata).  An expert's stream is often SHORTER than the depth (1 chunk for down at moe_inter 256): the skipped prologue loads leave
+//   their in-out destination registers as they are.  The table is NOT swept on a GPU; profiles/moe_experts_int4.md says what was measured.
+// ================================================================================================
+template <int RT> struct MoeI4Depth { static constexpr int value = RT == 1 ? 8 : RT == 3 ? 2 : 3; };
+
+template <typename TT, int RT, bool GU>
+__device__ __forceinline__ void moe_i4_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
+                                                 typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
+    typedef typename TT::elem E;
+    constexpr int DEPTH = MoeI4Depth<RT>::value;
+    constexpr int R = 16 * RT;
+    constexpr int NT = 64 * GEMM_WAVES;
+    constexpr int XV = (R * 32) / NT;
+    constexpr int NB = DEPTH + 1;
+    constexpr int PC = 3 + XV;                     // memory operations per thread and chunk: 2 element loads + 1 group-data load + the A staging
+    constexpr size_t WCH = 17408, WU = 8192, WS = 16384;   // bytes of one (tile, chunk) block; of one j row inside it; offset of its group data
+    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
+    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
+    __shared__ int lst[MOE_MAX_ROWS];
+
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
+    const int slot_a = blockIdx.y;
+    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts
+    const int expert = ws[MOE_WS_ACTIVE + slot_a];
+    int cnt = ws[MOE_WS_COUNT + slot_a];
+    cnt = cnt > R ? R : cnt;
+    if (tid < MOE_MAX_ROWS) lst[tid] = ws[MOE_WS_LIST + MOE_MAX_ROWS * slot_a + (tid < cnt ? tid : 0)];
+    __syncthreads();
+    // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
+    int srow[XV];
+#pragma unroll
+    for (int i = 0; i < XV; i++) { const int p = lst[(tid >> 5) + 16 * i]; srow[i] = GU ? p / top_k : p; }
+
+    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    const char *wtile = reinterpret_cast<const char *>(W4) + ((size_t)expert * (N / GEMM_COLS) + blockIdx.x) * n_chunks * WCH;
+    const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)(16 * w + n) * 8;
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
+
+    floatx4 acc[RT];
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
+    u32x4 wr[DEPTH][2];
+    u32x2 gdr[DEPTH];                              // the chunk's group data of this lane's row: {s0 | s1 << 16, zb0 | zb1 << 16}
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(gdr[d]));
+    auto load_wj = [&](u32x4 (&dst)[2], int c, int j) {
+        const char *p = wtile + (size_t)c * WCH;
+        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[j]) : "v"(wlane), "s"(p + WU * j) : "memory");
+    };
+    auto load_s = [&](u32x2 &dst, int c) {
+        const char *p = wtile + (size_t)c * WCH + WS;
+        asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
+    };
+    auto stage_xi = [&](int c, int buf, int i) {
+        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
+        const E *src = A + (size_t)srow[i] * K + (size_t)c * GEMM_KC + 8 * unit;
+        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        asm volatile("" ::: "memory");
+    };
+    auto load_w = [&](u32x4 (&dst)[2], u32x2 &sdst, int c) {
+        load_wj(dst, c, 0); load_wj(dst, c, 1); load_s(sdst, c);
+    };
+    auto stage_x = [&](int c, int buf) {
+#pragma unroll
+        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
+    };
+    auto phase = [&](u32x4 (&cur)[2], u32x2 &cs, int c, int buf) {
+        gemm_wait_younger_deep<DEPTH, PC>(n_chunks - 1 - c);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
+        // re-defined behind the counted wait (volatile asm keeps its order): no widening can be scheduled above it (see k_gemm_skinny_i4)
+        asm volatile("" : "+v"(cs) : : "memory");
+        const u32x2 gd = cs;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            asm volatile("" : "+v"(cur[j]) : : "memory");
+            const auto grp = I4Widen<TT>::group(gd, j);
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int u = 16 * j + 4 * g + 2 * h;
+                const uint32_t a0 = xbase + (uint32_t)(u ^ n) * 16, a1 = xbase + (uint32_t)((u + 1) ^ n) * 16;
+                u32x4 r[RT][2];
+                gemm_f4_read_a<RT>(r, a0, a1);
+                const auto lo = I4Widen<TT>::cvt(cur[j][2 * h], grp), hi = I4Widen<TT>::cvt(cur[j][2 * h + 1], grp);
+#pragma unroll
+                for (int mt = 0; mt < RT; mt++) {
+                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
+                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, acc[mt]);
+                }
+            }
+            if (RT >= 3 && c + DEPTH < n_chunks) {             // 48 / 64 rows: refill per unit (see k_gemm_skinny)
+                load_wj(cur, c + DEPTH, j);
+                if (j == 1) load_s(cs, c + DEPTH);
+#pragma unroll
+                for (int i = 2 * j; i < 2 * j + 2; i++)
+                    if (i < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, i);
+            }
+        }
+        if (RT < 3 && c + DEPTH < n_chunks) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
+    };
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++)
+        if (d < n_chunks) { load_w(wr[d], gdr[d], d); stage_x(d, d); }
+    int buf = 0;
+    for (int c = 0; c < n_chunks; c += DEPTH) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++)
+            if (c + d < n_chunks) { phase(wr[d], gdr[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+    }
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n; scale and zero point went in with the widening
+    if constexpr (GU) {
+        float *ex = reinterpret_cast<float *>(gemm_lds);            // [R][64] up values; the A tiles are dead by now
+        __syncthreads();
+        if (w >= 4) {
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) ex[(16 * mt + 4 * g + r) * 64 + 16 * (w - 4) + n] = acc[mt][r];
+        }
+        __syncthreads();
+        if (w < 4) {
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int m = 16 * mt + 4 * g + r;
+                    if (m >= cnt) continue;
+                    // the roundings of HF's act_fn(gate) * up in the model dtype (same as moe_expert_gemm)
+                    const float gf = (float)(E)acc[mt][r], uf = (float)(E)ex[m * 64 + 16 * w + n];
+                    const E sv = (E)(gf / (1.f + __expf(-gf)));
+                    out[(size_t)lst[m] * (N / 2) + blockIdx.x * 64 + 16 * w + n] = (E)((float)sv * uf);
+                }
+        }
+    } else {
+#pragma unroll
+        for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int m = 16 * mt + 4 * g + r;
+                if (m < cnt) out[(size_t)lst[m] * N + n0 + n] = (E)acc[mt][r];
+            }
+    }
+}
+
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i4_gate_up_silu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4,
+                                                                         const int *__restrict__ ws, typename TT::elem *__restrict__ act,
+                                                                         int K, int N, int n_chunks, int top_k) {
+    moe_i4_expert_gemm<TT, RT, true>(h, W4, ws, act, K, N, n_chunks, top_k);
+}
+
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i4_down(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4,
+                                                                 const int *__restrict__ ws, typename TT::elem *__restrict__ y,
+                                                                 int K, int N, int n_chunks, int top_k) {
+    moe_i4_expert_gemm<TT, RT, false>(act, W4, ws, y, K, N, n_chunks, top_k);
+}
+
+template <typename TT, int RT, bool GU>
+static hipError_t moe_i4_gemm_launch(dim3 grid, hipStream_t st, const void *A, const void *W4, const int *ws, void *out, int K, int N, int top_k) {
+    typedef typename TT::elem E;
+    constexpr int lds = (MoeI4Depth<RT>::value + 1) * 16 * RT * GEMM_KC * 2;
+    if constexpr (GU) {
+        if constexpr (lds > 65536) {
+            static unsigned long long done = 0ull;                 // per-device (samd_common.h)
+            const hipError_t attr = samd_reserve_lds((const void *)k_moe_i4_gate_up_silu<TT, RT>, lds, &done);
+            if (attr != hipSuccess) return attr;
+        }
+        hipLaunchKernelGGL((k_moe_i4_gate_up_silu<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const unsigned char *)W4, ws, (E *)out, K, N,
+                           K / GEMM_KC, top_k);
+    } else {
+        if constexpr (lds > 65536) {
+            static unsigned long long done = 0ull;
+            const hipError_t attr = samd_reserve_lds((const void *)k_moe_i4_down<TT, RT>, lds, &done);
+            if (attr != hipSuccess) return attr;
+        }
+        hipLaunchKernelGGL((k_moe_i4_down<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const unsigned char *)W4, ws, (E *)out, K, N,
+                           K / GEMM_KC, top_k);
+    }
+    return hipSuccess;
+}
+
+template <bool GU>
+static hipError_t moe_i4_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W4, const int *ws, void *out, int K, int N, int top_k) {
+#define GO(TT, RT) return moe_i4_gemm_launch<TT, RT, GU>(grid, st, A, W4, ws, out, K, N, top_k)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
+}
+
+extern "C" {
+
+int samd_moe_gate_up_silu_i4(const void *d_h, const void *d_Wgu4, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
+                             int32_t top_k, void *d_act, int32_t dtype, void *stream) {
+    if (!d_h || !d_Wgu4 || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
+        samd_set_error("samd_moe_gate_up_silu_i4: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
+    }
+    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const hipError_t e = moe_i4_gemm_dispatch<true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu4, (const int *)d_ws, d_act,
+                                                  hidden, 2 * moe_inter, top_k);
+    if (e != hipSuccess) { samd_set_error("samd_moe_gate_up_silu_i4: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_moe_down_combine_i4(const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                             int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream) {
+    if (!d_act || !d_Wdown4 || !d_topk_idx || !d_topk_w || !d_n || !d_ws || !d_out || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
+        samd_set_error("samd_moe_down_combine_i4: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    void *y = (char *)d_ws + MOE_WS_Y_OFF;
+    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const hipError_t e = moe_i4_gemm_dispatch<false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown4, (const int *)d_ws, y, moe_inter, hidden, top_k);
+    if (e != hipSuccess) { samd_set_error("samd_moe_down_combine_i4: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
+    if (dtype == SAMD_F16)
+        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
+    else
+        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+}  // extern "C"

@@ -155,8 +155,13 @@ class LlamaRunner:
         # expert_format "mxfp4": the experts of every sparse layer, and nothing else, as MXFP4 (samd_hip/moe.py); the default takes env
         # SAMD_EXPERT_FORMAT, and 4-bit expert tensors in `weights` make the runner "mxfp4" by themselves.  A knob of its own: weight_format
         # means the four dense projections and stays rejected for models with sparse layers
-        experts4 = [MOE.is_4bit(l["experts_gu"]) or MOE.is_4bit(l["experts_down"]) for l in weights["layers"] if "experts_gu" in l]
-        self.expert_format = MOE.resolve_expert_format(expert_format, any(experts4), shape.moe)      # (before any device work, as the next)
+        # expert_format "int4g128": the experts as AWQ / GPTQ INT4 (codes + "_z" zero points + "_s" scales in the model dtype: the _z / _s keys
+        # tell them from MXFP4's "_scale"); INT4 expert tensors make the runner "int4g128" by themselves
+        sparse_l = [l for l in weights["layers"] if "experts_gu" in l]
+        experts_i4 = [any(k in l for k in ("experts_gu_z", "experts_gu_s", "experts_down_z", "experts_down_s")) for l in sparse_l]
+        experts4 = [not i4e and (MOE.is_4bit(l["experts_gu"]) or MOE.is_4bit(l["experts_down"])) for l, i4e in zip(sparse_l, experts_i4)]
+        self.expert_format = MOE.resolve_expert_format(expert_format, any(experts4), shape.moe,
+                                                       carries_int4=any(experts_i4))                 # (before any device work, as the next)
         if shape.moe:
             MOE.reject_unsupported(_weight_format(weight_format, weights, dtype), native_gemm, draft_head)
         if any(experts4):
@@ -167,6 +172,14 @@ class LlamaRunner:
                 if "experts_gu" in l:
                     MOE.check_quantised_experts(l["experts_gu"], l.get("experts_gu_scale"), l["experts_down"], l.get("experts_down_scale"), dtype,
                                                 f"layer {i} experts")
+        if any(experts_i4):
+            if not all(experts_i4):
+                raise SamdError(f"a mix of INT4 and other sparse layers ({sum(experts_i4)} of {len(experts_i4)} carry INT4 experts): "
+                                "the runner takes the experts of all sparse layers in one format")
+            for i, l in enumerate(weights["layers"]):
+                if "experts_gu" in l:
+                    MOE.check_int4_experts((l["experts_gu"], l.get("experts_gu_z"), l.get("experts_gu_s")),
+                                           (l["experts_down"], l.get("experts_down_z"), l.get("experts_down_s")), dtype, f"layer {i} experts")
         self.draft_head = bool(draft_head)                       # the decoder is an EAGLE head (forward_rows)
         require_gpu()
         self.shape, self.dtype, self.device = shape, dtype, torch.device(device)
@@ -375,6 +388,18 @@ class LlamaRunner:
                     for k, t in zip(ekeys, quad):
                         l[k] = torch.empty(t.shape, dtype=torch.uint8, device="meta")
                     del quad
+                elif self.expert_format == "int4g128":
+                    # the experts as codes + zero points + scales (the checkpoint's own, already checked, or quantised here), packed once for
+                    # this dtype; only shapes stay
+                    gkeys, dkeys = ("experts_gu", "experts_gu_z", "experts_gu_s"), ("experts_down", "experts_down_z", "experts_down_s")
+                    if "experts_gu_z" in l:
+                        gu3, dn3 = (tuple(l[k].to(self.device).contiguous() for k in ks) for ks in (gkeys, dkeys))
+                    else:
+                        gu3, dn3 = MOE.quantize_experts_int4(l["experts_gu"], l["experts_down"], dtype, f"layer {len(layers)} experts")
+                    lp["moe_gu"], lp["moe_down"] = MOE.pack_experts_int4(gu3, dn3, dtype)
+                    for k, t in zip(gkeys + dkeys, gu3 + dn3):
+                        l[k] = torch.empty(t.shape, dtype=t.dtype, device="meta")
+                    del gu3, dn3
                 else:
                     lp["moe_gu"], lp["moe_down"] = MOE.pack_experts(l["experts_gu"], l["experts_down"])
                     for k in ("experts_gu", "experts_down"):
@@ -575,7 +600,19 @@ class LlamaRunner:
         expert_format (default: env SAMD_EXPERT_FORMAT, unset = the model dtype; models with sparse layers only): "mxfp4" quantises the EXPERTS
         of every sparse layer on load (uncalibrated: for benches and tests); router, attention, dense MLP layers, embedding and lm_head stay in
         the model dtype.  A module whose sparse layers carry 4-bit expert tensors with their block scales (samd_hip/moe.py has the convention)
-        is imported as it is and makes the runner "mxfp4" by itself; an explicit expert_format=None against such a module raises."""
+        is imported as it is and makes the runner "mxfp4" by itself; an explicit expert_format=None against such a module raises.
+        "int4g128" quantises the experts per group of 128 with a zero point on load (uncalibrated, as weight_format "int4g128" does).  A 4-bit
+        Qwen3-MoE checkpoint (AWQ / GPTQ) holds, in every sparse layer, an indexable `mlp.experts` of E modules whose gate_proj / up_proj /
+        down_proj are AWQ / GPTQ modules (`mlp.experts.{e}.gate_proj.qweight` ...): each is imported through int4.linear_int4 with the
+        config's quantization_config (so act-order, group sizes 32 / 64, GEMV or a v1 zero point of 15 raise by module name), gate|up are
+        fused per expert, the experts stacked, the scales rounded once for a bf16 runner, and the runner is "int4g128" by itself; an explicit
+        None or "mxfp4" against such a module raises.  The router must be a plain `weight` (an INT4 router raises).  The INT4 attention and
+        dense-MLP projections of a module with sparse layers are NOT streamed as INT4 (weight_format stays rejected for mixture-of-experts
+        models): they are dequantised ONCE at import by int4.dequantize_groups to the model dtype -- exactly the weights an INT4 launch would
+        multiply by, one rounding -- and run on the model-dtype kernels, at 16 bits instead of 4.25 per weight of those projections
+        (Qwen3-30B-A3B: 48 layers x 37.7 M attention weights = 3.6 GB instead of 0.96 GB; the experts, 97 % of the model, stay 4-bit).
+        Streaming them through samd_gemm_skinny_i4 inside a mixture-of-experts stack is the follow-up.  share_weights does not apply to
+        dequantised projections (there is no HF `weight` to re-point); INT4 attention beside model-dtype or MXFP4 experts stays rejected."""
         weight_format = _env_weight_format(weight_format)
         m = lm.model
         parts = (("self_attn", "q_proj"), ("self_attn", "k_proj"), ("self_attn", "v_proj"), ("self_attn", "o_proj"), ("mlp", "gate_proj"),
@@ -594,6 +631,13 @@ class LlamaRunner:
         qkv_bias, qk_norm = cls._hf_layer_extras(m.layers)
         shape = LlamaShape(lm.config, qkv_bias=qkv_bias, qk_norm=qk_norm)
         sparse = cls._hf_sparse_layers(m.layers)
+        # a module with INT4 EXPERTS whose attention / dense-MLP projections are INT4 too (an AWQ / GPTQ mixture-of-experts checkpoint):
+        # these are dequantised once at import (the docstring), so the runner is not a weight_format "int4g128" one.  INT4 projections
+        # beside model-dtype or MXFP4 experts stay rejected as before
+        experts_i4 = [cls._hf_experts_are_int4(lyr, i) for i, lyr in enumerate(m.layers) if sparse[i]]
+        moe_i4_dense = ckpt_i4 and any(experts_i4)
+        if moe_i4_dense:
+            ckpt_i4 = False
         if any(sparse) or shape.moe:
             if sparse != list(shape.sparse):
                 raise SamdError(f"the module's sparse MLP layers {[i for i, x in enumerate(sparse) if x]} are not the ones its config implies "
@@ -602,8 +646,18 @@ class LlamaRunner:
                                    kw.get("draft_head", False))
         # 4-bit experts: decided and checked on the module's own tensors, before anything moves to the device (the runner resolves the
         # format again from the weights it is given)
-        experts4 = [cls._hf_experts_are_4bit(lyr, i) for i, lyr in enumerate(m.layers) if sparse[i]]
-        MOE.resolve_expert_format(expert_format, any(experts4), any(sparse) or shape.moe)
+        experts4 = [not i4e and cls._hf_experts_are_4bit(lyr, i)
+                    for (i, lyr), i4e in zip(((i, lyr) for i, lyr in enumerate(m.layers) if sparse[i]), experts_i4)]
+        MOE.resolve_expert_format(expert_format, any(experts4), any(sparse) or shape.moe, carries_int4=any(experts_i4))
+        if any(experts_i4) and not all(experts_i4):
+            plain = [i for i, sp in enumerate(sparse) if sp and not cls._hf_experts_are_int4(m.layers[i], i)][:3]
+            raise SamdError(f"a mix of INT4 and other sparse layers ({sum(experts_i4)} of {len(experts_i4)} carry INT4 experts; e.g. layers "
+                            f"{plain} do not): the runner takes the experts of all sparse layers in one format")
+        for i, lyr in enumerate(m.layers):
+            if sparse[i] and any(experts_i4) and len(lyr.mlp.experts) != shape.n_experts:
+                raise SamdError(f"layers.{i}.mlp.experts: {len(lyr.mlp.experts)} expert modules, the config says num_experts = {shape.n_experts}")
+            if sparse[i] and I4.is_int4_module(getattr(lyr.mlp, "gate", None)):
+                raise SamdError(f"layers.{i}.mlp.gate: an INT4 router is not supported: the router stays a plain `weight` in the model dtype")
         if any(experts4):
             if not all(experts4):
                 plain = [i for i, sp in enumerate(sparse) if sp and not cls._hf_experts_are_4bit(m.layers[i], i)][:3]
@@ -627,7 +681,16 @@ class LlamaRunner:
         share = (os.environ.get("SAMD_SHARE_HF_WEIGHTS", "0") == "1") if share_weights is None else bool(share_weights)
         shared = [0]
 
-        def fuse(linears):
+        def lin_w(mod, name):
+            """a projection's weight; an INT4 module's (a module with sparse layers only) dequantised: rne_dtype((q - z) * s), one rounding"""
+            if not I4.is_int4_module(mod):
+                return mod.weight
+            q, z, sc = I4.linear_int4(mod, name, config=qcfg)
+            return I4.dequantize_groups(q, z, I4.as_scales(sc, dtype, name)).to(dtype)
+
+        def fuse(linears, names=None):
+            if moe_i4_dense:
+                return get(torch.cat([lin_w(l, n) for l, n in zip(linears, names)], dim=0))
             ws = [l.weight for l in linears]
             cat = get(torch.cat(ws, dim=0))
             if share and all(w.device == cat.device and w.dtype == cat.dtype for w in ws):
@@ -665,25 +728,33 @@ class LlamaRunner:
                     lw[k], lw[k + "_scale"] = F8.fuse_fp8([F8.linear_fp8(x) for x in lins], dev)
                 layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
                 continue
+            li = len(layers)
+            qkv_names, o_name = [f"layers.{li}.self_attn.{x}" for x in ("q_proj", "k_proj", "v_proj")], f"layers.{li}.self_attn.o_proj"
+            if sparse[li] and any(experts_i4):                   # router + the experts' canonical (q, z, s), fused and stacked
+                layers.append(dict(
+                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
+                    **MOE.import_experts_int4(f.experts, f"layers.{li}.mlp.experts", dtype, dev, qcfg),
+                    ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
+                continue
             if sparse[len(layers)] and any(experts4):            # router + the 4-bit expert tensors and their block scales, as they are
                 ex, raw = f.experts, lambda t: MX._bytes(t.detach()).to(dev).contiguous()
                 layers.append(dict(
-                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj)), wo=get(a.o_proj.weight), router=get(f.gate.weight),
+                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
                     experts_gu=raw(ex.gate_up_proj), experts_gu_scale=raw(ex.gate_up_proj_scale),
                     experts_down=raw(ex.down_proj), experts_down_scale=raw(ex.down_proj_scale),
                     ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
                 continue
             if sparse[len(layers)]:                              # router + HF's fused expert tensors [E, 2 I, H] / [E, H, I]
                 layers.append(dict(
-                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj)), wo=get(a.o_proj.weight), router=get(f.gate.weight),
+                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
                     experts_gu=get(f.experts.gate_up_proj), experts_down=get(f.experts.down_proj),
                     ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
                 continue
             layers.append(dict(
-                wqkv=fuse((a.q_proj, a.k_proj, a.v_proj)),
-                wo=get(a.o_proj.weight),
-                wgu=fuse((f.gate_proj, f.up_proj)),
-                wdown=get(f.down_proj.weight),
+                wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names),
+                wo=get(lin_w(a.o_proj, o_name)),
+                wgu=fuse((f.gate_proj, f.up_proj), [f"layers.{li}.mlp.gate_proj", f"layers.{li}.mlp.up_proj"]),
+                wdown=get(lin_w(f.down_proj, f"layers.{li}.mlp.down_proj")),
                 ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
         weights = dict(embed=get(m.embed_tokens.weight), layers=layers, norm=get(m.norm.weight), lm_head=get(lm.lm_head.weight))
         if shared[0]:
@@ -702,6 +773,23 @@ class LlamaRunner:
                             "4-bit experts need both tensors 4-bit")
         return gu
 
+    @classmethod
+    def _hf_experts_are_int4(cls, lyr, i):
+        """does layer i hold per-expert INT4 (AWQ / GPTQ) modules -- an indexable `mlp.experts` of modules with gate_proj / up_proj / down_proj
+        that are all INT4 (int4.is_int4_module)?  All: True; none (or the fused form, or no experts): False; some experts or some of the
+        three projections only: raises by name"""
+        ex = getattr(getattr(lyr, "mlp", None), "experts", None)
+        if ex is None or hasattr(ex, "gate_up_proj") or not hasattr(ex, "__len__") or not hasattr(ex, "__getitem__"):
+            return False
+        kinds = [(f"layers.{i}.mlp.experts.{e}.{p}", I4.is_int4_module(getattr(ex[e], p, None)))
+                 for e in range(len(ex)) for p in MOE.INT4_EXPERT_PROJECTIONS]
+        n4 = sum(k for _, k in kinds)
+        if 0 < n4 < len(kinds):
+            plain = [n for n, k in kinds if not k][:3]
+            raise SamdError(f"layers.{i}.mlp.experts: a mix of INT4 and other expert projections ({n4} of {len(kinds)} are INT4; e.g. "
+                            f"{', '.join(plain)} are not): INT4 experts need gate_proj, up_proj and down_proj of every expert INT4")
+        return n4 > 0
+
     # the parameters of a decoder layer that from_hf reads (named_parameters; FP8 checkpoints' weight_scale tensors are buffers)
     _LAYER_PARAMS = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
                      "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight", "input_layernorm.weight", "post_attention_layernorm.weight")
@@ -718,7 +806,7 @@ class LlamaRunner:
         may alternate); a shared expert or any other MLP parameter raises by name."""
         if len(layers) == 0:
             raise SamdError("the model has no decoder layers")
-        def names_of(lyr):
+        def names_of(lyr, i):
             # an FP8 projection's scales may be parameters as well as buffers (fbgemm / compressed-tensors layers): the runner reads
             # weight_scale through samd_hip/fp8.py (input scales are not used: weight-only FP8), so they are not extra parameters
             # (the same holds for an MXFP4 projection -- a float4_e2m1fn_x2 or uint8 weight -- and its e8m0 weight_scale)
@@ -739,14 +827,21 @@ class LlamaRunner:
                         params[n + ".bias"] = None
             if any(MOE.is_4bit(params.get(n)) for n in MOE.SPARSE_MLP_PARAMS[1:]):
                 skip |= set(MOE.EXPERT_SCALE_PARAMS)
+            # per-expert INT4 modules (mlp.experts.{e}.gate_proj ...; their tensors are buffers) count as the two fused expert tensors; a
+            # bias of one of them stays in the set and raises by name below
+            if cls._hf_experts_are_int4(lyr, i):
+                for e in range(len(lyr.mlp.experts)):
+                    for pn in MOE.INT4_EXPERT_PROJECTIONS:
+                        params.pop(f"mlp.experts.{e}.{pn}.weight", None)
+                params.update({n: None for n in MOE.SPARSE_MLP_PARAMS[1:]})
             return set(params) - skip
-        names0 = names_of(layers[0])
+        names0 = names_of(layers[0], 0)
         qkv_bias = any(n in names0 for n in cls._QKV_BIAS)
         qk_norm = any(n in names0 for n in cls._QK_NORM)
         want = set(cls._LAYER_PARAMS) | (set(cls._QKV_BIAS) if qkv_bias else set()) | (set(cls._QK_NORM) if qk_norm else set())
         want_sparse = (want - set(MOE.DENSE_MLP_PARAMS)) | set(MOE.SPARSE_MLP_PARAMS)
         for i, lyr in enumerate(layers):
-            names = names_of(lyr)
+            names = names_of(lyr, i)
             if names == want:
                 continue
             if any(n.startswith("mlp.experts.") or n == "mlp.gate.weight" for n in names):      # a sparse (Qwen3-MoE) layer
@@ -768,7 +863,8 @@ class LlamaRunner:
     @classmethod
     def _hf_sparse_layers(cls, layers):
         """per decoder layer: does its MLP hold experts (an HF Qwen3MoeSparseMoeBlock)?"""
-        return [any(n.startswith("mlp.experts.") for n, _ in lyr.named_parameters()) for lyr in layers]
+        return [any(n.startswith("mlp.experts.") for n, _ in lyr.named_parameters()) or cls._hf_experts_are_int4(lyr, i)
+                for i, lyr in enumerate(layers)]
 
     @classmethod
     def random_init(cls, cfg, max_cache_len, dtype=torch.float16, device="cuda", seed=0, std=0.02, weight_format=None, expert_format=MOE.AUTO, **kw):

@@ -12,12 +12,22 @@ samd_moe_gate_up_silu_f4 / samd_moe_down_combine_f4.  Router, attention, dense M
 transformers has no quantised form of its fused Qwen3-MoE expert module, so the pre-quantised convention is this project's own: a sparse
 layer's `mlp.experts.gate_up_proj` [E, 2 I, H/2] and `mlp.experts.down_proj` [E, H, I/2] as uint8 or float4_e2m1fn_x2 (low nibble = the even
 element), with `mlp.experts.gate_up_proj_scale` [E, 2 I, H/32] and `mlp.experts.down_proj_scale` [E, H, I/32] as uint8 or float8_e8m0fnu,
-parameters or buffers; in a raw weights dict: experts_gu, experts_gu_scale, experts_down, experts_down_scale."""
+parameters or buffers; in a raw weights dict: experts_gu, experts_gu_scale, experts_down, experts_down_scale.
+
+expert_format "int4g128" keeps the EXPERTS as AWQ / GPTQ INT4 (samd_hip/int4.py: 4-bit codes, one zero point and one scale in the model dtype
+per 128 along k, W = rne_dtype((q - z) * s)): (q [E, N, K/2], z [E, N, K/128], s [E, N, K/128]) per fused tensor, packed by samd_gemm_pack_i4
+as one matrix of E * N rows (the buffer is dtype-specific) and streamed by samd_moe_gate_up_silu_i4 / samd_moe_down_combine_i4.  A 4-bit
+Qwen3-MoE checkpoint holds an indexable `mlp.experts` of E modules with AWQ / GPTQ gate_proj / up_proj / down_proj (`mlp.experts.{e}.
+gate_proj.qweight` ...), which LlamaRunner.from_hf imports through int4.linear_int4; in a raw weights dict: experts_gu uint8 [E, 2 I, H/2],
+experts_gu_z uint8 [E, 2 I, H/128], experts_gu_s model dtype [E, 2 I, H/128], and experts_down / _z / _s likewise with [E, H, I/...] -- the
+_z / _s keys are what tells INT4 from MXFP4 (_scale).  EXPERT_FORMATS stays the pair of the first two formats (callers pin it);
+EXPERT_FORMATS_ALL is what an expert_format is validated against."""
 import os
 
 import torch
 
-from . import SamdError, _ptr, check, current_stream, lib
+from . import SamdError, _ptr, check, current_stream, lib, torch_dtype_code
+from . import int4 as I4
 from . import mxfp4 as MX
 
 MAX_EXPERTS = 256
@@ -29,6 +39,9 @@ DENSE_MLP_PARAMS = ("mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj
 EXPERT_SCALE_PARAMS = ("mlp.experts.gate_up_proj_scale", "mlp.experts.down_proj_scale")
 # what the experts of the sparse layers may be held in: None = the model dtype
 EXPERT_FORMATS = (None, "mxfp4")
+EXPERT_FORMATS_ALL = EXPERT_FORMATS + ("int4g128",)
+# the projections of one expert module of an INT4 (AWQ / GPTQ) checkpoint: mlp.experts.{e}.gate_proj / up_proj / down_proj
+INT4_EXPERT_PROJECTIONS = ("gate_proj", "up_proj", "down_proj")
 
 
 class _Auto:
@@ -69,18 +82,29 @@ def reject_unsupported(weight_format=None, native_gemm=True, draft_head=False):
         raise SamdError("mixture-of-experts layers are not supported on an EAGLE draft head")
 
 
-def resolve_expert_format(expert_format, carries_4bit, has_sparse):
-    """None or "mxfp4" from the argument (AUTO: env SAMD_EXPERT_FORMAT, for callers that cannot pass one) and from what the weights carry:
-    4-bit expert tensors make the runner "mxfp4" by themselves.  Raises before any device work."""
+def resolve_expert_format(expert_format, carries_4bit, has_sparse, carries_int4=False):
+    """None, "mxfp4" or "int4g128" from the argument (AUTO: env SAMD_EXPERT_FORMAT, for callers that cannot pass one) and from what the
+    weights carry: MXFP4 expert tensors (carries_4bit) make the runner "mxfp4" by themselves, INT4 ones (carries_int4) "int4g128"; any other
+    explicit format against them raises.  Raises before any device work."""
     explicit = expert_format is not AUTO
     if not explicit:
         expert_format = os.environ.get("SAMD_EXPERT_FORMAT") or None
-    if expert_format not in EXPERT_FORMATS:
-        raise SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS)}")
+    if expert_format not in EXPERT_FORMATS_ALL:
+        raise SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS_ALL)}")
     if expert_format is not None and not has_sparse:
         raise SamdError(f"expert_format '{expert_format}' on a model without mixture-of-experts (sparse) layers: it covers the experts only; "
                         "weight_format covers the dense projections")
+    if carries_4bit and carries_int4:
+        raise SamdError("a mix of MXFP4 and INT4 expert tensors: the runner takes the experts of all sparse layers in one format")
+    if carries_int4:
+        if explicit and expert_format != "int4g128":
+            raise SamdError(f"the sparse layers carry INT4 (AWQ / GPTQ) expert tensors; expert_format={expert_format!r} would need them "
+                            "dequantised (leave it out or pass 'int4g128')")
+        return "int4g128"
     if carries_4bit:
+        if explicit and expert_format == "int4g128":
+            raise SamdError("the sparse layers carry 4-bit (MXFP4) expert tensors; expert_format='int4g128' would need them re-quantised "
+                            "(leave it out or pass 'mxfp4')")
         if explicit and expert_format is None:
             raise SamdError("the sparse layers carry 4-bit (MXFP4) expert tensors; expert_format=None would need them dequantised "
                             "(leave it out or pass 'mxfp4')")
@@ -166,6 +190,100 @@ def pack_experts_mxfp4(q_gu, e8_gu, q_down, e8_down):
     return tuple(out)
 
 
+def quantize_experts_int4(gate_up, down, dtype, name="experts"):
+    """((q, z, s) of gate|up, (q, z, s) of down) of HF's fused expert tensors [E, 2 I, H] / [E, H, I]: int4.quantize_groups on every expert
+    (asymmetric min / max per group of 128 along K, round to nearest, no calibration: for benches and tests).  q uint8 [E, N, K/2], z uint8
+    [E, N, K/128], s `dtype` [E, N, K/128]."""
+    E, N2, H = gate_up.shape
+    if tuple(down.shape) != (E, H, N2 // 2):
+        raise SamdError(f"{name}: expert tensors of shapes {tuple(gate_up.shape)} and {tuple(down.shape)} do not belong together")
+    out = []
+    for t in (gate_up, down):
+        _, N, K = t.shape
+        if K % I4.GROUP != 0:
+            raise SamdError(f"{name}: INT4 needs K % 128 == 0, got [{E}, {N}, {K}] experts")
+        q = torch.empty((E, N, K // 2), dtype=torch.uint8, device=t.device)
+        z = torch.empty((E, N, K // I4.GROUP), dtype=torch.uint8, device=t.device)
+        s = torch.empty((E, N, K // I4.GROUP), dtype=dtype, device=t.device)
+        for e in range(E):                                       # (expert by expert: the fp32 temporaries stay small)
+            q[e], z[e], s[e] = I4.quantize_groups(t[e], dtype)
+        out.append((q, z, s))
+    return tuple(out)
+
+
+def dequantize_experts_int4(q, z, s, dtype=None):
+    """rne_{s.dtype}((q - z) * s), [E, N, K] in fp32 (or `dtype`): the weights the INT4 expert kernels of a runner in s.dtype multiply by"""
+    E, N, Kh = q.shape
+    w = I4.dequantize_groups(q.reshape(E * N, Kh), z.reshape(E * N, -1), s.reshape(E * N, -1)).reshape(E, N, 2 * Kh)
+    return w if dtype is None else w.to(dtype)
+
+
+def check_int4_experts(gu, down, dtype, name="experts"):
+    """the shapes, dtypes, zero points and scales of INT4 expert tensors (gu, down: (q, z, s) each) for a runner in `dtype`; raises SamdError
+    by tensor name.  Plain torch, any device."""
+    for what, (q, z, s) in ((f"{name}.gate_up_proj", gu), (f"{name}.down_proj", down)):
+        if z is None or s is None:
+            raise SamdError(f"{what}: INT4 expert tensor without its zero points and scales")
+        if q.dtype != torch.uint8 or z.dtype != torch.uint8 or q.dim() != 3:
+            raise SamdError(f"{what}: INT4 codes and zero points are uint8 tensors (q [E, N, K/2], z [E, N, K/128]), got {q.dtype} "
+                            f"{tuple(q.shape)} and {z.dtype} {tuple(z.shape)}")
+        E, N, Kh = q.shape
+        if N % 128 != 0 or (2 * Kh) % 256 != 0:
+            raise SamdError(f"{what} of shape ({E}, {N}, {2 * Kh}): the INT4 expert kernels need N % 128 == 0 and K % 256 == 0")
+        want = (E, N, 2 * Kh // I4.GROUP)
+        if tuple(z.shape) != want or tuple(s.shape) != want:
+            raise SamdError(f"{what}: zero points {tuple(z.shape)} / scales {tuple(s.shape)} for [{E}, {N}, {2 * Kh}] experts; one per 128 "
+                            f"along K is {want}")
+        if s.dtype != dtype:
+            raise SamdError(f"{what}: scales of dtype {s.dtype} for a {dtype} runner (int4.as_scales rounds a checkpoint's fp16 scales once)")
+        if bool((z > 15).any()):
+            raise SamdError(f"{what}: a zero point above 15")
+        I4.check_scales(s, dtype, what)
+    E, N2, Hh = gu[0].shape
+    if tuple(down[0].shape) != (E, 2 * Hh, N2 // 4):
+        raise SamdError(f"{name}: INT4 expert tensors of shapes {tuple(gu[0].shape)} and {tuple(down[0].shape)} do not belong together "
+                        f"(gate_up_proj [E, 2 I, H/2], down_proj [E, H, I/2])")
+
+
+def pack_experts_int4(gu, down, dtype):
+    """(packed gate|up, packed down) of (q, z, s) triples: uint8 buffers of E * int4.packed_bytes(N, K) bytes each in samd_gemm_pack_i4's
+    layout, the experts end to end as one matrix of E * N rows (tile e * N / 128 + t is expert e's tile t).  The gate|up rows are permuted
+    first (gate_up_tile_order; groups run along k, so whole rows move with their zero points and scales).  The buffers are specific to
+    `dtype` (scales and pre-biased zero points are stored in it).  Tensors already on the GPU.  The two returned tensors carry the mark
+    MoeBuffers.experts(..., expert_format="int4g128") asks for; pass them on as they are."""
+    check_int4_experts(gu, down, dtype)
+    E, N2, Hh = gu[0].shape
+    I, H = N2 // 2, 2 * Hh
+    order = gate_up_tile_order(I, gu[0].device)
+    dt_code = torch_dtype_code(dtype)
+    out = []
+    for (q, z, s), N, K in ((tuple(t[:, order] for t in gu), N2, H), (down, H, I)):
+        q, z, s = q.contiguous(), z.contiguous(), s.contiguous()
+        buf = torch.empty(E * I4.packed_bytes(N, K), dtype=torch.uint8, device=q.device)
+        check(lib().samd_gemm_pack_i4(_ptr(q), _ptr(z), _ptr(s), _ptr(buf), E * N, K, dt_code, current_stream()))
+        # as many bytes as the MXFP4 form: MoeBuffers.experts takes only tensors that carry this mark as INT4 ones.  A copy, a view or a
+        # slice does not carry it and is refused -- the guard fails closed; hand over the tensors this function returned
+        buf.expert_format = "int4g128"
+        out.append(buf)
+    return tuple(out)
+
+
+def import_experts_int4(experts, name, dtype, device, config=None):
+    """the raw-weights-dict entries (experts_gu / _z / _s, experts_down / _z / _s) of an indexable of E expert modules whose gate_proj /
+    up_proj / down_proj are AWQ / GPTQ modules: each imported by int4.linear_int4 (`config`: the model's quantization_config; its rejections
+    reach the caller by module name), gate|up fused per expert, the experts stacked on `device`, the scales rounded once to `dtype`."""
+    gu, dn = [], []
+    for e in range(len(experts)):
+        g, u, d = (I4.linear_int4(getattr(experts[e], p), f"{name}.{e}.{p}", config=config) for p in INT4_EXPERT_PROJECTIONS)
+        gu.append(I4.fuse_int4([g, u], device, dtype))
+        dn.append(I4.fuse_int4([d], device, dtype))
+    out = {}
+    for key, parts in (("experts_gu", gu), ("experts_down", dn)):
+        for sfx, j in (("", 0), ("_z", 1), ("_s", 2)):
+            out[key + sfx] = torch.stack([p[j] for p in parts]).contiguous()
+    return out
+
+
 def pack_experts(gate_up, down):
     """(packed gate|up, packed down) of HF's fused expert tensors [E, 2 I, H] / [E, H, I], already on the GPU in the model dtype"""
     E, N2, H = gate_up.shape
@@ -199,10 +317,24 @@ class MoeBuffers:
         check(lib().samd_moe_lists(_ptr(self.topk_idx), _ptr(d_n), self.rows_pad, self.n_experts, self.top_k, _ptr(self.ws), current_stream()))
 
     def experts(self, h, wgu_packed, wdown_packed, d_n, expert_format=None):
-        """the two expert launches over buffers of pack_experts (expert_format None) or pack_experts_mxfp4 ("mxfp4")"""
+        """the two expert launches over buffers of pack_experts (expert_format None), pack_experts_mxfp4 ("mxfp4") or pack_experts_int4
+        ("int4g128"; packed for this runner's dtype)"""
         L, st = lib(), current_stream()
-        if expert_format not in EXPERT_FORMATS:
-            raise SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS)}")
+        if expert_format not in EXPERT_FORMATS_ALL:
+            raise SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS_ALL)}")
+        if expert_format == "int4g128":
+            for t, want in ((wgu_packed, self.n_experts * I4.packed_bytes(2 * self.moe_inter, self.hidden)),
+                            (wdown_packed, self.n_experts * I4.packed_bytes(self.hidden, self.moe_inter))):
+                if t.dtype != torch.uint8 or t.numel() != want:
+                    raise SamdError(f"INT4 expert buffer of {t.numel()} {t.dtype} elements; pack_experts_int4 gives {want} bytes for this shape")
+                if getattr(t, "expert_format", None) != "int4g128":
+                    raise SamdError("expert_format 'int4g128' over a buffer that pack_experts_int4 did not return (an MXFP4 buffer of this shape "
+                                    "has the same byte count and other contents; a copy or a view of an INT4 buffer loses the packer's mark)")
+            check(L.samd_moe_gate_up_silu_i4(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts,
+                                             self.top_k, _ptr(self.act), self.dt, st))
+            check(L.samd_moe_down_combine_i4(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws),
+                                             self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k, _ptr(self.out), self.dt, st))
+            return self.out
         if expert_format == "mxfp4":
             for t, want in ((wgu_packed, self.n_experts * MX.packed_bytes(2 * self.moe_inter, self.hidden)),
                             (wdown_packed, self.n_experts * MX.packed_bytes(self.hidden, self.moe_inter))):

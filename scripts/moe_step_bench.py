@@ -12,11 +12,13 @@ random-init weights, per row bucket 1 / 8 / 16 / 64.
            gate|up + SiLU, down + combine and the whole three-call layer, each captured once over --layers weight sets and replayed ALTERNATELY
            (model dtype, mxfp4, model dtype, ...), every single replay between two hipEvents after a warm-up; median, 10th / 90th percentile and
            the achieved weight rate (bytes of the experts touched over the median of the two expert launches).  With --step step the forward is
-           built with expert_format="mxfp4".
+           built with expert_format="mxfp4".  --expert-format int4g128 adds the INT4 (AWQ / GPTQ) expert launches as a third graph in the
+           same alternation: model dtype and MXFP4, both untouched by the INT4 kernels, are its yardsticks in the same run.  --dtype picks
+           the model dtype (bf16 or fp16) of this step.
 
 Without --step every step runs as a child process of its own under its own time limit, and nothing more is started after a step that failed.
 --buckets 1 keeps a profiler's per-kernel statistics to one bucket: rocprofv3 --kernel-trace --stats -- python scripts/moe_step_bench.py --step experts --buckets 1
-usage: python scripts/moe_step_bench.py [--step experts|step] [--reps 30] [--layers 4] [--depth 12] [--buckets 1,8,16,64] [--expert-format none|mxfp4]"""
+usage: python scripts/moe_step_bench.py [--step experts|step] [--reps 30] [--layers 4] [--depth 12] [--buckets 1,8,16,64] [--expert-format none|mxfp4|int4g128] [--dtype bf16|fp16]"""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "sam-decoding_amd")]
@@ -109,15 +111,22 @@ def step_formats(a):
     import samd_hip
     from samd_hip import moe as MOE, _ptr, check, current_stream, lib
     H, I, E, k = A3B["hidden_size"], A3B["moe_intermediate_size"], A3B["num_experts"], A3B["num_experts_per_tok"]
-    dt, L, BF = torch.bfloat16, lib(), samd_hip.BF16
+    dt, BF = (torch.float16, samd_hip.F16) if a.dtype == "fp16" else (torch.bfloat16, samd_hip.BF16)
+    L = lib()
+    fmts = ("model", "mxfp4") + (("int4g128",) if a.expert_format == "int4g128" else ())
     g = torch.Generator(device="cuda").manual_seed(0)
     rnd = lambda *s: (torch.randn(s, generator=g, device="cuda") * 0.02).to(dt)
     sets = []
     for _ in range(a.layers):
         router, gu, dn = rnd(E, H) * 50, rnd(E, 2 * I, H), rnd(E, H, I)
-        sets.append((router, MOE.pack_experts(gu, dn), MOE.pack_experts_mxfp4(*MOE.quantize_experts(gu, dn, dt))))
+        packed = {"model": MOE.pack_experts(gu, dn), "mxfp4": MOE.pack_experts_mxfp4(*MOE.quantize_experts(gu, dn, dt))}
+        if "int4g128" in fmts:
+            packed["int4g128"] = MOE.pack_experts_int4(*MOE.quantize_experts_int4(gu, dn, dt), dt)
+        sets.append((router, packed))
         del gu, dn
-    per_expert = {"model": 3 * H * I * 2, "mxfp4": 3 * H * I // 2 + 3 * H * I // 32}
+    per_expert = {"model": 3 * H * I * 2, "mxfp4": 3 * H * I // 2 + 3 * H * I // 32, "int4g128": 3 * H * I // 2 + 3 * H * I // 32}
+    gate_up_fn = {"model": L.samd_moe_gate_up_silu, "mxfp4": L.samd_moe_gate_up_silu_f4, "int4g128": L.samd_moe_gate_up_silu_i4}
+    down_fn = {"model": L.samd_moe_down_combine, "mxfp4": L.samd_moe_down_combine_f4, "int4g128": L.samd_moe_down_combine_i4}
 
     def graph(fn):
         fn(); torch.cuda.synchronize()
@@ -143,7 +152,7 @@ def step_formats(a):
         h = torch.randn((RP, H), generator=g, device="cuda").to(dt)
         d_n = torch.tensor([n], dtype=torch.int32, device="cuda")
         bufs = [MOE.MoeBuffers(RP, H, I, E, k, dt, BF, "cuda") for _ in sets]
-        for (router, _, _), b in zip(sets, bufs):
+        for (router, _), b in zip(sets, bufs):
             b.route(h, router, d_n, True)
         torch.cuda.synchronize()
         active = [b.routing_state()[0] for b in bufs]
@@ -151,30 +160,29 @@ def step_formats(a):
         st = current_stream
 
         def gate_up(fmt):
-            f = L.samd_moe_gate_up_silu_f4 if fmt == "mxfp4" else L.samd_moe_gate_up_silu
-            for (_, pm, p4), b in zip(sets, bufs):
-                check(f(_ptr(h), _ptr((p4 if fmt == "mxfp4" else pm)[0]), _ptr(b.ws), RP, H, I, E, k, _ptr(b.act), BF, st()))
+            for (_, packed), b in zip(sets, bufs):
+                check(gate_up_fn[fmt](_ptr(h), _ptr(packed[fmt][0]), _ptr(b.ws), RP, H, I, E, k, _ptr(b.act), BF, st()))
 
         def down(fmt):
-            f = L.samd_moe_down_combine_f4 if fmt == "mxfp4" else L.samd_moe_down_combine
-            for (_, pm, p4), b in zip(sets, bufs):
-                check(f(_ptr(b.act), _ptr((p4 if fmt == "mxfp4" else pm)[1]), _ptr(b.topk_idx), _ptr(b.topk_w), _ptr(d_n), _ptr(b.ws), RP, H, I, E, k,
-                        _ptr(b.out), BF, st()))
+            for (_, packed), b in zip(sets, bufs):
+                check(down_fn[fmt](_ptr(b.act), _ptr(packed[fmt][1]), _ptr(b.topk_idx), _ptr(b.topk_w), _ptr(d_n), _ptr(b.ws), RP, H, I, E, k,
+                                   _ptr(b.out), BF, st()))
 
         def layer(fmt):
-            for (router, pm, p4), b in zip(sets, bufs):
+            for (router, packed), b in zip(sets, bufs):
                 b.route(h, router, d_n, True)
-                b.experts(h, *(p4 if fmt == "mxfp4" else pm), d_n, expert_format="mxfp4" if fmt == "mxfp4" else None)
-        out = dict(step="formats", rows=n, bucket=RP, experts_touched=active, reps=a.reps, layers=a.layers)
+                b.experts(h, *packed[fmt], d_n, expert_format=None if fmt == "model" else fmt)
+        out = dict(step="formats", dtype=a.dtype, rows=n, bucket=RP, experts_touched=active, reps=a.reps, layers=a.layers)
         med = {}
         for what, fn in (("gate_up", gate_up), ("down_combine", down), ("layer", layer)):
-            times = alternate({fmt: graph(lambda fmt=fmt: fn(fmt)) for fmt in ("model", "mxfp4")}, a.reps)
+            times = alternate({fmt: graph(lambda fmt=fmt: fn(fmt)) for fmt in fmts}, a.reps)
             for fmt, t in times.items():
                 med[what, fmt] = t[len(t) // 2]
                 out[f"{what}_{fmt}_us"] = dict(median=round(t[len(t) // 2], 2), p10=round(t[len(t) // 10], 2), p90=round(t[(9 * len(t)) // 10], 2),
                                                min=round(t[0], 2), max=round(t[-1], 2))
-            out[f"{what}_mxfp4_over_model"] = round(med[what, "mxfp4"] / med[what, "model"], 3)
-        for fmt in ("model", "mxfp4"):
+            for fmt in fmts[1:]:
+                out[f"{what}_{fmt}_over_model"] = round(med[what, fmt] / med[what, "model"], 3)
+        for fmt in fmts:
             nbytes = act_mean * per_expert[fmt]
             out[f"{fmt}_mbytes"] = round(nbytes / 1e6, 2)
             out[f"{fmt}_weight_tb_s"] = round(nbytes / (med["gate_up", fmt] + med["down_combine", fmt]) / 1e6, 3)
@@ -187,8 +195,8 @@ def step_forward(a):
     import torch
     import samd_hip
     from samd_hip.llama import LlamaRunner
-    runner = LlamaRunner.random_init(dict(A3B, num_hidden_layers=a.depth), 2048, torch.bfloat16, seed=0,
-                                     expert_format="mxfp4" if a.expert_format == "mxfp4" else None)
+    runner = LlamaRunner.random_init(dict(A3B, num_hidden_layers=a.depth), 2048, torch.float16 if a.dtype == "fp16" else torch.bfloat16, seed=0,
+                                     expert_format=None if a.expert_format == "none" else a.expert_format)
     sess = samd_hip.Session(4096)
     sess.reset()
     res, touched = {}, {}
@@ -203,7 +211,7 @@ def step_forward(a):
         touched[n] = round(sum(len(set(e[2][:e[1]].flatten().tolist())) for e in runner.route_log) / max(len(runner.route_log), 1), 1)
         runner.route_log = None
         res[n] = round(replay_us(lambda: runner.verify(sess, R), a.reps) / 1e3, 4)
-    print(json.dumps(dict(step="step", depth=a.depth, expert_format=runner.expert_format, step_ms=res, experts_touched_per_layer=touched,
+    print(json.dumps(dict(step="step", dtype=a.dtype, depth=a.depth, expert_format=runner.expert_format, step_ms=res, experts_touched_per_layer=touched,
                           ratio_to_1_row={n: round(res[n] / res[1], 3) for n in a.buckets if 1 in res})), flush=True)
 
 
@@ -214,16 +222,18 @@ def main():
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--buckets", default=",".join(map(str, BUCKETS)), help="row counts, comma separated")
-    ap.add_argument("--expert-format", default="none", choices=("none", "mxfp4"), help="mxfp4: the MXFP4 expert kernels against the model-dtype ones")
+    ap.add_argument("--expert-format", default="none", choices=("none", "mxfp4", "int4g128"),
+                    help="mxfp4: the MXFP4 expert kernels against the model-dtype ones; int4g128: the INT4 ones against both")
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp16"), help="model dtype of the formats and step measurements")
     a = ap.parse_args()
     a.buckets = tuple(int(b) for b in a.buckets.split(","))
     if a.step == "experts":
-        return step_formats(a) if a.expert_format == "mxfp4" else step_experts(a)
+        return step_formats(a) if a.expert_format != "none" else step_experts(a)
     if a.step == "step":
         return step_forward(a)
     for name, limit in STEP_LIMITS.items():        # a fresh process per step, each under its own limit; a failure ends the run
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(a.reps), "--layers", str(a.layers),
-               "--depth", str(a.depth), "--buckets", ",".join(map(str, a.buckets)), "--expert-format", a.expert_format]
+               "--depth", str(a.depth), "--buckets", ",".join(map(str, a.buckets)), "--expert-format", a.expert_format, "--dtype", a.dtype]
         rc = subprocess.run(cmd).returncode
         if rc != 0:
             raise SystemExit(f"step {name} ended with status {rc}; nothing more is started")
