@@ -741,6 +741,28 @@ int samd_moe_gate_up_silu_i4(const void *d_h, const void *d_Wgu4, const void *d_
                              int32_t top_k, void *d_act, int32_t dtype, void *stream);
 int samd_moe_down_combine_i4(const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
                              int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream);
+/* The same two expert launches over block-scaled FP8 experts (the official Qwen3-MoE FP8 checkpoints): OCP e4m3fn codes q with one fp32
+ * scale s per 128 x 128 block.  The numeric contract is samd_hip/fp8.py's: W[n][k] = float(q[n][k]) * s[n / 128][k / 128], s finite and
+ * positive; W is never formed: out = sum_b s_b * (sum_{k in block b} A[m][k] * q[n][k]), the inner sum an fp32 MFMA accumulation over the
+ * block's 128 k with q widened exactly, the outer step ONE fp32 FMA per accumulator and block (acc = fma(acc_blk, s_b, acc)) in ascending
+ * block order; the epilogues' roundings are unchanged.  Activations stay in the model dtype (weight-only).  Routing, the workspace,
+ * samd_moe_route / samd_moe_lists and the combine are the calls above; shapes, grids and errors are those of the _f4 calls, with hidden and
+ * moe_inter <= 16384 (the tile's scales are staged in 1 KiB of LDS); both are capturable.
+ *   d_Wgu8 / d_Wdown8      ONE buffer per fused tensor (samd_hip/moe.py: pack_experts_fp8), the same for both model dtypes.  First the codes:
+ *                          the E experts laid end to end as ONE matrix of E * N rows in samd_gemm_pack_f8's layout (samd_gemm_pack_f8 with
+ *                          N := E * N; N = 2 * moe_inter, K = hidden for gate|up; N = hidden, K = moe_inter for down): E * N * K bytes,
+ *                          expert e's tile t being tile e * N / 128 + t; for gate|up the rows are permuted BEFORE packing exactly as for the
+ *                          _f4 call.  Then, at the next multiple of 256 bytes (E * N * K itself for every shape served), an fp32 table
+ *                          [E * N / 64][K / 128]: one scale per (64 PACKED rows, 128 k), so that the 16 columns of a wave share one scale per
+ *                          k block.  Waves 0-3 of gate|up tile t hold gate rows 64 t .. (the scales of row-block t / 2 of gate), waves 4-7
+ *                          the up rows I + 64 t .. (row-block (I + 64 t) / 128); for down the two halves of a tile repeat one row of scales.
+ *                          E * (N * K + N / 64 * K / 128 * 4) bytes in all.
+ *   samd_moe_gate_up_silu_f8   as samd_moe_gate_up_silu.
+ *   samd_moe_down_combine_f8   as samd_moe_down_combine: the 8-bit down launch, then the same combine kernel. */
+int samd_moe_gate_up_silu_f8(const void *d_h, const void *d_Wgu8, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
+                             int32_t top_k, void *d_act, int32_t dtype, void *stream);
+int samd_moe_down_combine_f8(const void *d_act, const void *d_Wdown8, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                             int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream);
 
 /* ---- scripted verifier (tests, smoke and bench only): replaces the LM arg-max of every draft node by
  * the next token of a target stream while the node's context (committed history + root->node path) is a

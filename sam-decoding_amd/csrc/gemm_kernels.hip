@@ -2870,3 +2870,278 @@ int samd_moe_down_combine_i4(const void *d_act, const void *d_Wdown4, const int3
 }
 
 }  // extern "C"
+
+// ================================================================================================
+// Mixture-of-experts MLP with block-scaled FP8 experts (OCP e4m3fn codes, one fp32 scale per 128 x 128 block: the official Qwen3-MoE FP8
+// checkpoints' weight / weight_scale_inv): the gathered expert GEMMs of moe_expert_gemm over k_gemm_skinny_f8's 8-bit weight stream.
+//   NUMERIC CONTRACT (samd_hip/fp8.py): W[n][k] = float(q[n][k]) * s[n / 128][k / 128], s fp32, finite, positive.  W is never formed:
+//   out = sum_b s_b * (sum_{k in block b} A[m][k] * q[n][k]) -- the inner sum an fp32 MFMA accumulation over the block's 128 k with q widened
+//   exactly (F8Widen, scale 1), the outer step ONE fp32 FMA per accumulator and block (acc = fma(acc_blk, s_b, acc)), blocks in ascending
+//   order: 4 * RT FMAs per lane and block.  Nothing can overflow the model dtype on the way; the epilogues' roundings are unchanged.
+//   samd_moe_gate_up_silu_f8 / samd_moe_down_combine_f8: the fixed grid (N / 128, min(E, rows_pad * top_k)), the early exit of slots
+//   >= ws[0], the list in static LDS, the gathered LDS-DMA A tile (srow), the counted waits with in-out load destinations, both epilogues
+//   (HF's roundings; rows >= cnt not stored) and k_moe_combine are moe_expert_gemm's; the weight side is k_gemm_skinny_f8's: 32 KiB per
+//   (128-column tile, 256-k chunk), four hand-issued nt 16-byte loads per thread and chunk.  No split-K, no atomics: a row's output has the
+//   same bits whatever shares the launch.  A function of its own: the other expert kernels are left textually alone.
+//   PACKED BUFFER (samd_hip/moe.py: pack_experts_fp8), one per fused tensor: the codes of the E experts laid end to end as ONE matrix of
+//   E * N rows in samd_gemm_pack_f8's layout (expert e's tile t is global tile T = e * N / 128 + t, chunk c at (T * K / 256 + c) * 32768
+//   bytes; gate|up rows permuted before packing by gate_up_tile_order), then, at the next multiple of 256 bytes, an fp32 table
+//   [E * N / 64][K / 128]: one scale per (64 packed rows, 128 k), so that a wave's 16 columns share one scale per k block -- waves 0-3 of
+//   tile T read row 2 T, waves 4-7 row 2 T + 1 (gate|up: gate rows 64 t.. = scale row-block t / 2, up rows I + 64 t.. = row-block
+//   (I + 64 t) / 128; down: both halves repeat the tile's one scale).
+//   THE SCALES never are a dependent global load inside a phase: the tile's 2 * K / 128 scales are staged ONCE into static LDS beside
+//   the list, before the stream starts; a phase reads its two (chunk c = k blocks 2 c, 2 c + 1) as one wave-uniform 8-byte LDS read.
+//   DEPTH per row tile, as k_gemm_skinny_f8 chose it: 4 chunks of 32 KiB in flight = the model-dtype expert kernel's 128 KiB per workgroup
+//   (2 x 64 KiB) and its 64 weight VGPRs, where the 160 KiB of LDS allows DEPTH + 1 A buffers of R * 512 bytes: 16 rows 40 KiB, 32 rows
+//   80 KiB, 48 rows 120 KiB; at 64 rows 5 buffers would be the whole 160 KiB, so that tile keeps 3 chunks in flight (4 buffers, 128 KiB,
+//   48 weight VGPRs).  Static LDS: the list (256 bytes) + the scales (1 KiB: K <= 16384), 2 KiB as laid out.  With it only the 16-row
+//   tile fits two workgroups per CU, and the launch bounds say so: 2 there (128 VGPRs allowed, 112 used: 64 weight + 2 x 4 accumulators +
+//   8 A + 8 widened + addresses) and 1 for the others (136 / 158 / 166 VGPRs at 32 / 48 / 64 rows; at 64: 48 weight + 2 x 16
+//   accumulators + 32 A + 8 widened).  No instantiation has scratch (tests/test_moe_fp8_cpu.py).  (DEPTH - 1) * PC <= 63: 15, 18, 21, 16.
+//   An expert's stream is often SHORTER than the depth; the skipped prologue loads leave their in-out destinations as they are.
+//   The table is not swept on a GPU; profiles/moe_experts_fp8.md says what was measured.
+// ================================================================================================
+#define MOE8_MAX_KB 128                // k blocks of 128 per row: K <= 16384
+template <int RT> struct Moe8Depth { static constexpr int value = RT == 4 ? 3 : 4; };
+
+template <typename TT, int RT, bool GU>
+__device__ __forceinline__ void moe8_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8, const float *__restrict__ stab,
+                                                 const int *__restrict__ ws, typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
+    typedef typename TT::elem E;
+    constexpr int DEPTH = Moe8Depth<RT>::value;
+    constexpr int R = 16 * RT;
+    constexpr int NT = 64 * GEMM_WAVES;
+    constexpr int XV = (R * 32) / NT;
+    constexpr int NB = DEPTH + 1;
+    constexpr int PC = 4 + XV;                     // memory operations per thread and chunk: 4 weight loads + the A staging
+    constexpr size_t WCH = 32768, WU = 8192;       // bytes of one (tile, chunk) block; of one b row inside it
+    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
+    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
+    __shared__ int lst[MOE_MAX_ROWS];
+    __shared__ __attribute__((aligned(8))) float scl[2][MOE8_MAX_KB];
+
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
+    const int slot_a = blockIdx.y;
+    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts
+    const int expert = ws[MOE_WS_ACTIVE + slot_a];
+    int cnt = ws[MOE_WS_COUNT + slot_a];
+    cnt = cnt > R ? R : cnt;
+    const size_t tile = (size_t)expert * (N / GEMM_COLS) + blockIdx.x;
+    if (tid < MOE_MAX_ROWS) lst[tid] = ws[MOE_WS_LIST + MOE_MAX_ROWS * slot_a + (tid < cnt ? tid : 0)];
+    // the tile's scales: rows 2 tile (waves 0-3) and 2 tile + 1 (waves 4-7) of the table are contiguous, 2 * K / 128 floats
+    if (tid < 4 * n_chunks) scl[tid >= 2 * n_chunks][tid >= 2 * n_chunks ? tid - 2 * n_chunks : tid] = stab[tile * 4 * n_chunks + tid];
+    __syncthreads();
+    // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
+    int srow[XV];
+#pragma unroll
+    for (int i = 0; i < XV; i++) { const int p = lst[(tid >> 5) + 16 * i]; srow[i] = GU ? p / top_k : p; }
+
+    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    const char *wtile = reinterpret_cast<const char *>(W8) + tile * n_chunks * WCH;
+    const uint32_t wlane = (uint32_t)tid * 16;
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
+    const float *sw = scl[w >> 2];                 // this wave's scales, one per k block
+
+    floatx4 acc[RT];
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
+    u32x4 wr[DEPTH][4];
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) asm volatile("" : "=v"(wr[d][b]));
+    auto load_wb = [&](u32x4 (&dst)[4], int c, int b) {
+        const char *p = wtile + (size_t)c * WCH;
+        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[b]) : "v"(wlane), "s"(p + WU * b) : "memory");
+    };
+    auto stage_xi = [&](int c, int buf, int i) {
+        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
+        const E *src = A + (size_t)srow[i] * K + (size_t)c * GEMM_KC + 8 * unit;
+        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        asm volatile("" ::: "memory");
+    };
+    auto load_w = [&](u32x4 (&dst)[4], int c) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) load_wb(dst, c, b);
+    };
+    auto stage_x = [&](int c, int buf) {
+#pragma unroll
+        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
+    };
+    auto phase = [&](u32x4 (&cur)[4], int c, int buf) {
+        gemm_wait_younger<DEPTH, PC>(n_chunks - 1 - c);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
+        const float2 s2 = *reinterpret_cast<const float2 *>(sw + 2 * c);      // k blocks 2 c and 2 c + 1: an LDS read, ahead of their use
+        floatx4 blk[RT];
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            if ((b & 1) == 0) {
+#pragma unroll
+                for (int mt = 0; mt < RT; mt++) blk[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+            }
+            const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
+            u32x4 r[RT][2];
+            gemm_f4_read_a<RT>(r, a0, a1);
+            // re-defined behind the counted wait (volatile asm keeps its order): no conversion can be scheduled above it
+            asm volatile("" : "+v"(cur[b]) : : "memory");
+            const auto lo = F8Widen<TT>::cvt(cur[b][0], cur[b][1]), hi = F8Widen<TT>::cvt(cur[b][2], cur[b][3]);
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++) {
+                blk[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, blk[mt]);
+                blk[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, blk[mt]);
+            }
+            if (b & 1) {                                       // a 128-k block is complete: one fp32 FMA per accumulator
+                const float s = b == 1 ? s2.x : s2.y;
+#pragma unroll
+                for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                    for (int q = 0; q < 4; q++) acc[mt][q] = __builtin_fmaf(blk[mt][q], s, acc[mt][q]);
+            }
+            if (RT >= 3 && c + DEPTH < n_chunks) {             // 48 / 64 rows: refill per k block (see k_gemm_skinny)
+                load_wb(cur, c + DEPTH, b);
+                if (b < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, b);
+            }
+        }
+        if (RT < 3 && c + DEPTH < n_chunks) { load_w(cur, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
+    };
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++)
+        if (d < n_chunks) { load_w(wr[d], d); stage_x(d, d); }
+    int buf = 0;
+    for (int c = 0; c < n_chunks; c += DEPTH) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++)
+            if (c + d < n_chunks) { phase(wr[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+    }
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n; the block scales went in with the FMAs
+    if constexpr (GU) {
+        float *ex = reinterpret_cast<float *>(gemm_lds);            // [R][64] up values; the A tiles are dead by now
+        __syncthreads();
+        if (w >= 4) {
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) ex[(16 * mt + 4 * g + r) * 64 + 16 * (w - 4) + n] = acc[mt][r];
+        }
+        __syncthreads();
+        if (w < 4) {
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int m = 16 * mt + 4 * g + r;
+                    if (m >= cnt) continue;
+                    // the roundings of HF's act_fn(gate) * up in the model dtype (same as moe_expert_gemm)
+                    const float gf = (float)(E)acc[mt][r], uf = (float)(E)ex[m * 64 + 16 * w + n];
+                    const E sv = (E)(gf / (1.f + __expf(-gf)));
+                    out[(size_t)lst[m] * (N / 2) + blockIdx.x * 64 + 16 * w + n] = (E)((float)sv * uf);
+                }
+        }
+    } else {
+#pragma unroll
+        for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int m = 16 * mt + 4 * g + r;
+                if (m < cnt) out[(size_t)lst[m] * N + n0 + n] = (E)acc[mt][r];
+            }
+    }
+}
+
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, RT == 1 ? 2 : 1) void k_moe8_gate_up_silu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W8,
+                                                                                      const float *__restrict__ stab, const int *__restrict__ ws,
+                                                                                      typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
+    moe8_expert_gemm<TT, RT, true>(h, W8, stab, ws, act, K, N, n_chunks, top_k);
+}
+
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, RT == 1 ? 2 : 1) void k_moe8_down(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W8,
+                                                                              const float *__restrict__ stab, const int *__restrict__ ws,
+                                                                              typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
+    moe8_expert_gemm<TT, RT, false>(act, W8, stab, ws, y, K, N, n_chunks, top_k);
+}
+
+// the scale table's byte offset inside a packed buffer of `rows` = E * N rows: after the codes, at a multiple of 256 (samd_hip/fp8.py:
+// block_scale_offset is the same formula)
+static inline size_t moe8_scale_offset(size_t rows, size_t K) { return (rows * K + 255) / 256 * 256; }
+
+template <typename TT, int RT, bool GU>
+static hipError_t moe8_gemm_launch(dim3 grid, hipStream_t st, const void *A, const void *W8, const float *stab, const int *ws, void *out, int K, int N, int top_k) {
+    typedef typename TT::elem E;
+    constexpr int lds = (Moe8Depth<RT>::value + 1) * 16 * RT * GEMM_KC * 2;
+    if constexpr (GU) {
+        if constexpr (lds > 65536) {
+            static unsigned long long done = 0ull;                 // per-device (samd_common.h)
+            const hipError_t attr = samd_reserve_lds((const void *)k_moe8_gate_up_silu<TT, RT>, lds, &done);
+            if (attr != hipSuccess) return attr;
+        }
+        hipLaunchKernelGGL((k_moe8_gate_up_silu<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const unsigned char *)W8, stab, ws, (E *)out, K, N,
+                           K / GEMM_KC, top_k);
+    } else {
+        if constexpr (lds > 65536) {
+            static unsigned long long done = 0ull;
+            const hipError_t attr = samd_reserve_lds((const void *)k_moe8_down<TT, RT>, lds, &done);
+            if (attr != hipSuccess) return attr;
+        }
+        hipLaunchKernelGGL((k_moe8_down<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const unsigned char *)W8, stab, ws, (E *)out, K, N,
+                           K / GEMM_KC, top_k);
+    }
+    return hipSuccess;
+}
+
+template <bool GU>
+static hipError_t moe8_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W8, size_t rows, const int *ws, void *out, int K, int N, int top_k) {
+    const float *stab = reinterpret_cast<const float *>(reinterpret_cast<const char *>(W8) + moe8_scale_offset(rows, (size_t)K));
+#define GO(TT, RT) return moe8_gemm_launch<TT, RT, GU>(grid, st, A, W8, stab, ws, out, K, N, top_k)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
+}
+
+#define MOE8_SHAPE_MSG "unsupported shape (rows 16/32/48/64, hidden %% 256 == 0, moe_intermediate %% 256 == 0, both <= 16384, experts <= 256, top-k <= 8, f16/bf16) or null pointer"
+
+extern "C" {
+
+int samd_moe_gate_up_silu_f8(const void *d_h, const void *d_Wgu8, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
+                             int32_t top_k, void *d_act, int32_t dtype, void *stream) {
+    if (!d_h || !d_Wgu8 || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype) || hidden > 128 * MOE8_MAX_KB ||
+        moe_inter > 128 * MOE8_MAX_KB) {
+        samd_set_error("samd_moe_gate_up_silu_f8: " MOE8_SHAPE_MSG); return SAMD_E_INVALID;
+    }
+    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const hipError_t e = moe8_gemm_dispatch<true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu8,
+                                                  (size_t)n_experts * 2 * moe_inter, (const int *)d_ws, d_act, hidden, 2 * moe_inter, top_k);
+    if (e != hipSuccess) { samd_set_error("samd_moe_gate_up_silu_f8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_moe_down_combine_f8(const void *d_act, const void *d_Wdown8, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                             int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream) {
+    if (!d_act || !d_Wdown8 || !d_topk_idx || !d_topk_w || !d_n || !d_ws || !d_out || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype) ||
+        hidden > 128 * MOE8_MAX_KB || moe_inter > 128 * MOE8_MAX_KB) {
+        samd_set_error("samd_moe_down_combine_f8: " MOE8_SHAPE_MSG); return SAMD_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    void *y = (char *)d_ws + MOE_WS_Y_OFF;
+    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const hipError_t e = moe8_gemm_dispatch<false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown8, (size_t)n_experts * hidden,
+                                                   (const int *)d_ws, y, moe_inter, hidden, top_k);
+    if (e != hipSuccess) { samd_set_error("samd_moe_down_combine_f8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
+    if (dtype == SAMD_F16)
+        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
+    else
+        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+}  // extern "C"

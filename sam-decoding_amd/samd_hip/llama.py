@@ -157,11 +157,16 @@ class LlamaRunner:
         # means the four dense projections and stays rejected for models with sparse layers
         # expert_format "int4g128": the experts as AWQ / GPTQ INT4 (codes + "_z" zero points + "_s" scales in the model dtype: the _z / _s keys
         # tell them from MXFP4's "_scale"); INT4 expert tensors make the runner "int4g128" by themselves
+        # expert_format "fp8b128": the experts as block-scaled FP8 (float8_e4m3fn codes, or their bytes, + "_sinv" fp32 scales per 128 x 128
+        # block: the _sinv keys tell them from the others); such tensors make the runner "fp8b128" by themselves
         sparse_l = [l for l in weights["layers"] if "experts_gu" in l]
         experts_i4 = [any(k in l for k in ("experts_gu_z", "experts_gu_s", "experts_down_z", "experts_down_s")) for l in sparse_l]
-        experts4 = [not i4e and (MOE.is_4bit(l["experts_gu"]) or MOE.is_4bit(l["experts_down"])) for l, i4e in zip(sparse_l, experts_i4)]
-        self.expert_format = MOE.resolve_expert_format(expert_format, any(experts4), shape.moe,
-                                                       carries_int4=any(experts_i4))                 # (before any device work, as the next)
+        experts_f8 = [any(k in l for k in ("experts_gu_sinv", "experts_down_sinv")) or F8.is_fp8_dtype(l["experts_gu"].dtype)
+                      or F8.is_fp8_dtype(l["experts_down"].dtype) for l in sparse_l]
+        experts4 = [not i4e and not f8e and (MOE.is_4bit(l["experts_gu"]) or MOE.is_4bit(l["experts_down"]))
+                    for l, i4e, f8e in zip(sparse_l, experts_i4, experts_f8)]
+        self.expert_format = MOE.resolve_expert_format(expert_format, any(experts4), shape.moe, carries_int4=any(experts_i4),
+                                                       carries_fp8=any(experts_f8))                  # (before any device work, as the next)
         if shape.moe:
             MOE.reject_unsupported(_weight_format(weight_format, weights, dtype), native_gemm, draft_head)
         if any(experts4):
@@ -180,6 +185,14 @@ class LlamaRunner:
                 if "experts_gu" in l:
                     MOE.check_int4_experts((l["experts_gu"], l.get("experts_gu_z"), l.get("experts_gu_s")),
                                            (l["experts_down"], l.get("experts_down_z"), l.get("experts_down_s")), dtype, f"layer {i} experts")
+        if any(experts_f8):
+            if not all(experts_f8):
+                raise SamdError(f"a mix of block-scaled FP8 and other sparse layers ({sum(experts_f8)} of {len(experts_f8)} carry FP8 experts): "
+                                "the runner takes the experts of all sparse layers in one format")
+            for i, l in enumerate(weights["layers"]):
+                if "experts_gu" in l:
+                    MOE.check_fp8_experts((l["experts_gu"], l.get("experts_gu_sinv")), (l["experts_down"], l.get("experts_down_sinv")),
+                                          f"layer {i} experts")
         self.draft_head = bool(draft_head)                       # the decoder is an EAGLE head (forward_rows)
         require_gpu()
         self.shape, self.dtype, self.device = shape, dtype, torch.device(device)
@@ -374,7 +387,7 @@ class LlamaRunner:
                     and not moe)
             if sparse:
                 # the experts packed once (per expert the 128-column tiles of the streaming GEMM, gate | up interleaved); no row-major copy stays
-                gu_cols = s.hidden // 2 if MOE.is_4bit(l["experts_gu"]) else s.hidden
+                gu_cols = s.hidden // 2 if MOE.is_4bit(l["experts_gu"]) and "experts_gu_sinv" not in l else s.hidden
                 if tuple(l["router"].shape) != (s.n_experts, s.hidden) or tuple(l["experts_gu"].shape) != (s.n_experts, 2 * s.moe_inter, gu_cols):
                     raise SamdError(f"sparse layer weights of shapes {tuple(l['router'].shape)}, {tuple(l['experts_gu'].shape)} do not match the shape")
                 if self.expert_format == "mxfp4":
@@ -400,6 +413,18 @@ class LlamaRunner:
                     for k, t in zip(gkeys + dkeys, gu3 + dn3):
                         l[k] = torch.empty(t.shape, dtype=t.dtype, device="meta")
                     del gu3, dn3
+                elif self.expert_format == "fp8b128":
+                    # the experts as e4m3fn codes + one fp32 scale per 128 x 128 block (the checkpoint's own, already checked, or quantised
+                    # here), packed once (the buffer serves both model dtypes); only shapes stay
+                    gkeys, dkeys = ("experts_gu", "experts_gu_sinv"), ("experts_down", "experts_down_sinv")
+                    if "experts_gu_sinv" in l:
+                        gu2, dn2 = (tuple(l[k].to(self.device).contiguous() for k in ks) for ks in (gkeys, dkeys))
+                    else:
+                        gu2, dn2 = MOE.quantize_experts_fp8(l["experts_gu"], l["experts_down"], f"layer {len(layers)} experts")
+                    lp["moe_gu"], lp["moe_down"] = MOE.pack_experts_fp8(gu2, dn2)
+                    for k, t in zip(gkeys + dkeys, gu2 + dn2):
+                        l[k] = torch.empty(t.shape, dtype=torch.float8_e4m3fn if t.dtype == torch.uint8 else t.dtype, device="meta")
+                    del gu2, dn2
                 else:
                     lp["moe_gu"], lp["moe_down"] = MOE.pack_experts(l["experts_gu"], l["experts_down"])
                     for k in ("experts_gu", "experts_down"):
@@ -611,7 +636,16 @@ class LlamaRunner:
         models): they are dequantised ONCE at import by int4.dequantize_groups to the model dtype -- exactly the weights an INT4 launch would
         multiply by, one rounding -- and run on the model-dtype kernels, at 16 bits instead of 4.25 per weight of those projections
         (Qwen3-30B-A3B: 48 layers x 37.7 M attention weights = 3.6 GB instead of 0.96 GB; the experts, 97 % of the model, stay 4-bit).
-        Streaming them through samd_gemm_skinny_i4 inside a mixture-of-experts stack is the follow-up.  share_weights does not apply to
+        Streaming them through samd_gemm_skinny_i4 inside a mixture-of-experts stack is the follow-up.
+        "fp8b128" quantises the experts per 128 x 128 block on load (uncalibrated, for benches and tests).  A block-scaled FP8 Qwen3-MoE
+        checkpoint (Qwen3-30B-A3B-FP8: float8_e4m3fn `weight` + fp32 `weight_scale_inv`, weight_block_size [128, 128]) holds, in every sparse
+        layer, transformers' fused FP8Experts (`mlp.experts.gate_up_proj` + `gate_up_proj_scale_inv`, `down_proj` + `down_proj_scale_inv`)
+        or per-expert modules (`mlp.experts.{e}.gate_proj.weight` + `weight_scale_inv`): the codes and scales are imported as they are
+        (samd_hip/fp8.py has the contract and the rejections, by tensor name) and the runner is "fp8b128" by itself, weight_format None.
+        The module's FP8 attention and dense-MLP projections (block-scaled, or per row / per tensor `weight_scale`) are dequantised ONCE at
+        import to rne_dtype(fl32(float(q) * s)) and run on the model-dtype kernels; the router must be a plain `weight`.  Weight-only: the
+        checkpoint's dynamic activation quantisation is not reproduced.  FP8 projections beside non-FP8 experts stay rejected.
+        share_weights does not apply to
         dequantised projections (there is no HF `weight` to re-point); INT4 attention beside model-dtype or MXFP4 experts stays rejected."""
         weight_format = _env_weight_format(weight_format)
         m = lm.model
@@ -620,7 +654,12 @@ class LlamaRunner:
         linears = [(f"layers.{i}.{a}.{b}", getattr(getattr(lyr, a), b)) for i, lyr in enumerate(m.layers) for a, b in parts
                    if hasattr(getattr(lyr, a), b)]               # (a sparse layer's MLP has no gate / up / down projections of its own)
         ckpt_i4 = I4.checkpoint_is_int4(linears)                 # AWQ / GPTQ modules (qweight / qzeros / scales, no `weight`)
-        ckpt_f8 = (not ckpt_i4) and F8.checkpoint_is_fp8(linears)
+        # a module with block-scaled FP8 EXPERTS (the official Qwen3-MoE FP8 checkpoints) is not a weight_format "fp8" one: its FP8 attention
+        # and dense-MLP projections are dequantised once at import (the docstring).  Decided before checkpoint_is_fp8, which rejects block scales
+        layer_f8 = [cls._hf_experts_are_fp8(lyr, i) for i, lyr in enumerate(m.layers)]
+        moe_f8_dense = any(layer_f8)
+        qcfg8 = getattr(getattr(lm, "config", None), "quantization_config", None)
+        ckpt_f8 = (not ckpt_i4) and (not moe_f8_dense) and F8.checkpoint_is_fp8(linears)
         ckpt_f4 = (not ckpt_i4) and MX.checkpoint_is_mxfp4(linears)
         qcfg = I4.quant_config(getattr(lm, "config", None))
         if F8.is_fp8_dtype(lm.lm_head.weight.dtype) or F8.is_fp8_dtype(m.embed_tokens.weight.dtype):
@@ -646,9 +685,25 @@ class LlamaRunner:
                                    kw.get("draft_head", False))
         # 4-bit experts: decided and checked on the module's own tensors, before anything moves to the device (the runner resolves the
         # format again from the weights it is given)
-        experts4 = [not i4e and cls._hf_experts_are_4bit(lyr, i)
+        experts4 = [not i4e and not layer_f8[i] and cls._hf_experts_are_4bit(lyr, i)
                     for (i, lyr), i4e in zip(((i, lyr) for i, lyr in enumerate(m.layers) if sparse[i]), experts_i4)]
-        MOE.resolve_expert_format(expert_format, any(experts4), any(sparse) or shape.moe, carries_int4=any(experts_i4))
+        experts_f8 = [layer_f8[i] for i in range(len(m.layers)) if sparse[i]]
+        MOE.resolve_expert_format(expert_format, any(experts4), any(sparse) or shape.moe, carries_int4=any(experts_i4), carries_fp8=any(experts_f8))
+        if any(experts_f8):
+            if not all(experts_f8):
+                plain = [i for i, sp in enumerate(sparse) if sp and not layer_f8[i]][:3]
+                raise SamdError(f"a mix of block-scaled FP8 and other sparse layers ({sum(experts_f8)} of {len(experts_f8)} carry FP8 experts; "
+                                f"e.g. layers {plain} do not): the runner takes the experts of all sparse layers in one format")
+            for i, lyr in enumerate(m.layers):
+                if not sparse[i]:
+                    continue
+                ex = lyr.mlp.experts
+                n_ex = ex.gate_up_proj.shape[0] if hasattr(ex, "gate_up_proj") else len(ex)
+                if n_ex != shape.n_experts:
+                    raise SamdError(f"layers.{i}.mlp.experts: {n_ex} experts, the config says num_experts = {shape.n_experts}")
+                gate = getattr(lyr.mlp, "gate", None)
+                if gate is None or getattr(gate, "weight", None) is None or F8.is_fp8_dtype(gate.weight.dtype):
+                    raise SamdError(f"layers.{i}.mlp.gate: an FP8 router is not supported: the router stays a plain `weight` in the model dtype")
         if any(experts_i4) and not all(experts_i4):
             plain = [i for i, sp in enumerate(sparse) if sp and not cls._hf_experts_are_int4(m.layers[i], i)][:3]
             raise SamdError(f"a mix of INT4 and other sparse layers ({sum(experts_i4)} of {len(experts_i4)} carry INT4 experts; e.g. layers "
@@ -683,14 +738,16 @@ class LlamaRunner:
 
         def lin_w(mod, name):
             """a projection's weight; an INT4 module's (a module with sparse layers only) dequantised: rne_dtype((q - z) * s), one rounding"""
+            if moe_f8_dense and F8.is_fp8_dtype(mod.weight.dtype):   # beside FP8 experts: rne_dtype(fl32(float(q) * s)), one rounding
+                return F8.linear_fp8_dequantized(mod, name, qcfg8).to(dtype)
             if not I4.is_int4_module(mod):
                 return mod.weight
             q, z, sc = I4.linear_int4(mod, name, config=qcfg)
             return I4.dequantize_groups(q, z, I4.as_scales(sc, dtype, name)).to(dtype)
 
         def fuse(linears, names=None):
-            if moe_i4_dense:
-                return get(torch.cat([lin_w(l, n) for l, n in zip(linears, names)], dim=0))
+            if moe_i4_dense or (moe_f8_dense and any(F8.is_fp8_dtype(l.weight.dtype) for l in linears)):
+                return get(torch.cat([lin_w(l, n).to(dtype) for l, n in zip(linears, names)], dim=0))
             ws = [l.weight for l in linears]
             cat = get(torch.cat(ws, dim=0))
             if share and all(w.device == cat.device and w.dtype == cat.dtype for w in ws):
@@ -730,6 +787,12 @@ class LlamaRunner:
                 continue
             li = len(layers)
             qkv_names, o_name = [f"layers.{li}.self_attn.{x}" for x in ("q_proj", "k_proj", "v_proj")], f"layers.{li}.self_attn.o_proj"
+            if sparse[li] and any(experts_f8):                   # router + the experts' e4m3fn codes and block scales, as they are
+                layers.append(dict(
+                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
+                    **MOE.import_experts_fp8(f.experts, f"layers.{li}.mlp.experts", dev, qcfg8),
+                    ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
+                continue
             if sparse[li] and any(experts_i4):                   # router + the experts' canonical (q, z, s), fused and stacked
                 layers.append(dict(
                     wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
@@ -774,6 +837,29 @@ class LlamaRunner:
         return gu
 
     @classmethod
+    def _hf_experts_are_fp8(cls, lyr, i):
+        """does layer i hold FP8 experts -- the fused form (transformers' FP8Experts: float8 gate_up_proj and down_proj) or an indexable
+        `mlp.experts` of modules whose gate_proj / up_proj / down_proj weights are all float8?  All: True; none (or no experts): False; some
+        only: raises by name"""
+        ex = getattr(getattr(lyr, "mlp", None), "experts", None)
+        if ex is None:
+            return False
+        if hasattr(ex, "gate_up_proj"):
+            kinds = [(f"layers.{i}.mlp.experts.{p}", F8.is_fp8_dtype(getattr(ex, p).dtype)) for p in ("gate_up_proj", "down_proj")
+                     if getattr(ex, p, None) is not None]
+        elif hasattr(ex, "__len__") and hasattr(ex, "__getitem__"):
+            kinds = [(f"layers.{i}.mlp.experts.{e}.{p}", F8.is_fp8_dtype(getattr(ex[e], p).weight.dtype))
+                     for e in range(len(ex)) for p in MOE.INT4_EXPERT_PROJECTIONS if getattr(getattr(ex[e], p, None), "weight", None) is not None]
+        else:
+            return False
+        n8 = sum(k for _, k in kinds)
+        if 0 < n8 < len(kinds):
+            plain = [n for n, k in kinds if not k][:3]
+            raise SamdError(f"layers.{i}.mlp.experts: a mix of FP8 and other expert tensors ({n8} of {len(kinds)} are FP8; e.g. "
+                            f"{', '.join(plain)} are not): FP8 experts need every expert tensor float8_e4m3fn")
+        return n8 > 0
+
+    @classmethod
     def _hf_experts_are_int4(cls, lyr, i):
         """does layer i hold per-expert INT4 (AWQ / GPTQ) modules -- an indexable `mlp.experts` of modules with gate_proj / up_proj / down_proj
         that are all INT4 (int4.is_int4_module)?  All: True; none (or the fused form, or no experts): False; some experts or some of the
@@ -812,7 +898,7 @@ class LlamaRunner:
             # (the same holds for an MXFP4 projection -- a float4_e2m1fn_x2 or uint8 weight -- and its e8m0 weight_scale)
             skip = {f"{n[:-len('.weight')]}.{sc}" for n, p in lyr.named_parameters()
                     if n.endswith(".weight") and (F8.is_fp8_dtype(p.dtype) or _is_f4_tensor(p))
-                    for sc in ("weight_scale", "input_scale")}
+                    for sc in ("weight_scale", "input_scale", "weight_scale_inv")}
             # the block scales of 4-bit expert tensors (samd_hip/moe.py), which the runner reads; beside plain experts they are extra
             params = dict(lyr.named_parameters())
             # an AWQ / GPTQ projection holds qweight / qzeros / scales (/ g_idx) and maybe a bias, as buffers or parameters, in place of a
@@ -829,6 +915,15 @@ class LlamaRunner:
                 skip |= set(MOE.EXPERT_SCALE_PARAMS)
             # per-expert INT4 modules (mlp.experts.{e}.gate_proj ...; their tensors are buffers) count as the two fused expert tensors; a
             # bias of one of them stays in the set and raises by name below
+            # FP8 experts (samd_hip/moe.py): the fused form's two scale tensors are read; the per-expert form (mlp.experts.{e}.gate_proj.weight
+            # + weight_scale_inv, skipped above) counts as the two fused expert tensors
+            if cls._hf_experts_are_fp8(lyr, i):
+                skip |= set(MOE.FP8_EXPERT_SCALE_PARAMS)
+                if not hasattr(lyr.mlp.experts, "gate_up_proj"):
+                    for e in range(len(lyr.mlp.experts)):
+                        for pn in MOE.INT4_EXPERT_PROJECTIONS:
+                            params.pop(f"mlp.experts.{e}.{pn}.weight", None)
+                    params.update({n: None for n in MOE.SPARSE_MLP_PARAMS[1:]})
             if cls._hf_experts_are_int4(lyr, i):
                 for e in range(len(lyr.mlp.experts)):
                     for pn in MOE.INT4_EXPERT_PROJECTIONS:
@@ -909,7 +1004,9 @@ class LlamaRunner:
         (an FP8 projection: one byte per weight + its fp32 column scales; an MXFP4 projection: half a byte per weight + one scale byte per 32; an
         INT4 projection: half a byte per weight + 4 bytes of scale and zero point per 128).
         A sparse (mixture-of-experts) layer counts `experts` of its experts in the format they are held in (MXFP4 experts: elements + block
-        scales; default: num_experts_per_tok, what the 1-row step streams; a wider step streams the experts its rows are routed to, at most
+        scales; block-scaled FP8 experts: one byte per weight + one fp32 scale per 128 x 128 block -- the packed table repeats each scale for
+        the two 64-row halves of its block, another 4 bytes per 16384 weights;
+        default: num_experts_per_tok, what the 1-row step streams; a wider step streams the experts its rows are routed to, at most
         all of them: pass experts=shape.n_experts for that bound)."""
         n_act = self.shape.top_k if experts is None else int(experts)
         nb = lambda t: t.numel() * t.element_size() if t.dim() != 3 else t[0].numel() * t.element_size() * min(n_act, t.shape[0])

@@ -21,12 +21,22 @@ Qwen3-MoE checkpoint holds an indexable `mlp.experts` of E modules with AWQ / GP
 gate_proj.qweight` ...), which LlamaRunner.from_hf imports through int4.linear_int4; in a raw weights dict: experts_gu uint8 [E, 2 I, H/2],
 experts_gu_z uint8 [E, 2 I, H/128], experts_gu_s model dtype [E, 2 I, H/128], and experts_down / _z / _s likewise with [E, H, I/...] -- the
 _z / _s keys are what tells INT4 from MXFP4 (_scale).  EXPERT_FORMATS stays the pair of the first two formats (callers pin it);
-EXPERT_FORMATS_ALL is what an expert_format is validated against."""
+EXPERT_FORMATS_ALL is the first three (pinned likewise); EXPERT_FORMATS_KNOWN is what an expert_format is validated against.
+
+expert_format "fp8b128" keeps the EXPERTS as block-scaled FP8 (samd_hip/fp8.py: OCP e4m3fn codes, one fp32 scale per 128 x 128 block,
+W = float(q) * s, never formed: one fp32 FMA per accumulator and 128-k block): (q [E, N, K] float8_e4m3fn, s [E, N/128, K/128] fp32) per fused
+tensor -- exactly transformers' FP8Experts (`mlp.experts.gate_up_proj` + `gate_up_proj_scale_inv`, `down_proj` + `down_proj_scale_inv`), the
+form the official Qwen3-MoE FP8 checkpoints load into; per-expert modules (`mlp.experts.{e}.gate_proj.weight` + `weight_scale_inv`, the
+on-disk naming) are taken as well.  In a raw weights dict: experts_gu (float8_e4m3fn or its bytes), experts_gu_sinv, experts_down,
+experts_down_sinv -- the _sinv keys are what tells this format from the others.  Packed by pack_experts_fp8 (codes: samd_gemm_pack_f8 over
+E * N rows; then the fp32 scale table [E * N / 64][K / 128]) and streamed by samd_moe_gate_up_silu_f8 / samd_moe_down_combine_f8.  The
+buffer does not depend on the model dtype."""
 import os
 
 import torch
 
 from . import SamdError, _ptr, check, current_stream, lib, torch_dtype_code
+from . import fp8 as F8
 from . import int4 as I4
 from . import mxfp4 as MX
 
@@ -40,6 +50,9 @@ EXPERT_SCALE_PARAMS = ("mlp.experts.gate_up_proj_scale", "mlp.experts.down_proj_
 # what the experts of the sparse layers may be held in: None = the model dtype
 EXPERT_FORMATS = (None, "mxfp4")
 EXPERT_FORMATS_ALL = EXPERT_FORMATS + ("int4g128",)
+EXPERT_FORMATS_KNOWN = EXPERT_FORMATS_ALL + ("fp8b128",)
+# the scale tensors of transformers' FP8Experts: consumed only beside float8_e4m3fn expert tensors
+FP8_EXPERT_SCALE_PARAMS = ("mlp.experts.gate_up_proj_scale_inv", "mlp.experts.down_proj_scale_inv")
 # the projections of one expert module of an INT4 (AWQ / GPTQ) checkpoint: mlp.experts.{e}.gate_proj / up_proj / down_proj
 INT4_EXPERT_PROJECTIONS = ("gate_proj", "up_proj", "down_proj")
 
@@ -82,20 +95,34 @@ def reject_unsupported(weight_format=None, native_gemm=True, draft_head=False):
         raise SamdError("mixture-of-experts layers are not supported on an EAGLE draft head")
 
 
-def resolve_expert_format(expert_format, carries_4bit, has_sparse, carries_int4=False):
-    """None, "mxfp4" or "int4g128" from the argument (AUTO: env SAMD_EXPERT_FORMAT, for callers that cannot pass one) and from what the
-    weights carry: MXFP4 expert tensors (carries_4bit) make the runner "mxfp4" by themselves, INT4 ones (carries_int4) "int4g128"; any other
-    explicit format against them raises.  Raises before any device work."""
+def _format_error(expert_format):
+    hint = " ('fp8' is weight_format's spelling of per-row FP8; block-scaled FP8 experts are 'fp8b128')" if expert_format == "fp8" else ""
+    return SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS_KNOWN)}{hint}")
+
+
+def resolve_expert_format(expert_format, carries_4bit, has_sparse, carries_int4=False, carries_fp8=False):
+    """None, "mxfp4", "int4g128" or "fp8b128" from the argument (AUTO: env SAMD_EXPERT_FORMAT, for callers that cannot pass one) and from
+    what the weights carry: MXFP4 expert tensors (carries_4bit) make the runner "mxfp4" by themselves, INT4 ones (carries_int4) "int4g128",
+    block-scaled FP8 ones (carries_fp8) "fp8b128"; any other explicit format against them raises.  Raises before any device work."""
     explicit = expert_format is not AUTO
     if not explicit:
         expert_format = os.environ.get("SAMD_EXPERT_FORMAT") or None
-    if expert_format not in EXPERT_FORMATS_ALL:
-        raise SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS_ALL)}")
+    if expert_format not in EXPERT_FORMATS_KNOWN:
+        raise _format_error(expert_format)
     if expert_format is not None and not has_sparse:
         raise SamdError(f"expert_format '{expert_format}' on a model without mixture-of-experts (sparse) layers: it covers the experts only; "
                         "weight_format covers the dense projections")
     if carries_4bit and carries_int4:
         raise SamdError("a mix of MXFP4 and INT4 expert tensors: the runner takes the experts of all sparse layers in one format")
+    if carries_fp8 and (carries_4bit or carries_int4):
+        raise SamdError("a mix of block-scaled FP8 and 4-bit expert tensors: the runner takes the experts of all sparse layers in one format")
+    if carries_fp8:
+        if explicit and expert_format != "fp8b128":
+            raise SamdError(f"the sparse layers carry block-scaled FP8 expert tensors; expert_format={expert_format!r} would need them "
+                            "dequantised or re-quantised (leave it out or pass 'fp8b128')")
+        return "fp8b128"
+    if explicit and expert_format == "fp8b128" and (carries_int4 or carries_4bit):
+        raise SamdError("the sparse layers carry 4-bit expert tensors; expert_format='fp8b128' would need them re-quantised (leave it out)")
     if carries_int4:
         if explicit and expert_format != "int4g128":
             raise SamdError(f"the sparse layers carry INT4 (AWQ / GPTQ) expert tensors; expert_format={expert_format!r} would need them "
@@ -284,6 +311,132 @@ def import_experts_int4(experts, name, dtype, device, config=None):
     return out
 
 
+def _f8_view(t):
+    return t.view(torch.float8_e4m3fn) if t.dtype == torch.uint8 else t
+
+
+def quantize_experts_fp8(gate_up, down, name="experts"):
+    """((q, s) of gate|up, (q, s) of down) of HF's fused expert tensors [E, 2 I, H] / [E, H, I]: fp8.quantize_blocks on every expert
+    (symmetric absmax / 448 per 128 x 128 block, round to nearest even, no calibration: for benches and tests).  q float8_e4m3fn [E, N, K],
+    s fp32 [E, N/128, K/128]."""
+    E, N2, H = gate_up.shape
+    if tuple(down.shape) != (E, H, N2 // 2):
+        raise SamdError(f"{name}: expert tensors of shapes {tuple(gate_up.shape)} and {tuple(down.shape)} do not belong together")
+    out = []
+    for t in (gate_up, down):
+        _, N, K = t.shape
+        if N % F8.BLOCK != 0 or K % F8.BLOCK != 0:
+            raise SamdError(f"{name}: block-scaled FP8 needs N % 128 == 0 and K % 128 == 0, got [{E}, {N}, {K}] experts")
+        q = torch.empty((E, N, K), dtype=torch.float8_e4m3fn, device=t.device)
+        s = torch.empty((E, N // F8.BLOCK, K // F8.BLOCK), dtype=torch.float32, device=t.device)
+        for e in range(E):                                       # (expert by expert: the fp32 temporaries stay small)
+            q[e], s[e] = F8.quantize_blocks(t[e])
+        out.append((q, s))
+    return tuple(out)
+
+
+def dequantize_experts_fp8(q, s, dtype=None):
+    """fl32(float(q) * s), [E, N, K] in fp32 (or rounded once to `dtype`): the weights the FP8 expert kernels multiply by"""
+    w = F8.dequantize_blocks(_f8_view(q), s)
+    return w if dtype is None else w.to(dtype)
+
+
+def check_fp8_experts(gu, down, name="experts"):
+    """the shapes, dtypes and scales of block-scaled FP8 expert tensors (gu, down: (q, s) each; q float8_e4m3fn or its bytes); raises
+    SamdError by tensor name.  Plain torch, any device."""
+    for what, (q, s) in ((f"{name}.gate_up_proj", gu), (f"{name}.down_proj", down)):
+        if s is None:
+            raise SamdError(f"{what}: FP8 expert tensor without its block scales ({what}_scale_inv)")
+        if q.dim() != 3:
+            raise SamdError(f"{what}: expected float8_e4m3fn [E, N, K], got {q.dtype} {tuple(q.shape)}")
+        F8.check_block_scales(_f8_view(q), s, what)
+        E, N, K = q.shape
+        if N % 128 != 0 or K % 256 != 0:
+            raise SamdError(f"{what} of shape ({E}, {N}, {K}): the FP8 expert kernels need N % 128 == 0 and K % 256 == 0")
+    E, N2, H = gu[0].shape
+    if tuple(down[0].shape) != (E, H, N2 // 2):
+        raise SamdError(f"{name}: FP8 expert tensors of shapes {tuple(gu[0].shape)} and {tuple(down[0].shape)} do not belong together "
+                        f"(gate_up_proj [E, 2 I, H], down_proj [E, H, I])")
+
+
+def fp8_scale_table(s, order=None):
+    """the packed buffer's scale table [E * N / 64, K / 128] fp32 of block scales s [E, N / 128, K / 128]: one row per 64 PACKED rows.
+    Packed row block j of an expert starts at source row order[64 j] (gate|up: gate_up_tile_order, so block 2 t is gate row 64 t -- scale
+    row-block t / 2 -- and block 2 t + 1 is up row I + 64 t -- row-block (I + 64 t) / 128; down: the identity, both halves of a tile
+    repeat one scale row).  64 divides 128 and the gate / up halves start at multiples of 64, so a 64-row packed block never straddles
+    two scale blocks."""
+    E, NB, KB = s.shape
+    first = torch.arange(0, NB * F8.BLOCK, 64, device=s.device)
+    src = first if order is None else order[first]
+    return s.float()[:, src // F8.BLOCK, :].reshape(E * NB * 2, KB).contiguous()
+
+
+def pack_experts_fp8(gu, down):
+    """(packed gate|up, packed down) of (q, s) pairs: uint8 buffers of E * fp8.packed_block_bytes(N, K) bytes each -- the codes in
+    samd_gemm_pack_f8's layout, the experts end to end as one matrix of E * N rows (tile e * N / 128 + t is expert e's tile t), the gate|up
+    rows permuted first (gate_up_tile_order); then, at fp8.block_scale_offset(E * N, K), the fp32 table of fp8_scale_table.  Tensors
+    already on the GPU; the buffers serve both model dtypes."""
+    check_fp8_experts(gu, down)
+    E, N2, H = gu[0].shape
+    I = N2 // 2
+    order = gate_up_tile_order(I, gu[0].device)
+    out = []
+    for (q, s), N, K, perm in ((gu, N2, H, order), (down, H, I, None)):
+        qb = q.view(torch.uint8) if q.dtype != torch.uint8 else q
+        qb = (qb if perm is None else qb[:, perm]).contiguous()
+        off = F8.block_scale_offset(E * N, K)
+        buf = torch.empty(E * F8.packed_block_bytes(N, K), dtype=torch.uint8, device=q.device)
+        assert off == E * N * K and buf.numel() == off + E * (N // 64) * (K // F8.BLOCK) * 4
+        check(lib().samd_gemm_pack_f8(_ptr(qb), _ptr(buf), E * N, K, current_stream()))
+        buf[off:].view(torch.float32).copy_(fp8_scale_table(s, perm).reshape(-1))
+        out.append(buf)
+    return tuple(out)
+
+
+def is_fp8_experts_module(experts):
+    """the fused form: a module with float8 gate_up_proj / down_proj tensors (transformers' FP8Experts)"""
+    gu, dn = getattr(experts, "gate_up_proj", None), getattr(experts, "down_proj", None)
+    return gu is not None and dn is not None and (F8.is_fp8_dtype(gu.dtype) or F8.is_fp8_dtype(dn.dtype))
+
+
+def import_experts_fp8(experts, name, device, config=None):
+    """the raw-weights-dict entries (experts_gu / experts_gu_sinv / experts_down / experts_down_sinv) of a sparse layer's block-scaled FP8
+    experts, on `device`: either the fused form (transformers' FP8Experts: gate_up_proj [E, 2 I, H] + gate_up_proj_scale_inv [E, 2 I/128,
+    H/128], down_proj [E, H, I] + down_proj_scale_inv) or an indexable of E modules whose gate_proj / up_proj / down_proj carry `weight` +
+    `weight_scale_inv` (the on-disk naming), each imported by fp8.linear_fp8_block, gate|up fused per expert and the experts stacked.
+    `config`: the model's quantization_config.  Rejections reach the caller by tensor name."""
+    mv = lambda t: t.detach().view(torch.uint8).to(device).view(torch.float8_e4m3fn).contiguous()
+    if hasattr(experts, "gate_up_proj"):
+        F8.check_block_config(config, name)
+        bs = getattr(experts, "block_size", None)
+        if bs is not None and tuple(int(x) for x in bs) != (F8.BLOCK, F8.BLOCK):
+            raise SamdError(f"{name}: block_size {list(bs)} is not supported; block-scaled FP8 takes [128, 128]")
+        if getattr(experts, "activation_scheme", None) == "static":
+            raise SamdError(f"{name}: activation_scheme 'static' is not supported; the runner is weight-only and takes 'dynamic' checkpoints")
+        out = {}
+        for key, pn in (("experts_gu", "gate_up_proj"), ("experts_down", "down_proj")):
+            q, s = getattr(experts, pn), getattr(experts, pn + "_scale_inv", None)
+            F8.check_block_scales(q.detach(), None if s is None else s.detach(), f"{name}.{pn}")
+            out[key], out[key + "_sinv"] = mv(q), s.detach().to(device).contiguous()
+        return out
+    gu, dn = [], []
+    for e in range(len(experts)):
+        parts = []
+        for p in INT4_EXPERT_PROJECTIONS:
+            r = F8.linear_fp8_block(getattr(experts[e], p), f"{name}.{e}.{p}", config)
+            if r is None:
+                raise SamdError(f"{name}.{e}.{p}: not an FP8 weight beside FP8 experts: the experts of a layer come in one format")
+            parts.append(r)
+        g, u, d = parts
+        gu.append((torch.cat([mv(g[0]).view(torch.uint8), mv(u[0]).view(torch.uint8)], dim=0), torch.cat([g[1].to(device), u[1].to(device)], dim=0)))
+        dn.append((mv(d[0]).view(torch.uint8), d[1].to(device)))
+    out = {}
+    for key, parts in (("experts_gu", gu), ("experts_down", dn)):
+        out[key] = torch.stack([p[0] for p in parts]).view(torch.float8_e4m3fn).contiguous()
+        out[key + "_sinv"] = torch.stack([p[1] for p in parts]).contiguous()
+    return out
+
+
 def pack_experts(gate_up, down):
     """(packed gate|up, packed down) of HF's fused expert tensors [E, 2 I, H] / [E, H, I], already on the GPU in the model dtype"""
     E, N2, H = gate_up.shape
@@ -317,11 +470,22 @@ class MoeBuffers:
         check(lib().samd_moe_lists(_ptr(self.topk_idx), _ptr(d_n), self.rows_pad, self.n_experts, self.top_k, _ptr(self.ws), current_stream()))
 
     def experts(self, h, wgu_packed, wdown_packed, d_n, expert_format=None):
-        """the two expert launches over buffers of pack_experts (expert_format None), pack_experts_mxfp4 ("mxfp4") or pack_experts_int4
-        ("int4g128"; packed for this runner's dtype)"""
+        """the two expert launches over buffers of pack_experts (expert_format None), pack_experts_mxfp4 ("mxfp4"), pack_experts_int4
+        ("int4g128"; packed for this runner's dtype) or pack_experts_fp8 ("fp8b128")"""
         L, st = lib(), current_stream()
-        if expert_format not in EXPERT_FORMATS_ALL:
-            raise SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS_ALL)}")
+        if expert_format not in EXPERT_FORMATS_KNOWN:
+            raise _format_error(expert_format)
+        if expert_format == "fp8b128":
+            # the byte count tells this buffer from every other one of the shape (gate|up and down differ too: swapped buffers raise)
+            for what, t, want in (("gate|up", wgu_packed, self.n_experts * F8.packed_block_bytes(2 * self.moe_inter, self.hidden)),
+                                  ("down", wdown_packed, self.n_experts * F8.packed_block_bytes(self.hidden, self.moe_inter))):
+                if t.dtype != torch.uint8 or t.numel() != want:
+                    raise SamdError(f"FP8 {what} expert buffer of {t.numel()} {t.dtype} elements; pack_experts_fp8 gives {want} bytes for this shape")
+            check(L.samd_moe_gate_up_silu_f8(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts,
+                                             self.top_k, _ptr(self.act), self.dt, st))
+            check(L.samd_moe_down_combine_f8(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws),
+                                             self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k, _ptr(self.out), self.dt, st))
+            return self.out
         if expert_format == "int4g128":
             for t, want in ((wgu_packed, self.n_experts * I4.packed_bytes(2 * self.moe_inter, self.hidden)),
                             (wdown_packed, self.n_experts * I4.packed_bytes(self.hidden, self.moe_inter))):
