@@ -648,6 +648,17 @@ int samd_gemm_skinny_groups(const void *d_A, const void *d_Wg, int32_t rows_pad,
 int samd_gemm_pack_f8(const void *d_W8, void *d_out, int32_t N, int32_t K, void *stream);
 int samd_gemm_skinny_f8(const void *d_A, const void *d_W8p, const float *d_scale, int32_t rows_pad, int32_t N, int32_t K, int32_t splits,
                         float *d_partial, void *d_out, int32_t dtype, void *stream);
+/* Dense block-scaled FP8 projection (the weight / weight_scale_inv of transformers' fine-grained FP8 checkpoints, e.g. Qwen3-*-FP8: OCP e4m3fn
+ * codes q, one fp32 scale s per 128 x 128 block).  Numeric contract of samd_hip/fp8.py: W[n][k] = float(q[n][k]) * s[n / 128][k / 128] is never
+ * formed; out[m][n] = sum_b s[n / 128][b] * (sum_{k in block b} A[m][k] * q[n][k]), the inner sum an fp32 MFMA accumulation over the block's 128 k,
+ * the outer step ONE fp32 FMA per accumulator and block, blocks in ascending order.
+ *   d_W8p    the codes in samd_gemm_pack_f8's layout (the pack entry point is shared with samd_gemm_skinny_f8).
+ *   d_sinv   the checkpoint's own table, fp32 [N / 128][K / 128] row-major, not repacked, 8-byte aligned; read by wave-uniform scalar loads.
+ *   splits == 1: d_out [rows_pad][N] in the model dtype (one rounding of the fp32 sum); otherwise fp32 partials [splits][rows_pad][N] in d_partial,
+ *   the layout of samd_gemm_skinny_f8, so samd_rmsnorm_warm, samd_silu_mul and samd_rope_kv_write_* take them unchanged.  Rows 16/32/48/64,
+ *   N % 128 == 0, K % 256 == 0 (no upper limit on K: no scale table is staged), 1 <= splits <= K / 256, f16 / bf16; anything else is SAMD_E_INVALID. */
+int samd_gemm_skinny_f8b(const void *d_A, const void *d_W8p, const float *d_sinv, int32_t rows_pad, int32_t N, int32_t K, int32_t splits,
+                         float *d_partial, void *d_out, int32_t dtype, void *stream);
 /* MXFP4 weight-only projections (OCP Microscaling: e2m1 elements, two per byte with the low nibble first, one e8m0 scale 2^(e8 - 127) per 32
  * elements along k; no per-row or per-tensor scale):
  *   samd_gemm_pack_f4     row-major q [N][K/2] bytes + e8 [N][K/32] codes -> ONE buffer of N * K / 2 + N * K / 32 bytes: per (128-column tile,

@@ -3145,3 +3145,201 @@ int samd_moe_down_combine_f8(const void *d_act, const void *d_Wdown8, const int3
 }
 
 }  // extern "C"
+
+// ================================================================================================
+// Dense block-scaled FP8 projection (OCP e4m3fn codes, one fp32 scale per 128 x 128 block: the weight / weight_scale_inv of transformers'
+// fine-grained FP8 checkpoints, e.g. Qwen3-*-FP8): out[m][n] = sum_b s[n / 128][b] * (sum_{k in block b} A[m][k] * q[n][k]).
+//   NUMERIC CONTRACT (samd_hip/fp8.py), the one of moe8_expert_gemm: the inner sum is an fp32 MFMA accumulation over the block's 128 k with q
+//   widened exactly (F8Widen, scale 1); the outer step is ONE fp32 FMA per accumulator and block (acc = fma(blk, s_b, acc)), blocks in
+//   ascending order.  W is never formed.  splits == 1: one rounding of the fp32 sum to the model dtype; otherwise fp32 partials
+//   [splits][rows_pad][N], as samd_gemm_skinny_f8 writes them.
+//   The dense sibling of moe8_expert_gemm with k_gemm_skinny_f8's grid (N / 128, splits), split-K ranges, A staging, k permutation, packed
+//   layout (samd_gemm_pack_f8, reused unchanged), hand-issued nt 16-byte weight loads with in-out destinations and counted waits.  A function
+//   of its own: every other kernel is left textually alone.
+//   THE SCALES are the checkpoint's own table, fp32 [N / 128][K / 128] row-major, not repacked: tile t = block row t, chunk c = entries 2 c
+//   and 2 c + 1, so a split reads the contiguous entries [2 c0, 2 c1) of one row.  They arrive as a WAVE-UNIFORM SCALAR LOAD of 8 bytes per
+//   chunk (the address depends on blockIdx and the chunk counter only; the pointer is read through the constant address space so that the
+//   load is selected as a scalar-memory load whatever the memory clobbers of the hand-written stream say).  Why not staged in LDS as the
+//   expert kernel does: (1) a scalar load counts on lgkmcnt, so the counted vmcnt waits (PC = 4 + XV operations per chunk) stay true -- a
+//   vector global load inside the stream would break them, and tests/test_fp8b128_cpu.py reads off the code object that there is none;
+//   (2) the 32-row tile takes 80 KiB of dynamic LDS and two workgroups fill the CU's 160 KiB exactly: any static LDS would cost it its
+//   second workgroup; (3) no table, so no limit on K (Qwen3-32B's down projection has 200 k blocks, more than MOE8_MAX_KB): every
+//   K % 256 == 0 that fits int32 is accepted.  The pair of chunk c + 1 is requested during phase c (behind its last A read) and lands in
+//   SGPRs while that phase's MFMAs run; the FMAs take the scale as a scalar operand, so the scales cost no VGPR.  The last chunk of a split
+//   requests nothing: no read past the table.
+//   DEPTH AND LAUNCH BOUNDS per row tile, from the LDS each tile takes and the VGPR counts of the code object (the second launch-bound
+//   argument is waves per SIMD: a 512-thread workgroup is 2 waves per SIMD, so two workgroups per CU = 4 waves = 128 VGPRs each).
+//   k_gemm_skinny_f8's depths (4 / 4 / 4 / 3) are the starting point; the block accumulators add 4 * RT VGPRs:
+//     16 rows: DEPTH 4, 40 KiB LDS, 108 VGPRs -> bound 4, two workgroups per CU as before.
+//     32 rows: at DEPTH 4 the code object takes 130 VGPRs unbounded (3 waves per SIMD: ONE workgroup per CU) and spills 3 registers when
+//              bounded to 128 -- a spilled load destination would be stored before its data has landed.  DEPTH 3 (48 weight VGPRs, 4 A
+//              buffers = 64 KiB) takes 114 VGPRs under bound 4 without spills: two workgroups per CU with 2 x 96 KiB of weights in
+//              flight, more than one workgroup's 128 KiB at DEPTH 4.
+//     48 rows: DEPTH 4, 120 KiB LDS -> one workgroup per CU whatever the registers; 152 VGPRs, bound 2 (the workgroup's own 2 waves per SIMD).
+//     64 rows: DEPTH 3 (5 A buffers would take the whole 160 KiB), 128 KiB LDS, 160 VGPRs, bound 2.
+//   (DEPTH - 1) * PC = 15, 12, 21, 16 <= 63.  No instantiation has scratch or VGPR spills, and the only vector global loads are the 16-byte
+//   weight loads and the LDS-DMA A loads (tests/test_fp8b128_cpu.py reads both off the code object).  The table is derived from the code
+//   object, not swept on a GPU; profiles/fp8b128_gemm.md says what was measured.
+// ================================================================================================
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(4))) const f32x2 *cscale2_t;
+template <int RT> struct F8bDepth { static constexpr int value = (RT == 2 || RT == 4) ? 3 : 4; };
+
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, RT <= 2 ? 4 : 2) void k_gemm_skinny_f8b(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8,
+                                                                                     const float *__restrict__ sinv, float *__restrict__ partial,
+                                                                                     typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int n_splits) {
+    typedef typename TT::elem E;
+    constexpr int DEPTH = F8bDepth<RT>::value;
+    constexpr int R = 16 * RT;
+    constexpr int NT = 64 * GEMM_WAVES;
+    constexpr int XV = (R * 32) / NT;              // 16-byte units per thread to stage one A chunk (as k_gemm_skinny)
+    constexpr int NB = DEPTH + 1;
+    constexpr int PC = 4 + XV;                     // memory operations per thread and chunk: 4 weight loads + the A staging
+    constexpr size_t WCH = 32768, WU = 8192;       // bytes of one (tile, chunk) block; of one b row inside it
+    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
+    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
+
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
+    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    const int split = blockIdx.y;
+    const int c0 = (int)((long long)split * n_chunks / n_splits), c1 = (int)((long long)(split + 1) * n_chunks / n_splits);
+    const char *wtile = reinterpret_cast<const char *>(W8) + (size_t)blockIdx.x * n_chunks * WCH;
+    const uint32_t wlane = (uint32_t)tid * 16;
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
+    // this tile's row of the scale table, two entries per chunk; wave-uniform, read by scalar loads only
+    const cscale2_t srow = (cscale2_t)(uintptr_t)(sinv + (size_t)blockIdx.x * 2 * n_chunks);
+
+    floatx4 acc[RT];
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
+    u32x4 wr[DEPTH][4];
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) asm volatile("" : "=v"(wr[d][b]));
+    auto load_wb = [&](u32x4 (&dst)[4], int c, int b) {
+        const char *p = wtile + (size_t)c * WCH;
+        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[b]) : "v"(wlane), "s"(p + WU * b) : "memory");
+    };
+    auto stage_xi = [&](int c, int buf, int i) {
+        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
+        const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
+        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        asm volatile("" ::: "memory");
+    };
+    auto load_w = [&](u32x4 (&dst)[4], int c) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) load_wb(dst, c, b);
+    };
+    auto stage_x = [&](int c, int buf) {
+#pragma unroll
+        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
+    };
+    f32x2 snext = (f32x2){0.f, 0.f};               // the scales of the next phase's two k blocks (SGPRs)
+    auto phase = [&](u32x4 (&cur)[4], int c, int buf) {
+        gemm_wait_younger<DEPTH, PC>(c1 - 1 - c);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
+        const f32x2 s2 = snext;                                // k blocks 2 c and 2 c + 1, requested one phase ago
+        floatx4 blk[RT];
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            if ((b & 1) == 0) {
+#pragma unroll
+                for (int mt = 0; mt < RT; mt++) blk[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+            }
+            const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
+            u32x4 r[RT][2];
+            gemm_f4_read_a<RT>(r, a0, a1);
+            // re-defined behind the counted wait (volatile asm keeps its order): no conversion can be scheduled above it
+            asm volatile("" : "+v"(cur[b]) : : "memory");
+            if (b == 3 && c + 1 < c1) snext = srow[c + 1];     // behind this phase's last A read (whose wait would otherwise cover it)
+            const auto lo = F8Widen<TT>::cvt(cur[b][0], cur[b][1]), hi = F8Widen<TT>::cvt(cur[b][2], cur[b][3]);
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++) {
+                blk[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, blk[mt]);
+                blk[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, blk[mt]);
+            }
+            if (b & 1) {                                       // a 128-k block is complete: one fp32 FMA per accumulator
+                const float s = b == 1 ? s2.x : s2.y;
+#pragma unroll
+                for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                    for (int q = 0; q < 4; q++) acc[mt][q] = __builtin_fmaf(blk[mt][q], s, acc[mt][q]);
+            }
+            if (RT >= 3 && c + DEPTH < c1) {                   // 48 / 64 rows: refill per k block (see k_gemm_skinny)
+                load_wb(cur, c + DEPTH, b);
+                if (b < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, b);
+            }
+        }
+        if (RT < 3 && c + DEPTH < c1) { load_w(cur, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
+    };
+    if (c0 < c1) {
+        snext = srow[c0];
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++)
+            if (c0 + d < c1) { load_w(wr[d], c0 + d); stage_x(c0 + d, d); }
+        int buf = 0;
+        for (int c = c0; c < c1; c += DEPTH) {
+#pragma unroll
+            for (int d = 0; d < DEPTH; d++)
+                if (c + d < c1) { phase(wr[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+        }
+    }
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n; the block scales went in with the FMAs
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int m = 16 * mt + 4 * g + r;
+            const float v = acc[mt][r];
+            if (out) out[(size_t)m * N + n0 + n] = (E)v;
+            else __hip_atomic_store(&partial[((size_t)split * R + m) * N + n0 + n], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+template <typename TT, int RT>
+static hipError_t gemm_f8b_launch(dim3 grid, hipStream_t st, const void *A, const void *W8, const float *sinv, float *partial, void *out, int K, int N,
+                                  int splits) {
+    constexpr int lds = (F8bDepth<RT>::value + 1) * 16 * RT * GEMM_KC * 2;
+    if constexpr (lds > 65536) {
+        static unsigned long long done = 0ull;                     // per-device (samd_common.h)
+        const hipError_t attr = samd_reserve_lds((const void *)k_gemm_skinny_f8b<TT, RT>, lds, &done);
+        if (attr != hipSuccess) return attr;
+    }
+    hipLaunchKernelGGL((k_gemm_skinny_f8b<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const typename TT::elem *)A, (const unsigned char *)W8, sinv,
+                       partial, (typename TT::elem *)out, K, N, K / GEMM_KC, splits);
+    return hipSuccess;
+}
+
+extern "C" {
+
+int samd_gemm_skinny_f8b(const void *d_A, const void *d_W8p, const float *d_sinv, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial,
+                         void *d_out, int32_t dtype, void *stream) {
+    if (!d_A || !d_W8p || !d_sinv || ((uintptr_t)d_sinv & 7) != 0 || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS ||
+        N % GEMM_COLS != 0 || K < GEMM_KC || K % GEMM_KC != 0 || splits < 1 || splits > K / GEMM_KC || (splits == 1 ? !d_out : !d_partial) ||
+        (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("samd_gemm_skinny_f8b: unsupported shape (rows 16/32/48/64, N %% 128 == 0, K %% 256 == 0, scale table 8-byte aligned) or null pointer");
+        return SAMD_E_INVALID;
+    }
+    const dim3 grid(N / GEMM_COLS, splits);
+    const hipStream_t st = (hipStream_t)stream;
+    float *part = splits == 1 ? nullptr : d_partial;
+    void *out = splits == 1 ? d_out : nullptr;
+#define GO(TT, RT) e = gemm_f8b_launch<TT, RT>(grid, st, d_A, d_W8p, d_sinv, part, out, K, N, splits)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
+    hipError_t e;
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
+    if (e != hipSuccess) { samd_set_error("samd_gemm_skinny_f8b: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+}  // extern "C"

@@ -180,6 +180,7 @@ _PROTOS = {
     "samd_gemm_skinny_groups": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "samd_gemm_pack_f8": (C.c_int, [_VP, _VP, _I32, _I32, _VP]),
     "samd_gemm_skinny_f8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
+    "samd_gemm_skinny_f8b": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "samd_gemm_pack_f4": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _VP]),
     "samd_gemm_skinny_f4": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "samd_gemm_pack_i4": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),

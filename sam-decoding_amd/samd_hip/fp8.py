@@ -7,10 +7,12 @@ Checkpoints that already carry FP8 projections (an nn.Linear whose weight is flo
 [N, 1]) are imported as they are.  Everything here is plain torch and runs on any device.
 
 BLOCK-SCALED FP8 (the official Qwen3-MoE FP8 checkpoints: `weight` float8_e4m3fn with `weight_scale_inv` fp32, one scale per 128 x 128 block,
-quantization_config.weight_block_size = [128, 128]) is the format of mixture-of-experts EXPERTS only (expert_format "fp8b128",
-samd_hip/moe.py); linear_fp8 keeps rejecting it for the dense FP8 runner.  Its numeric contract:
+quantization_config.weight_block_size = [128, 128]; the dense Qwen3-*-FP8 checkpoints and everything else transformers' fine-grained FP8
+quantiser writes) is the format of mixture-of-experts experts (expert_format "fp8b128", samd_hip/moe.py) and of the dense runner's
+weight_format "fp8b128" (samd_gemm_skinny_f8b: the same contract, the checkpoint's own scale table); linear_fp8 keeps rejecting it for the
+per-row weight_format "fp8".  Its numeric contract:
     W[n][k] = float(q[n][k]) * s[n / 128][k / 128],  q OCP e4m3fn, s fp32, finite and positive.
-The expert kernels never form W.  Per output element they compute out = sum_b s_b * (sum_{k in block b} A[m][k] * q[n][k]): the inner sum is
+The kernels never form W.  Per output element they compute out = sum_b s_b * (sum_{k in block b} A[m][k] * q[n][k]): the inner sum is
 an fp32 MFMA accumulation over the block's 128 k with q widened exactly (v_cvt_scalef32_pk_{f16,bf16}_fp8 at scale 1: every e4m3fn value is
 exact in fp16 and in bf16), the outer step ONE fp32 FMA per accumulator and block, acc = fma(acc_blk, s_b, acc), in ascending block order.
 That is the weight side of HF's own block-FP8 matmul; it cannot overflow fp16.  The epilogues' roundings (HF's: gate, up, their product, the
@@ -196,3 +198,49 @@ def linear_fp8_dequantized(lin, name="projection", config=None):
     if getattr(lin, "weight_scale_inv", None) is not None:
         return dequantize_blocks(*linear_fp8_block(lin, name, config))
     return dequantize_rows(*linear_fp8(lin, name))
+
+
+def block_scaled_bytes(N, K):
+    """bytes of one [N, K] block-scaled FP8 projection as the dense runner holds it (weight_format "fp8b128"): N * K codes in
+    samd_gemm_pack_f8's layout and the checkpoint's own table, one fp32 scale per 128 x 128 block"""
+    return N * K + (N // BLOCK) * (K // BLOCK) * 4
+
+
+def fuse_fp8_blocks(parts, device, names=None):
+    """row-concatenate the (q [N_i, K], s [N_i/128, K/128]) of q|k|v or gate|up on `device` (the bytes are moved as uint8).  The block rows of
+    the parts line up in the fused table because every part has N_i % 128 == 0; a part that has not raises SamdError by its name"""
+    names = names or [f"part {i}" for i in range(len(parts))]
+    K = parts[0][0].shape[1]
+    for (q, s), name in zip(parts, names):
+        N = q.shape[0]
+        if N % BLOCK != 0 or q.shape[1] != K or K % BLOCK != 0 or tuple(s.shape) != (N // BLOCK, K // BLOCK):
+            raise SamdError(f"{name}: a [{N}, {q.shape[1]}] block-scaled FP8 part with scales {list(s.shape)} cannot be fused: every part needs "
+                            f"N % 128 == 0 (a 128 x 128 block would straddle two parts), the same K % 128 == 0 and one scale per block")
+    q = torch.cat([p[0].to(device).view(torch.uint8) for p in parts], dim=0).view(torch.float8_e4m3fn).contiguous()
+    s = torch.cat([p[1].to(device=device, dtype=torch.float32) for p in parts], dim=0).contiguous()
+    return q, s
+
+
+def checkpoint_is_fp8_block(linears, config=None):
+    """True when every projection Linear is block-scaled FP8 (an FP8 `weight` beside a `weight_scale_inv`; each is then checked by
+    linear_fp8_block with the module's quantization_config, whose rejections apply by name), False when none is; a mix -- block-scaled
+    beside per-row / per-tensor FP8, plain or other formats -- raises SamdError naming examples"""
+    def kind(lin):
+        w = getattr(lin, "weight", None)
+        if w is None or not is_fp8_dtype(w.dtype):
+            return "other"
+        return "block" if getattr(lin, "weight_scale_inv", None) is not None else "row"
+    kinds = [(name, kind(lin)) for name, lin in linears]
+    nb = sum(k == "block" for _, k in kinds)
+    if nb == 0:
+        return False
+    if nb < len(kinds):
+        rows = [n for n, k in kinds if k == "row"][:3]
+        other = [n for n, k in kinds if k == "other"][:3]
+        what = "; ".join(x for x in (f"e.g. {', '.join(rows)} carry a per-row / per-tensor weight_scale" if rows else "",
+                                     f"e.g. {', '.join(other)} are not FP8" if other else "") if x)
+        raise SamdError(f"a mix of block-scaled FP8 and other projections ({nb} of {len(kinds)} are block-scaled FP8; {what}); "
+                        "the runner takes all projections in one format")
+    for name, lin in linears:
+        linear_fp8_block(lin, name, config)
+    return True

@@ -29,25 +29,29 @@ def _env_weight_format(weight_format):
 
 
 def _weight_format(weight_format, weights, dtype):
-    """"fp8", "mxfp4", "int4g128" or None (the model dtype; the plain word "int4" stays an unknown format: the name carries the group size).  Projections that arrive as float8_e4m3fn (an FP8 checkpoint), as packed e2m1 bytes
+    """"fp8", "fp8b128", "mxfp4", "int4g128" or None (the model dtype; the plain word "int4" stays an unknown format: the name carries the group size).  Projections that arrive as float8_e4m3fn (an FP8 checkpoint), as packed e2m1 bytes
     (an MXFP4 checkpoint: uint8 / float4_e2m1fn_x2 [N, K/2]) or as 4-bit codes with zero points and group scales (an AWQ / GPTQ checkpoint:
-    uint8 [N, K/2] beside k + "_z" and k + "_s") make the runner FP8 / MXFP4 / INT4 by themselves."""
-    has_f8 = any(l[k].dtype == torch.float8_e4m3fn for l in weights["layers"] for k in F8.PROJECTIONS if k in l)
+    uint8 [N, K/2] beside k + "_z" and k + "_s") make the runner FP8 / MXFP4 / INT4 by themselves.  float8_e4m3fn projections beside k + "_sinv"
+    (fp32, one scale per 128 x 128 block) are block-scaled FP8 and make the runner "fp8b128": the _sinv keys tell them from per-row "fp8"."""
+    has_f8b = any(k + "_sinv" in l for l in weights["layers"] for k in F8.PROJECTIONS)
+    has_f8 = any(l[k].dtype == torch.float8_e4m3fn and k + "_sinv" not in l for l in weights["layers"] for k in F8.PROJECTIONS if k in l)
     has_i4 = any(k + "_z" in l for l in weights["layers"] for k in I4.PROJECTIONS)
     has_f4 = any(_is_f4_tensor(l[k]) and k + "_z" not in l for l in weights["layers"] for k in MX.PROJECTIONS if k in l)
     names = {torch.float16: ("fp16", "float16", "half"), torch.bfloat16: ("bf16", "bfloat16")}.get(dtype, ())
     if weight_format is None:
-        fmt = "fp8" if has_f8 else ("mxfp4" if has_f4 else ("int4g128" if has_i4 else None))
-    elif weight_format in ("fp8", "mxfp4", "int4g128"):
+        fmt = "fp8" if has_f8 else ("fp8b128" if has_f8b else ("mxfp4" if has_f4 else ("int4g128" if has_i4 else None)))
+    elif weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128"):
         fmt = weight_format
     elif weight_format == dtype or (isinstance(weight_format, str) and weight_format.lower() in names):
         fmt = None
     else:
         hint = " (the AWQ / GPTQ format is spelled 'int4g128': 4-bit codes in groups of 128, the only group size the kernel has)" \
             if weight_format == "int4" else ""
-        raise SamdError(f"weight_format {weight_format!r}: expected None, 'fp8', 'mxfp4', 'int4g128' or the model dtype ({dtype}){hint}")
+        raise SamdError(f"weight_format {weight_format!r}: expected None, 'fp8', 'mxfp4', 'int4g128', 'fp8b128' or the model dtype ({dtype}){hint}")
     if has_f8 and fmt != "fp8":
         raise SamdError(f"the weights carry float8_e4m3fn projections; weight_format {weight_format!r} would need them dequantised (pass None or 'fp8')")
+    if has_f8b and fmt != "fp8b128":
+        raise SamdError(f"the weights carry block-scaled FP8 projections; weight_format {weight_format!r} would need them dequantised (pass None or 'fp8b128')")
     if has_f4 and fmt != "mxfp4":
         raise SamdError(f"the weights carry MXFP4 projections; weight_format {weight_format!r} would need them dequantised (pass None or 'mxfp4')")
     if has_i4 and fmt != "int4g128":
@@ -206,8 +210,23 @@ class LlamaRunner:
         # samd_gemm_skinny_f4 only; everything FP8 implies for the runner holds here too (quant)
         # weight_format "int4g128": the same four projections as AWQ / GPTQ 4-bit codes with one scale (model dtype) and one zero point per 128 along
         # K (samd_hip/int4.py), streamed by samd_gemm_skinny_i4 only; again everything FP8 implies holds
+        # weight_format "fp8b128": the same four projections as OCP e4m3fn with one fp32 scale per 128 x 128 block (the weight / weight_scale_inv
+        # of transformers' fine-grained FP8 checkpoints; samd_hip/fp8.py has the contract), streamed by samd_gemm_skinny_f8b only from
+        # (samd_gemm_pack_f8's packed codes, the checkpoint's own scale table); again everything FP8 implies holds
         f8, f4, i4 = self.weight_format == "fp8", self.weight_format == "mxfp4", self.weight_format == "int4g128"
-        quant = f8 or f4 or i4
+        f8b = self.weight_format == "fp8b128"
+        quant = f8 or f4 or i4 or f8b
+        if f8b and not native_gemm:
+            raise SamdError("FP8 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'fp8b128'")
+        if f8b:                                                  # shapes the kernel cannot run, by projection, before any device work
+            if shape.inter % 128 != 0:
+                raise SamdError(f"block-scaled FP8 projection wgu: intermediate_size {shape.inter} is not a multiple of 128, so a 128 x 128 block "
+                                "would straddle gate and up")
+            for li, l in enumerate(weights["layers"]):
+                for k in F8.PROJECTIONS:
+                    N, K = l[k].shape
+                    if N % 128 != 0 or K % 256 != 0:
+                        raise SamdError(f"block-scaled FP8 projection {k} of layer {li}, shape ({N}, {K}): the kernel needs N % 128 == 0 and K % 256 == 0")
         if f8 and not native_gemm:
             raise SamdError("FP8 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'fp8'")
         if f4 and not native_gemm:
@@ -318,6 +337,22 @@ class LlamaRunner:
             out = torch.empty_like(q)
             check(lib().samd_gemm_pack_f8(_ptr(q), _ptr(out), N, K, current_stream()))
             return out, scale
+        def pack_f8b(l, k):
+            """(packed e4m3fn bytes, fp32 [N/128][K/128] block scales) of projection k: quantised on load (symmetric per 128 x 128 block,
+            uncalibrated) unless the checkpoint brought its own (q, s), which are taken as they are -- the codes packed by samd_gemm_pack_f8,
+            the table untouched; the model-dtype matrix is dropped as soon as it is packed"""
+            t = l[k]
+            N, K = t.shape
+            if t.dtype == torch.float8_e4m3fn:
+                q, sinv = t.to(self.device).contiguous(), l.pop(k + "_sinv").to(device=self.device).contiguous()
+                F8.check_block_scales(q, sinv, f"block-scaled FP8 projection {k}")
+            else:
+                q, sinv = F8.quantize_blocks(t)
+            l[k] = torch.empty(t.shape, dtype=torch.float8_e4m3fn, device="meta")
+            del t
+            out = torch.empty_like(q)
+            check(lib().samd_gemm_pack_f8(_ptr(q), _ptr(out), N, K, current_stream()))
+            return out, sinv
         def pack_f4(l, k):
             """projection k in samd_gemm_pack_f4's form (e2m1 elements with their e8m0 block scales inline): quantised on load per block of 32
             unless the checkpoint brought its own (q, e8), whose exponents must lie in the model dtype's exact range; the model-dtype matrix
@@ -375,6 +410,12 @@ class LlamaRunner:
                 lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
                 for k in F8.PROJECTIONS:
                     lp[k + "_f8"] = pack_f8(l, k)
+                layers.append(lp)
+                continue
+            if f8b:
+                lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
+                for k in F8.PROJECTIONS:
+                    lp[k + "_f8b"] = pack_f8b(l, k)
                 layers.append(lp)
                 continue
             sparse = "experts_gu" in l
@@ -510,6 +551,10 @@ class LlamaRunner:
                 for k in F8.PROJECTIONS:
                     rep["packed_" + k + "_f8"] = sum(nbytes(l[k + "_f8"][0]) for l in self.wp["layers"])
                 rep["fp8_scales"] = sum(nbytes(l[k + "_f8"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
+            if self.weight_format == "fp8b128":                  # the packed codes and, beside them, the checkpoint's own block-scale tables
+                for k in F8.PROJECTIONS:
+                    rep["packed_" + k + "_f8b"] = sum(nbytes(l[k + "_f8b"][0]) for l in self.wp["layers"])
+                rep["fp8_block_scales"] = sum(nbytes(l[k + "_f8b"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
             if self.weight_format == "mxfp4":                    # one buffer per projection: 16 KiB of elements, then their 1 KiB of scales
                 for k in MX.PROJECTIONS:
                     rep["packed_" + k + "_f4"] = sum(nbytes(l[k + "_f4"]) * 16 // 17 for l in self.wp["layers"])
@@ -519,7 +564,7 @@ class LlamaRunner:
                     rep["packed_" + k + "_i4"] = sum(nbytes(l[k + "_i4"]) * 16 // 17 for l in self.wp["layers"])
                 rep["int4_group_data"] = sum(nbytes(l[k + "_i4"]) // 17 for l in self.wp["layers"] for k in I4.PROJECTIONS)
         rep["total"] = sum(rep.values())
-        if self.weight_format in ("fp8", "mxfp4", "int4g128"):
+        if self.weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128"):
             rep["weight_format"] = self.weight_format
         rep["expert_format"] = self.expert_format                # None: experts (if any) in the model dtype; packed_moe_* are the bytes held
         return rep
@@ -614,7 +659,10 @@ class LlamaRunner:
         SAMD_SHARE_HF_WEIGHTS, off): re-point the HF module's q/k/v and gate/up weights at row slices of the runner's concatenated
         matrices -- saves one row-major copy of the model, but the caller's parameters become views of storage the runner owns
         (matters for save_pretrained / in-place edits), so it is opt-in and logged once.
-        weight_format (default: env SAMD_WEIGHT_FORMAT, unset = the model dtype): "fp8" quantises the projections on load.  A module whose
+        weight_format (default: env SAMD_WEIGHT_FORMAT, unset = the model dtype): "fp8" quantises the projections on load.
+        "fp8b128" quantises them per 128 x 128 block (no calibration: for benches and tests); a module without sparse layers whose seven
+        projections per layer are all block-scaled FP8 (`weight` float8_e4m3fn + `weight_scale_inv` fp32, weight_block_size [128, 128]: the
+        dense Qwen3-*-FP8 checkpoints) is imported as it is through fp8.linear_fp8_block and makes the runner "fp8b128" by itself.  A module whose
         projections already hold float8_e4m3fn weights with a `weight_scale` (per tensor, [N] or [N, 1]) is imported as it is (samd_hip/fp8.py).
         "mxfp4" quantises them per block of 32 (no calibration: for benches and tests); a module whose projections hold float4_e2m1fn_x2 or uint8
         weights [N, K/2] with an e8m0 `weight_scale` [N, K/32] is imported as it is (samd_hip/mxfp4.py).
@@ -659,7 +707,18 @@ class LlamaRunner:
         layer_f8 = [cls._hf_experts_are_fp8(lyr, i) for i, lyr in enumerate(m.layers)]
         moe_f8_dense = any(layer_f8)
         qcfg8 = getattr(getattr(lm, "config", None), "quantization_config", None)
-        ckpt_f8 = (not ckpt_i4) and (not moe_f8_dense) and F8.checkpoint_is_fp8(linears)
+        # a module WITHOUT sparse layers whose projections are all block-scaled FP8 (the dense Qwen3-*-FP8 checkpoints) is imported as it is,
+        # codes and scales untouched, and the runner is "fp8b128" by itself; modules with sparse layers are left to the branches above
+        ckpt_f8b = (not ckpt_i4) and (not moe_f8_dense) and not any(cls._hf_sparse_layers(m.layers)) and F8.checkpoint_is_fp8_block(linears, qcfg8)
+        if ckpt_f8b:
+            if weight_format not in (None, "fp8b128"):
+                raise SamdError(f"the module carries block-scaled FP8 projections; weight_format {weight_format!r} would need them dequantised "
+                                "(pass None or 'fp8b128')")
+            for name, lin in linears:                            # shapes the kernel cannot run, by projection, before any device work
+                N, K = lin.weight.shape
+                if N % 128 != 0 or K % 256 != 0:
+                    raise SamdError(f"{name}: a block-scaled FP8 projection of shape ({N}, {K}); the kernel needs N % 128 == 0 and K % 256 == 0")
+        ckpt_f8 = (not ckpt_i4) and (not moe_f8_dense) and (not ckpt_f8b) and F8.checkpoint_is_fp8(linears)
         ckpt_f4 = (not ckpt_i4) and MX.checkpoint_is_mxfp4(linears)
         qcfg = I4.quant_config(getattr(lm, "config", None))
         if F8.is_fp8_dtype(lm.lm_head.weight.dtype) or F8.is_fp8_dtype(m.embed_tokens.weight.dtype):
@@ -681,7 +740,7 @@ class LlamaRunner:
             if sparse != list(shape.sparse):
                 raise SamdError(f"the module's sparse MLP layers {[i for i, x in enumerate(sparse) if x]} are not the ones its config implies "
                                 f"{[i for i, x in enumerate(shape.sparse) if x]} (model_type '{shape.model_type}')")
-            MOE.reject_unsupported("int4g128" if ckpt_i4 else "fp8" if ckpt_f8 else ("mxfp4" if ckpt_f4 else weight_format), kw.get("native_gemm", True),
+            MOE.reject_unsupported("int4g128" if ckpt_i4 else "fp8" if ckpt_f8 else "fp8b128" if ckpt_f8b else ("mxfp4" if ckpt_f4 else weight_format), kw.get("native_gemm", True),
                                    kw.get("draft_head", False))
         # 4-bit experts: decided and checked on the module's own tensors, before anything moves to the device (the runner resolves the
         # format again from the weights it is given)
@@ -777,6 +836,14 @@ class LlamaRunner:
                 lw = {}
                 for k, lins in (("wqkv", (a.q_proj, a.k_proj, a.v_proj)), ("wo", (a.o_proj,)), ("wgu", (f.gate_proj, f.up_proj)), ("wdown", (f.down_proj,))):
                     lw[k], lw[k + "_e8"] = MX.fuse_mxfp4([MX.linear_mxfp4(x) for x in lins], dev)
+                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
+                continue
+            if ckpt_f8b:                                         # (q, block scales) as the checkpoint has them; the runner packs the codes
+                lw, li = {}, len(layers)
+                for k, own, names in (("wqkv", a, ("q_proj", "k_proj", "v_proj")), ("wo", a, ("o_proj",)), ("wgu", f, ("gate_proj", "up_proj")),
+                                      ("wdown", f, ("down_proj",))):
+                    full = [f"layers.{li}.{'self_attn' if own is a else 'mlp'}.{x}" for x in names]
+                    lw[k], lw[k + "_sinv"] = F8.fuse_fp8_blocks([F8.linear_fp8_block(getattr(own, x), n, qcfg8) for x, n in zip(names, full)], dev, full)
                 layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
                 continue
             if ckpt_f8:                                          # (q, scale) as the checkpoint has them; the runner packs them
@@ -1001,7 +1068,8 @@ class LlamaRunner:
 
     def weight_bytes(self, experts=None):
         """bytes of weights one decode step streams from HBM (the embedding table is only gathered), tensor by tensor in its own format
-        (an FP8 projection: one byte per weight + its fp32 column scales; an MXFP4 projection: half a byte per weight + one scale byte per 32; an
+        (an FP8 projection: one byte per weight + its fp32 column scales; a block-scaled FP8 projection: one byte per weight + 4 bytes per
+        128 x 128 block; an MXFP4 projection: half a byte per weight + one scale byte per 32; an
         INT4 projection: half a byte per weight + 4 bytes of scale and zero point per 128).
         A sparse (mixture-of-experts) layer counts `experts` of its experts in the format they are held in (MXFP4 experts: elements + block
         scales; block-scaled FP8 experts: one byte per weight + one fp32 scale per 128 x 128 block -- the packed table repeats each scale for
@@ -1020,6 +1088,8 @@ class LlamaRunner:
             n += sum(nb(t) for t in l.values())
         if self.weight_format == "fp8":
             n += sum(nb(l[k + "_f8"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
+        if self.weight_format == "fp8b128":                      # one byte per weight (counted above) + 4 bytes per 128 x 128 block
+            n += sum(nb(l[k + "_f8b"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
         return n
 
     # ------------------------------------------------------------------------------------------------
@@ -1087,9 +1157,9 @@ class LlamaRunner:
             sp = 1 if (fused or is_head) else L.samd_gemm_splits(n, k, RP)
             return C.byref(Warm(wp.data_ptr(), n, k, sp, self.warm_kb, self.warm_delay, self.warm_where))
 
-        def gemm(a, w, wp, out, wg=None, f8=None, f4=None, i4=None):
+        def gemm(a, w, wp, out, wg=None, f8=None, f4=None, i4=None, f8b=None):
             """out = a @ w.T (wp = w in the packed 128-column-tile layout, wg = w group-major: whichever exists; f8 = (packed e4m3fn, column
-            scales) of an FP8 runner; f4 = the packed elements + block scales of an MXFP4 runner; i4 = the packed codes + group data of an INT4 runner); returns (operand for the consumer,
+            scales) of an FP8 runner; f8b = (packed e4m3fn, fp32 block-scale table) of a block-scaled FP8 runner; f4 = the packed elements + block scales of an MXFP4 runner; i4 = the packed codes + group data of an INT4 runner); returns (operand for the consumer,
             n_partials, partial_stride)."""
             n, k = w.shape
             if i4 is not None:                                    # (RP <= 64 here, as for FP8; the INT4 runner's own packed buffer)
@@ -1099,6 +1169,10 @@ class LlamaRunner:
             if f4 is not None:                                    # (RP <= 64 here, as for FP8)
                 sp = L.samd_gemm_splits(n, k, RP)
                 check(L.samd_gemm_skinny_f4(_ptr(a), _ptr(f4), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
+                return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
+            if f8b is not None:                                   # (RP <= 64 here, as for FP8)
+                sp = L.samd_gemm_splits(n, k, RP)
+                check(L.samd_gemm_skinny_f8b(_ptr(a), _ptr(f8b[0]), _ptr(f8b[1]), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
                 return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
             if f8 is not None:                                    # (RP <= 64 here: an FP8 runner has no library-GEMM path, see the check above)
                 sp = L.samd_gemm_splits(n, k, RP)
@@ -1151,7 +1225,7 @@ class LlamaRunner:
                     _ptr(b["x"] if raw_in else b["h"]), _ptr(wp["wqkv64"]), RP, s.hidden, _ptr(b["cs"]), _ptr(d_L), _ptr(d_n),
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), s.heads, s.kv_heads, s.head_dim, self.max_len, dt, st))
             else:
-                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], f8=wp.get("wqkv_f8"), f4=wp.get("wqkv_f4"), i4=wp.get("wqkv_i4"))
+                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], f8=wp.get("wqkv_f8"), f8b=wp.get("wqkv_f8b"), f4=wp.get("wqkv_f4"), i4=wp.get("wqkv_i4"))
             if block:
                 # RoPE + K row / V^T column write + tree attention + merge of the tile partials: one launch (csrc/attn_kernels.hip)
                 check(L.samd_attention_block(_ptr(src), n_p, stride, _ptr(b["cs"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R,
@@ -1183,7 +1257,7 @@ class LlamaRunner:
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R, s.heads,
                     s.kv_heads, s.head_dim, self.max_len, _ptr(d_mask), _ptr(d_L), _ptr(d_n), self.scale,
                     _ptr(b["ws"]), b["ws_bytes"], hint(w["wo"], wp.get("wo")), st))
-            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"), f4=wp.get("wo_f4"), i4=wp.get("wo_i4"))
+            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"), f8b=wp.get("wo_f8b"), f4=wp.get("wo_f4"), i4=wp.get("wo_i4"))
             check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(src), _ptr(w["ln2"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, n_p, stride,
                                       None, st))           # (no warm-up hint: gate|up is packed group-major, the hint describes 128-column tiles)
             if "moe_gu" in wp:
@@ -1198,9 +1272,9 @@ class LlamaRunner:
             if wp.get("wgu") is not None and RP <= self.native_gemm_max_rows:
                 check(L.samd_gemm_pairs_silu(_ptr(b["h"]), _ptr(wp["wgu"]), RP, s.inter, s.hidden, _ptr(b["act"]), dt, st))
             else:
-                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"), f4=wp.get("wgu_f4"), i4=wp.get("wgu_i4"))     # wgu is only ever packed for the fused form (or FP8)
+                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"), f8b=wp.get("wgu_f8b"), f4=wp.get("wgu_f4"), i4=wp.get("wgu_i4"))     # wgu is only ever packed for the fused form (or FP8)
                 check(L.samd_silu_mul(_ptr(src), _ptr(b["act"]), R, s.inter, dt, n_p, stride, st))
-            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"), f4=wp.get("wdown_f4"), i4=wp.get("wdown_i4"))
+            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"), f8b=wp.get("wdown_f8b"), f4=wp.get("wdown_f4"), i4=wp.get("wdown_i4"))
         check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(delta), _ptr(self.w["norm"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, dn, dstride,
                                   hint(self.w["lm_head"], self.wp["lm_head"] if self.wp else None, is_head=True), st))
         # (for a draft head the call above only folds the last projection into the residual stream; its norm output is unused)
