@@ -689,6 +689,24 @@ int samd_gemm_skinny_f4(const void *d_A, const void *d_W4p, int32_t rows_pad, in
 int samd_gemm_pack_i4(const void *d_q, const void *d_z, const void *d_s, void *d_out, int32_t N, int32_t K, int32_t dtype, void *stream);
 int samd_gemm_skinny_i4(const void *d_A, const void *d_W4p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
                         int32_t dtype, void *stream);
+/* INT8 weight-only projections (GPTQ 8-bit checkpoints: unsigned 8-bit codes, one per byte, one scale in the model dtype and one zero point
+ * 0..255 per group of 128 elements along k; samd_hip/int8.py has the numeric contract and the checkpoint importer):
+ *   W[n][k] = rne_dtype((q[n][k] - z[n][k/128]) * s[n][k/128])  -- q - z an exact integer in [-255, 255], the product exact in fp32, ONE
+ *   rounding to dtype (fp16: with subnormals).  255 * max(s) must be finite in dtype (the caller checks: int8.check_scales).
+ *   samd_gemm_pack_i8     row-major q [N][K] bytes + z [N][K/128] bytes + s [N][K/128] 16-bit floats of `dtype` -> ONE buffer of
+ *                         N * K + N * K / 32 bytes: per (128-column tile, 256-k chunk) a 33 KiB block, 32 KiB of codes in samd_gemm_pack_f8's
+ *                         unit order (16 consecutive k of one column per 16-byte unit, all in one group) followed by 1 KiB of group data, 8
+ *                         bytes per row: the two scales and the two zero points of the chunk's two groups, the zero points as the dtype's
+ *                         widening subtracts them (fp16: the bits of 1024 + z, 0x6400 | z; bf16: the bits of z) (layout:
+ *                         csrc/gemm_kernels.hip; the buffer is specific to `dtype`).  N % 128 == 0, K % 256 == 0, d_out distinct from the inputs.
+ *   samd_gemm_skinny_i8   out[m][n] = sum_k A[m][k] * W[n][k]: A in the model dtype (dtype, the one d_W8p was packed for), fp32 accumulation in
+ *                         chunk order, zero point and scale applied by the widening, nothing in the epilogue.  splits == 1: d_out
+ *                         [rows_pad][N] in the model dtype (one rounding); otherwise fp32 partials [splits][rows_pad][N] in d_partial, the
+ *                         layout of samd_gemm_skinny.  Arguments and errors as samd_gemm_skinny_i4's (rows 16/32/48/64, N % 128, K % 256,
+ *                         1 <= splits <= K / 256; split rule samd_gemm_splits); the group data travels inside d_W8p. */
+int samd_gemm_pack_i8(const void *d_q, const void *d_z, const void *d_s, void *d_out, int32_t N, int32_t K, int32_t dtype, void *stream);
+int samd_gemm_skinny_i8(const void *d_A, const void *d_W8p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
+                        int32_t dtype, void *stream);
 /* Mixture-of-experts MLP (Qwen3-MoE; HF Qwen3MoeSparseMoeBlock) at rows_pad in {16, 32, 48, 64}, hidden % 256 == 0, moe_inter % 256 == 0,
  * n_experts <= 256, top_k <= min(8, n_experts), f16 / bf16.  Every launch has a fixed grid and reads its counts from device memory, so the
  * three calls of a sparse layer can be captured.  norm_topk is a flag (Qwen3-MoE's norm_topk_prob), not a model name.

@@ -1892,6 +1892,252 @@ int samd_gemm_skinny_i4(const void *d_A, const void *d_W4p, int32_t rows_pad, in
 }  // extern "C"
 
 // ================================================================================================
+// INT8 (GPTQ: unsigned 8-bit codes, one scale and one 8-bit zero point per 128 elements along k) weight-only projection:
+// out[m][n] = sum_k A[m][k] * W[n][k], W[n][k] = rne_dtype((q[n][k] - z[n][k/128]) * s[n][k/128]), A and s in the model dtype
+// (samd_hip/int8.py has the numeric contract).  The stream is k_gemm_skinny_f8's: grid, 32 KiB of codes per (tile, chunk), four hand-issued
+// nt 16-byte loads per lane and chunk, A staging by LDS-DMA with the A-side swizzle, counted waits, the per-k-block refill at 48 / 64 rows.
+// The group data is k_gemm_skinny_i4's: one 8-byte nt load per lane and chunk, in-out load destinations defined once.
+//   PACKED LAYOUT (samd_gemm_pack_i8): block (tile t = 128 columns, chunk c = 256 k) is 33 KiB contiguous at (t * K/256 + c) * 33792 bytes:
+//   32 KiB of codes, then 1 KiB of group data.  Code unit b * 512 + tid (16 bytes, b = 0..3) holds the 16 codes
+//   q[128 t + 16 w + n][256 c + 64 b + 16 g .. +15] for tid = 64 w + 16 g + n, in k order, one byte each (samd_gemm_pack_f8's unit): all
+//   inside ONE 128-group, 2 c + (b >> 1).  Group data: the 8 bytes at 32768 + 8 (16 w + n) are, as four 16-bit words, s[row][2 c],
+//   s[row][2 c + 1], zb[row][2 c], zb[row][2 c + 1] -- s the scale's bits in the model dtype, zb the zero point in the form the dtype's
+//   widening subtracts: fp16 the bits of 1024 + z (0x6400 | z), bf16 the bits of z itself (0..255 are exact in bf16's 8 significant bits).
+//   The four g lanes of a row read the same 8 bytes: 5 + XV memory operations per lane and chunk.
+// WIDENING, one rounding: fp16: a byte under 0x64 is the fp16 1024 + q (one v_perm_b32 per k pair); v_pk_add_f16 by -(1024 + z) is exact
+// (integers below 2048), v_pk_mul_f16 by s rounds once (fp16 denormals on).  bf16: v_cvt_f32_ubyte{0..3} gives q exactly in fp32; minus
+// float(z) is exact, times float(s) is exact in fp32 (9 x 8 significant bits), v_cvt_pk_bf16_f32 rounds once.  The library builds with
+// -ffp-contract=off, so (q - z) * s stays two operations.  The conversion sits behind the counted wait, as f8's.
+// DEPTH: k_gemm_skinny_f8's table (4 / 4 / 4 / 3 chunks in flight at 16 / 32 / 48 / 64 rows): 16 weight VGPRs + 2 of group data per chunk in
+// flight; no instantiation spills (tests/test_int8_codeobject_cpu.py reads it from the code object's metadata).
+// ================================================================================================
+typedef float float2v __attribute__((ext_vector_type(2)));
+
+template <typename TT> struct I8Widen;
+template <> struct I8Widen<GF16> {
+    struct G { half2v s, zb; };
+    static __device__ __forceinline__ G group(u32x2 gd, int j) {
+        const unsigned s = (gd[0] >> (16 * j)) & 0xffffu, z = (gd[1] >> (16 * j)) & 0xffffu;
+        return {__builtin_bit_cast(half2v, s | (s << 16)), __builtin_bit_cast(half2v, z | (z << 16))};
+    }
+    // 8 codes (two dwords, k order) -> the 8-element MFMA operand
+    static __device__ __forceinline__ half8 cvt(unsigned x0, unsigned x1, G g) {
+        u32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const unsigned x = i < 2 ? x0 : x1;
+            // v_perm_b32: selector bytes 0..3 take bytes of the second source, 4..7 of the first: (0x64, q_2i+1, 0x64, q_2i) from the high byte down
+            const unsigned p = __builtin_amdgcn_perm(0x64646464u, x, (i & 1) ? 0x04030402u : 0x04010400u);
+            r[i] = __builtin_bit_cast(unsigned, (__builtin_bit_cast(half2v, p) - g.zb) * g.s);              // (1024 + q) - (1024 + z), then ONE rounding
+        }
+        return __builtin_bit_cast(half8, r);
+    }
+};
+template <> struct I8Widen<GBF16> {
+    struct G { float s, zb; };
+    static __device__ __forceinline__ G group(u32x2 gd, int j) {
+        return {__builtin_bit_cast(float, (gd[0] >> (16 * j)) << 16), __builtin_bit_cast(float, (gd[1] >> (16 * j)) << 16)};
+    }
+    static __device__ __forceinline__ bf16x8 cvt(unsigned x0, unsigned x1, G g) {
+        u32x4 r;
+        const float2v zz = {g.zb, g.zb}, ss = {g.s, g.s};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const unsigned x = (i < 2 ? x0 : x1) >> (16 * (i & 1));
+            const float2v q = {(float)(x & 0xffu), (float)((x >> 8) & 0xffu)};                               // v_cvt_f32_ubyte*: exact
+            const float2v v = (q - zz) * ss;                                                                // both exact in fp32; not fused
+            unsigned p;
+            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p) : "v"(v[0]), "v"(v[1]));
+            r[i] = p;
+        }
+        return __builtin_bit_cast(bf16x8, r);
+    }
+};
+
+template <typename TT, int RT, int DEPTH>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i8(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8,
+                                                                     float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
+                                                                     int n_chunks, int n_splits) {
+    typedef typename TT::elem E;
+    constexpr int R = 16 * RT;
+    constexpr int NT = 64 * GEMM_WAVES;
+    constexpr int XV = (R * 32) / NT;              // 16-byte units per thread to stage one A chunk (as k_gemm_skinny)
+    constexpr int NB = DEPTH + 1;
+    constexpr int PC = 5 + XV;                     // memory operations per thread and chunk: 4 code loads + 1 group-data load + the A staging
+    constexpr size_t WCH = 33792, WU = 8192, WS = 32768;   // bytes of one (tile, chunk) block; of one b row inside it; offset of its group data
+    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
+    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
+
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
+    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    const int split = blockIdx.y;
+    const int c0 = (int)((long long)split * n_chunks / n_splits), c1 = (int)((long long)(split + 1) * n_chunks / n_splits);
+    const char *wtile = reinterpret_cast<const char *>(W8) + (size_t)blockIdx.x * n_chunks * WCH;
+    const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)(16 * w + n) * 8;
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
+
+    floatx4 acc[RT];
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+
+    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
+    u32x4 wr[DEPTH][4];
+    u32x2 ws[DEPTH];                               // the chunk's group data of this lane's row: {s0 | s1 << 16, zb0 | zb1 << 16}
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(wr[d][2]), "=v"(wr[d][3]), "=v"(ws[d]));
+    auto load_wb = [&](u32x4 (&dst)[4], int c, int b) {
+        const char *p = wtile + (size_t)c * WCH;
+        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[b]) : "v"(wlane), "s"(p + WU * b) : "memory");
+    };
+    auto load_s = [&](u32x2 &dst, int c) {
+        const char *p = wtile + (size_t)c * WCH + WS;
+        asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
+    };
+    auto stage_xi = [&](int c, int buf, int i) {
+        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
+        const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
+        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        asm volatile("" ::: "memory");
+    };
+    auto load_w = [&](u32x4 (&dst)[4], u32x2 &sdst, int c) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) load_wb(dst, c, b);
+        load_s(sdst, c);
+    };
+    auto stage_x = [&](int c, int buf) {
+#pragma unroll
+        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
+    };
+    auto phase = [&](u32x4 (&cur)[4], u32x2 &cs, int c, int buf) {
+        gemm_wait_younger_deep<DEPTH, PC>(c1 - 1 - c);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
+        // the widening is ordinary VALU code on the loaded registers: re-define them here, behind the counted wait (volatile asm keeps its
+        // order), so that no conversion can be scheduled above the wait while the load is still in flight
+        asm volatile("" : "+v"(cs) : : "memory");
+        const u32x2 gd = cs;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
+            u32x4 r[RT][2];
+            gemm_f4_read_a<RT>(r, a0, a1);
+            asm volatile("" : "+v"(cur[b]) : : "memory");
+            const auto grp = I8Widen<TT>::group(gd, b >> 1);
+            const auto lo = I8Widen<TT>::cvt(cur[b][0], cur[b][1], grp), hi = I8Widen<TT>::cvt(cur[b][2], cur[b][3], grp);
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++) {
+                acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
+                acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, acc[mt]);
+            }
+            if (RT >= 3 && c + DEPTH < c1) {       // 48 / 64 rows: refill per k block (see k_gemm_skinny)
+                load_wb(cur, c + DEPTH, b);
+                if (b < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, b);
+                if (b == 3) load_s(cs, c + DEPTH);                 // (after the group data's last use)
+            }
+        }
+        if (RT < 3 && c + DEPTH < c1) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
+    };
+    if (c0 < c1) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++)
+            if (c0 + d < c1) { load_w(wr[d], ws[d], c0 + d); stage_x(c0 + d, d); }
+        int buf = 0;
+        for (int c = c0; c < c1; c += DEPTH) {
+#pragma unroll
+            for (int d = 0; d < DEPTH; d++)
+                if (c + d < c1) { phase(wr[d], ws[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+        }
+    }
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n; scale and zero point went in with the widening, so ONE rounding and nothing else
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int m = 16 * mt + 4 * g + r;
+            const float v = acc[mt][r];
+            if (out) out[(size_t)m * N + n0 + n] = (E)v;
+            else __hip_atomic_store(&partial[((size_t)split * R + m) * N + n0 + n], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// row-major q [N][K] bytes, z [N][K/128] bytes, s [N][K/128] 16-bit words -> the packed blocks of k_gemm_skinny_i8; one thread moves one
+// 16-byte unit (as k_gemm_pack_f8), the g == 0 thread of k blocks 0 and 2 also that half of its row's group data
+__global__ __launch_bounds__(256) void k_gemm_pack_i8(const uint4 *__restrict__ q, const unsigned char *__restrict__ z, const unsigned short *__restrict__ s,
+                                                      unsigned char *__restrict__ out, int N, int K, int bf16) {
+    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;          // code unit: 16 codes of one row
+    const long long total = (long long)N * K / 16;
+    if (u >= total) return;
+    const int n_chunks = K / GEMM_KC;
+    const long long blk = u >> 11;                                          // 2048 code units per block
+    const int in = (int)(u & 2047), b = in >> 9, tid = in & 511, w = tid >> 6, g = (tid >> 4) & 3, n = tid & 15;
+    const int t = (int)(blk / n_chunks), c = (int)(blk % n_chunks);
+    const long long row = 128LL * t + 16 * w + n, col = 256LL * c + 64 * b + 16 * g;
+    unsigned char *dst = out + blk * 33792;
+    reinterpret_cast<uint4 *>(dst)[in] = q[(row * K + col) / 16];
+    if (g == 0 && (b & 1) == 0) {
+        const int j = b >> 1;
+        const long long grp = row * (K / 128) + 2 * c + j;
+        unsigned short *gdst = reinterpret_cast<unsigned short *>(dst + 32768 + 8 * (16 * w + n));
+        const unsigned zv = z[grp];
+        gdst[j] = s[grp];
+        gdst[2 + j] = (unsigned short)(bf16 ? __float_as_uint((float)zv) >> 16 : 0x6400u | zv);
+    }
+}
+
+template <typename TT, int RT, int DEPTH>
+static hipError_t gemm_i8_launch(dim3 grid, hipStream_t st, const void *A, const void *W8, float *partial, void *out, int K, int N, int splits) {
+    constexpr int lds = (DEPTH + 1) * 16 * RT * GEMM_KC * 2;
+    if constexpr (lds > 65536) {
+        static unsigned long long done = 0ull;                     // per-device (samd_common.h)
+        const hipError_t attr = samd_reserve_lds((const void *)k_gemm_skinny_i8<TT, RT, DEPTH>, lds, &done);
+        if (attr != hipSuccess) return attr;
+    }
+    hipLaunchKernelGGL((k_gemm_skinny_i8<TT, RT, DEPTH>), grid, dim3(64 * GEMM_WAVES), lds, st, (const typename TT::elem *)A, (const unsigned char *)W8,
+                       partial, (typename TT::elem *)out, K, N, K / GEMM_KC, splits);
+    return hipSuccess;
+}
+
+extern "C" {
+
+int samd_gemm_pack_i8(const void *d_q, const void *d_z, const void *d_s, void *d_out, int32_t N, int32_t K, int32_t dtype, void *stream) {
+    if (!d_q || !d_z || !d_s || !d_out || d_q == d_out || d_z == d_out || d_s == d_out || N < GEMM_COLS || N % GEMM_COLS != 0 || K < GEMM_KC ||
+        K % GEMM_KC != 0 || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("samd_gemm_pack_i8: needs N %% 128 == 0, K %% 256 == 0, dtype fp16 or bf16 and distinct buffers"); return SAMD_E_INVALID;
+    }
+    const long long units = (long long)N * K / 16;
+    hipLaunchKernelGGL(k_gemm_pack_i8, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)d_q,
+                       (const unsigned char *)d_z, (const unsigned short *)d_s, (unsigned char *)d_out, N, K, dtype == SAMD_BF16 ? 1 : 0);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_gemm_skinny_i8(const void *d_A, const void *d_W8p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
+                        int32_t dtype, void *stream) {
+    if (!d_A || !d_W8p || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS || N % GEMM_COLS != 0 ||
+        K < GEMM_KC || K % GEMM_KC != 0 || splits < 1 || splits > K / GEMM_KC || (splits == 1 ? !d_out : !d_partial) || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("samd_gemm_skinny_i8: unsupported shape (rows 16/32/48/64, N %% 128 == 0, K %% 256 == 0) or null pointer"); return SAMD_E_INVALID;
+    }
+    const dim3 grid(N / GEMM_COLS, splits);
+    const hipStream_t st = (hipStream_t)stream;
+    float *part = splits == 1 ? nullptr : d_partial;
+    void *out = splits == 1 ? d_out : nullptr;
+#define GO(TT, RT, D) e = gemm_i8_launch<TT, RT, D>(grid, st, d_A, d_W8p, part, out, K, N, splits)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1, 4); else if (rows_pad == 32) GO(TT, 2, 4); else if (rows_pad == 48) GO(TT, 3, 4); else GO(TT, 4, 3); } while (0)
+    hipError_t e;
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
+    if (e != hipSuccess) { samd_set_error("samd_gemm_skinny_i8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================
 // Mixture-of-experts MLP (Qwen3-MoE: HF Qwen3MoeSparseMoeBlock): router, gathered expert gate|up + SiLU, gathered expert down + combine.
 // A sparse layer streams a data-dependent subset of E small matrices, each for its own subset of rows; the choice is made on the device
 // and every launch has a fixed grid, so a decode step stays one hipGraph replay.

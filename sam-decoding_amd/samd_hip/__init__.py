@@ -185,6 +185,8 @@ _PROTOS = {
     "samd_gemm_skinny_f4": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "samd_gemm_pack_i4": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),
     "samd_gemm_skinny_i4": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
+    "samd_gemm_pack_i8": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),
+    "samd_gemm_skinny_i8": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "samd_moe_workspace_layout": (_I32, [_I32]),
     "samd_moe_workspace": (_I64, [_I32, _I32, _I32, _I32, _I32]),
     "samd_moe_pack_experts": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP]),

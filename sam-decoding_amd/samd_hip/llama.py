@@ -20,6 +20,7 @@ from . import (F16, BF16, MAX_DRAFT, TILE_ROWS, QkvEpilogue, SamdError, Session,
 from . import fp8 as F8
 from . import mxfp4 as MX
 from . import int4 as I4
+from . import int8 as I8
 from . import moe as MOE
 
 
@@ -29,25 +30,27 @@ def _env_weight_format(weight_format):
 
 
 def _weight_format(weight_format, weights, dtype):
-    """"fp8", "fp8b128", "mxfp4", "int4g128" or None (the model dtype; the plain word "int4" stays an unknown format: the name carries the group size).  Projections that arrive as float8_e4m3fn (an FP8 checkpoint), as packed e2m1 bytes
+    """"fp8", "fp8b128", "mxfp4", "int4g128", "int8g128" or None (the model dtype; the plain word "int4" stays an unknown format: the name carries the group size).  Projections that arrive as float8_e4m3fn (an FP8 checkpoint), as packed e2m1 bytes
     (an MXFP4 checkpoint: uint8 / float4_e2m1fn_x2 [N, K/2]) or as 4-bit codes with zero points and group scales (an AWQ / GPTQ checkpoint:
     uint8 [N, K/2] beside k + "_z" and k + "_s") make the runner FP8 / MXFP4 / INT4 by themselves.  float8_e4m3fn projections beside k + "_sinv"
-    (fp32, one scale per 128 x 128 block) are block-scaled FP8 and make the runner "fp8b128": the _sinv keys tell them from per-row "fp8"."""
+    (fp32, one scale per 128 x 128 block) are block-scaled FP8 and make the runner "fp8b128": the _sinv keys tell them from per-row "fp8".
+    8-bit codes with zero points and group scales (a GPTQ 8-bit checkpoint: uint8 [N, K] beside k + "_z8" and k + "_s8") make it "int8g128"."""
+    has_i8 = any(k + "_z8" in l for l in weights["layers"] for k in I8.PROJECTIONS)
     has_f8b = any(k + "_sinv" in l for l in weights["layers"] for k in F8.PROJECTIONS)
     has_f8 = any(l[k].dtype == torch.float8_e4m3fn and k + "_sinv" not in l for l in weights["layers"] for k in F8.PROJECTIONS if k in l)
     has_i4 = any(k + "_z" in l for l in weights["layers"] for k in I4.PROJECTIONS)
-    has_f4 = any(_is_f4_tensor(l[k]) and k + "_z" not in l for l in weights["layers"] for k in MX.PROJECTIONS if k in l)
+    has_f4 = any(_is_f4_tensor(l[k]) and k + "_z" not in l and k + "_z8" not in l for l in weights["layers"] for k in MX.PROJECTIONS if k in l)
     names = {torch.float16: ("fp16", "float16", "half"), torch.bfloat16: ("bf16", "bfloat16")}.get(dtype, ())
     if weight_format is None:
-        fmt = "fp8" if has_f8 else ("fp8b128" if has_f8b else ("mxfp4" if has_f4 else ("int4g128" if has_i4 else None)))
-    elif weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128"):
+        fmt = "fp8" if has_f8 else ("fp8b128" if has_f8b else ("mxfp4" if has_f4 else ("int4g128" if has_i4 else ("int8g128" if has_i8 else None))))
+    elif weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128", "int8g128"):
         fmt = weight_format
     elif weight_format == dtype or (isinstance(weight_format, str) and weight_format.lower() in names):
         fmt = None
     else:
         hint = " (the AWQ / GPTQ format is spelled 'int4g128': 4-bit codes in groups of 128, the only group size the kernel has)" \
             if weight_format == "int4" else ""
-        raise SamdError(f"weight_format {weight_format!r}: expected None, 'fp8', 'mxfp4', 'int4g128', 'fp8b128' or the model dtype ({dtype}){hint}")
+        raise SamdError(f"weight_format {weight_format!r}: expected None, 'fp8', 'mxfp4', 'int4g128', 'fp8b128' or the model dtype ({dtype}), or 'int8g128'{hint}")
     if has_f8 and fmt != "fp8":
         raise SamdError(f"the weights carry float8_e4m3fn projections; weight_format {weight_format!r} would need them dequantised (pass None or 'fp8')")
     if has_f8b and fmt != "fp8b128":
@@ -56,6 +59,8 @@ def _weight_format(weight_format, weights, dtype):
         raise SamdError(f"the weights carry MXFP4 projections; weight_format {weight_format!r} would need them dequantised (pass None or 'mxfp4')")
     if has_i4 and fmt != "int4g128":
         raise SamdError(f"the weights carry INT4 (AWQ / GPTQ) projections; weight_format {weight_format!r} would need them dequantised (pass None or 'int4g128')")
+    if has_i8 and fmt != "int8g128":
+        raise SamdError(f"the weights carry INT8 (GPTQ) projections; weight_format {weight_format!r} would need them dequantised (pass None or 'int8g128')")
     return fmt
 
 
@@ -215,7 +220,12 @@ class LlamaRunner:
         # (samd_gemm_pack_f8's packed codes, the checkpoint's own scale table); again everything FP8 implies holds
         f8, f4, i4 = self.weight_format == "fp8", self.weight_format == "mxfp4", self.weight_format == "int4g128"
         f8b = self.weight_format == "fp8b128"
-        quant = f8 or f4 or i4 or f8b
+        # weight_format "int8g128": the same four projections as GPTQ 8-bit codes with one scale (model dtype) and one zero point per 128 along K
+        # (samd_hip/int8.py), streamed by samd_gemm_skinny_i8 only; again everything FP8 implies holds
+        i8 = self.weight_format == "int8g128"
+        quant = f8 or f4 or i4 or f8b or i8
+        if i8 and not native_gemm:
+            raise SamdError("INT8 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'int8g128'")
         if f8b and not native_gemm:
             raise SamdError("FP8 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'fp8b128'")
         if f8b:                                                  # shapes the kernel cannot run, by projection, before any device work
@@ -391,9 +401,33 @@ class LlamaRunner:
             out = torch.empty(I4.packed_bytes(N, K), dtype=torch.uint8, device=self.device)
             check(lib().samd_gemm_pack_i4(_ptr(q), _ptr(z), _ptr(sc), _ptr(out), N, K, self.dt, current_stream()))
             return out
+        def pack_i8(l, k):
+            """projection k in samd_gemm_pack_i8's form (8-bit codes with their group scales and zero points inline): quantised on load per
+            group of 128 (uncalibrated) unless the checkpoint brought its own (q, z, s), whose scales are taken in the model dtype (a bf16
+            runner rounds fp16 scales once) and checked; the model-dtype matrix is dropped as soon as it is packed"""
+            t = l[k]
+            if k + "_z8" in l:
+                q, z, sc = I8.fuse_int8([(t, l.pop(k + "_z8"), l.pop(k + "_s8"))], self.device, dtype)
+            else:
+                if t.shape[0] % 128 != 0 or t.shape[1] % 256 != 0:
+                    raise SamdError(f"INT8 projection {k} of shape {tuple(t.shape)}: the INT8 kernel needs N % 128 == 0 and K % 256 == 0")
+                q, z, sc = I8.quantize_groups(t, dtype)
+            I8.check_groups(q, z, sc, dtype, k)
+            N, K = q.shape
+            l[k] = torch.empty((N, K), dtype=torch.uint8, device="meta")
+            del t
+            out = torch.empty(I8.packed_bytes(N, K), dtype=torch.uint8, device=self.device)
+            check(lib().samd_gemm_pack_i8(_ptr(q), _ptr(z), _ptr(sc), _ptr(out), N, K, self.dt, current_stream()))
+            return out
         # packed_lm_head: a draft head shares the base model's lm_head, packed copy included
         layers = []
         for l in weights["layers"]:
+            if i8:
+                lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
+                for k in I8.PROJECTIONS:
+                    lp[k + "_i8"] = pack_i8(l, k)
+                layers.append(lp)
+                continue
             if i4:
                 lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
                 for k in I4.PROJECTIONS:
@@ -563,8 +597,12 @@ class LlamaRunner:
                 for k in I4.PROJECTIONS:
                     rep["packed_" + k + "_i4"] = sum(nbytes(l[k + "_i4"]) * 16 // 17 for l in self.wp["layers"])
                 rep["int4_group_data"] = sum(nbytes(l[k + "_i4"]) // 17 for l in self.wp["layers"] for k in I4.PROJECTIONS)
+            if self.weight_format == "int8g128":                     # one buffer per projection: 32 KiB of codes, then their 1 KiB of group data
+                for k in I8.PROJECTIONS:
+                    rep["packed_" + k + "_i8"] = sum(nbytes(l[k + "_i8"]) * 32 // 33 for l in self.wp["layers"])
+                rep["int8_group_data"] = sum(nbytes(l[k + "_i8"]) // 33 for l in self.wp["layers"] for k in I8.PROJECTIONS)
         rep["total"] = sum(rep.values())
-        if self.weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128"):
+        if self.weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128", "int8g128"):
             rep["weight_format"] = self.weight_format
         rep["expert_format"] = self.expert_format                # None: experts (if any) in the model dtype; packed_moe_* are the bytes held
         return rep
@@ -670,6 +708,11 @@ class LlamaRunner:
         ("GEMM") or GPTQ modules -- int32 `qweight` / `qzeros` and a floating `scales` -- is imported as it is, by the layout its
         config.quantization_config names, and makes the runner "int4g128" by itself (samd_hip/int4.py: group sizes, zero-point conventions and what
         raises).  A bf16 runner rounds the checkpoint's fp16 scales once to bf16.
+        "int8g128" quantises them per group of 128 with an 8-bit zero point (no calibration: for benches and tests); a module whose seven
+        projections per layer are all 8-bit GPTQ modules (the `...-GPTQ-Int8` releases: bits 8 by config.quantization_config, by the module's
+        own `bits`, or by qweight's shape [K/4, N]) is imported as it is through int8.linear_int8 and makes the runner "int8g128" by itself
+        (samd_hip/int8.py: group sizes, zero-point conventions and what raises); a mix of 8-bit and 4-bit or plain projections raises, and so
+        does a module with sparse layers that carries 8-bit projections or experts (nothing is dequantised silently).
         expert_format (default: env SAMD_EXPERT_FORMAT, unset = the model dtype; models with sparse layers only): "mxfp4" quantises the EXPERTS
         of every sparse layer on load (uncalibrated: for benches and tests); router, attention, dense MLP layers, embedding and lm_head stay in
         the model dtype.  A module whose sparse layers carry 4-bit expert tensors with their block scales (samd_hip/moe.py has the convention)
@@ -701,7 +744,16 @@ class LlamaRunner:
                  ("mlp", "up_proj"), ("mlp", "down_proj"))
         linears = [(f"layers.{i}.{a}.{b}", getattr(getattr(lyr, a), b)) for i, lyr in enumerate(m.layers) for a, b in parts
                    if hasattr(getattr(lyr, a), b)]               # (a sparse layer's MLP has no gate / up / down projections of its own)
-        ckpt_i4 = I4.checkpoint_is_int4(linears)                 # AWQ / GPTQ modules (qweight / qzeros / scales, no `weight`)
+        qcfg = I4.quant_config(getattr(lm, "config", None))
+        # 8-bit GPTQ modules are decided first: they carry qweight / qzeros / scales too, so the INT4 test below is true for them
+        if any(cls._hf_sparse_layers(m.layers)):
+            for i, lyr in enumerate(m.layers):
+                for n, mod in lyr.named_modules():
+                    if n and I8.is_int8_module(mod, qcfg):
+                        raise SamdError(f"layers.{i}.{n}: an 8-bit GPTQ module in a mixture-of-experts model: 8-bit projections and experts are "
+                                        "not supported there (weight_format 'int8g128' covers dense models only, and nothing is dequantised silently)")
+        ckpt_i8 = I8.checkpoint_is_int8(linears, qcfg)           # all seven projections of every layer, or a SamdError for a mix
+        ckpt_i4 = (not ckpt_i8) and I4.checkpoint_is_int4(linears)   # AWQ / GPTQ modules (qweight / qzeros / scales, no `weight`)
         # a module with block-scaled FP8 EXPERTS (the official Qwen3-MoE FP8 checkpoints) is not a weight_format "fp8" one: its FP8 attention
         # and dense-MLP projections are dequantised once at import (the docstring).  Decided before checkpoint_is_fp8, which rejects block scales
         layer_f8 = [cls._hf_experts_are_fp8(lyr, i) for i, lyr in enumerate(m.layers)]
@@ -709,7 +761,7 @@ class LlamaRunner:
         qcfg8 = getattr(getattr(lm, "config", None), "quantization_config", None)
         # a module WITHOUT sparse layers whose projections are all block-scaled FP8 (the dense Qwen3-*-FP8 checkpoints) is imported as it is,
         # codes and scales untouched, and the runner is "fp8b128" by itself; modules with sparse layers are left to the branches above
-        ckpt_f8b = (not ckpt_i4) and (not moe_f8_dense) and not any(cls._hf_sparse_layers(m.layers)) and F8.checkpoint_is_fp8_block(linears, qcfg8)
+        ckpt_f8b = (not ckpt_i4) and (not ckpt_i8) and (not moe_f8_dense) and not any(cls._hf_sparse_layers(m.layers)) and F8.checkpoint_is_fp8_block(linears, qcfg8)
         if ckpt_f8b:
             if weight_format not in (None, "fp8b128"):
                 raise SamdError(f"the module carries block-scaled FP8 projections; weight_format {weight_format!r} would need them dequantised "
@@ -718,9 +770,8 @@ class LlamaRunner:
                 N, K = lin.weight.shape
                 if N % 128 != 0 or K % 256 != 0:
                     raise SamdError(f"{name}: a block-scaled FP8 projection of shape ({N}, {K}); the kernel needs N % 128 == 0 and K % 256 == 0")
-        ckpt_f8 = (not ckpt_i4) and (not moe_f8_dense) and (not ckpt_f8b) and F8.checkpoint_is_fp8(linears)
-        ckpt_f4 = (not ckpt_i4) and MX.checkpoint_is_mxfp4(linears)
-        qcfg = I4.quant_config(getattr(lm, "config", None))
+        ckpt_f8 = (not ckpt_i4) and (not ckpt_i8) and (not moe_f8_dense) and (not ckpt_f8b) and F8.checkpoint_is_fp8(linears)
+        ckpt_f4 = (not ckpt_i4) and (not ckpt_i8) and MX.checkpoint_is_mxfp4(linears)
         if F8.is_fp8_dtype(lm.lm_head.weight.dtype) or F8.is_fp8_dtype(m.embed_tokens.weight.dtype):
             raise SamdError("FP8 embedding / lm_head weights are not supported: they stay in the model dtype")
         if _is_f4_tensor(lm.lm_head.weight) or _is_f4_tensor(m.embed_tokens.weight):
@@ -830,6 +881,14 @@ class LlamaRunner:
                     own = a if k in ("wqkv", "wo") else f
                     lw[k], lw[k + "_z"], lw[k + "_s"] = I4.fuse_int4(
                         [I4.linear_int4(getattr(own, x), f"layers.{len(layers)}.{x}", config=qcfg) for x in names], dev, dtype)
+                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
+                continue
+            if ckpt_i8:                                          # canonical (q, z, s) of the 8-bit GPTQ modules; the runner checks and packs them
+                lw = {}
+                for k, names in (("wqkv", ("q_proj", "k_proj", "v_proj")), ("wo", ("o_proj",)), ("wgu", ("gate_proj", "up_proj")), ("wdown", ("down_proj",))):
+                    own = a if k in ("wqkv", "wo") else f
+                    lw[k], lw[k + "_z8"], lw[k + "_s8"] = I8.fuse_int8(
+                        [I8.linear_int8(getattr(own, x), f"layers.{len(layers)}.{x}", config=qcfg) for x in names], dev, dtype)
                 layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
                 continue
             if ckpt_f4:                                          # (q, e8) as the checkpoint has them; the runner checks and packs them
@@ -1070,7 +1129,7 @@ class LlamaRunner:
         """bytes of weights one decode step streams from HBM (the embedding table is only gathered), tensor by tensor in its own format
         (an FP8 projection: one byte per weight + its fp32 column scales; a block-scaled FP8 projection: one byte per weight + 4 bytes per
         128 x 128 block; an MXFP4 projection: half a byte per weight + one scale byte per 32; an
-        INT4 projection: half a byte per weight + 4 bytes of scale and zero point per 128).
+        INT4 projection: half a byte per weight + 4 bytes of scale and zero point per 128; an INT8 projection: one byte per weight + the same 4 bytes per 128).
         A sparse (mixture-of-experts) layer counts `experts` of its experts in the format they are held in (MXFP4 experts: elements + block
         scales; block-scaled FP8 experts: one byte per weight + one fp32 scale per 128 x 128 block -- the packed table repeats each scale for
         the two 64-row halves of its block, another 4 bytes per 16384 weights;
@@ -1079,8 +1138,8 @@ class LlamaRunner:
         n_act = self.shape.top_k if experts is None else int(experts)
         nb = lambda t: t.numel() * t.element_size() if t.dim() != 3 else t[0].numel() * t.element_size() * min(n_act, t.shape[0])
         n = nb(self.w["lm_head"]) + nb(self.w["norm"])
-        if self.weight_format in ("mxfp4", "int4g128"):
-            sfx = "_f4" if self.weight_format == "mxfp4" else "_i4"
+        if self.weight_format in ("mxfp4", "int4g128", "int8g128"):
+            sfx = {"mxfp4": "_f4", "int4g128": "_i4", "int8g128": "_i8"}[self.weight_format]
             for l, lp in zip(self.w["layers"], self.wp["layers"]):
                 n += sum(nb(t) for k, t in l.items() if k not in MX.PROJECTIONS) + sum(nb(lp[k + sfx]) for k in MX.PROJECTIONS)
             return n
@@ -1157,11 +1216,15 @@ class LlamaRunner:
             sp = 1 if (fused or is_head) else L.samd_gemm_splits(n, k, RP)
             return C.byref(Warm(wp.data_ptr(), n, k, sp, self.warm_kb, self.warm_delay, self.warm_where))
 
-        def gemm(a, w, wp, out, wg=None, f8=None, f4=None, i4=None, f8b=None):
+        def gemm(a, w, wp, out, wg=None, f8=None, f4=None, i4=None, f8b=None, i8=None):
             """out = a @ w.T (wp = w in the packed 128-column-tile layout, wg = w group-major: whichever exists; f8 = (packed e4m3fn, column
-            scales) of an FP8 runner; f8b = (packed e4m3fn, fp32 block-scale table) of a block-scaled FP8 runner; f4 = the packed elements + block scales of an MXFP4 runner; i4 = the packed codes + group data of an INT4 runner); returns (operand for the consumer,
+            scales) of an FP8 runner; f8b = (packed e4m3fn, fp32 block-scale table) of a block-scaled FP8 runner; f4 = the packed elements + block scales of an MXFP4 runner; i4 / i8 = the packed codes + group data of an INT4 / INT8 runner); returns (operand for the consumer,
             n_partials, partial_stride)."""
             n, k = w.shape
+            if i8 is not None:                                    # (RP <= 64 here, as for FP8; the INT8 runner's own packed buffer)
+                sp = L.samd_gemm_splits(n, k, RP)
+                check(L.samd_gemm_skinny_i8(_ptr(a), _ptr(i8), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
+                return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
             if i4 is not None:                                    # (RP <= 64 here, as for FP8; the INT4 runner's own packed buffer)
                 sp = L.samd_gemm_splits(n, k, RP)
                 check(L.samd_gemm_skinny_i4(_ptr(a), _ptr(i4), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
@@ -1225,7 +1288,7 @@ class LlamaRunner:
                     _ptr(b["x"] if raw_in else b["h"]), _ptr(wp["wqkv64"]), RP, s.hidden, _ptr(b["cs"]), _ptr(d_L), _ptr(d_n),
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), s.heads, s.kv_heads, s.head_dim, self.max_len, dt, st))
             else:
-                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], f8=wp.get("wqkv_f8"), f8b=wp.get("wqkv_f8b"), f4=wp.get("wqkv_f4"), i4=wp.get("wqkv_i4"))
+                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], f8=wp.get("wqkv_f8"), f8b=wp.get("wqkv_f8b"), f4=wp.get("wqkv_f4"), i4=wp.get("wqkv_i4"), i8=wp.get("wqkv_i8"))
             if block:
                 # RoPE + K row / V^T column write + tree attention + merge of the tile partials: one launch (csrc/attn_kernels.hip)
                 check(L.samd_attention_block(_ptr(src), n_p, stride, _ptr(b["cs"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R,
@@ -1257,7 +1320,7 @@ class LlamaRunner:
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R, s.heads,
                     s.kv_heads, s.head_dim, self.max_len, _ptr(d_mask), _ptr(d_L), _ptr(d_n), self.scale,
                     _ptr(b["ws"]), b["ws_bytes"], hint(w["wo"], wp.get("wo")), st))
-            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"), f8b=wp.get("wo_f8b"), f4=wp.get("wo_f4"), i4=wp.get("wo_i4"))
+            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"), f8b=wp.get("wo_f8b"), f4=wp.get("wo_f4"), i4=wp.get("wo_i4"), i8=wp.get("wo_i8"))
             check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(src), _ptr(w["ln2"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, n_p, stride,
                                       None, st))           # (no warm-up hint: gate|up is packed group-major, the hint describes 128-column tiles)
             if "moe_gu" in wp:
@@ -1272,9 +1335,9 @@ class LlamaRunner:
             if wp.get("wgu") is not None and RP <= self.native_gemm_max_rows:
                 check(L.samd_gemm_pairs_silu(_ptr(b["h"]), _ptr(wp["wgu"]), RP, s.inter, s.hidden, _ptr(b["act"]), dt, st))
             else:
-                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"), f8b=wp.get("wgu_f8b"), f4=wp.get("wgu_f4"), i4=wp.get("wgu_i4"))     # wgu is only ever packed for the fused form (or FP8)
+                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"), f8b=wp.get("wgu_f8b"), f4=wp.get("wgu_f4"), i4=wp.get("wgu_i4"), i8=wp.get("wgu_i8"))     # wgu is only ever packed for the fused form (or FP8)
                 check(L.samd_silu_mul(_ptr(src), _ptr(b["act"]), R, s.inter, dt, n_p, stride, st))
-            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"), f8b=wp.get("wdown_f8b"), f4=wp.get("wdown_f4"), i4=wp.get("wdown_i4"))
+            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"), f8b=wp.get("wdown_f8b"), f4=wp.get("wdown_f4"), i4=wp.get("wdown_i4"), i8=wp.get("wdown_i8"))
         check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(delta), _ptr(self.w["norm"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, dn, dstride,
                                   hint(self.w["lm_head"], self.wp["lm_head"] if self.wp else None, is_head=True), st))
         # (for a draft head the call above only folds the last projection into the residual stream; its norm output is unused)

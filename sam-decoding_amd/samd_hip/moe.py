@@ -87,7 +87,7 @@ def check_shape(hidden, moe_inter, n_experts, top_k):
 
 def reject_unsupported(weight_format=None, native_gemm=True, draft_head=False):
     """what a runner with sparse layers does not offer; raises before any device work"""
-    if weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128"):
+    if weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128", "int8g128"):
         raise SamdError(f"mixture-of-experts models are not available with weight_format '{weight_format}': quantised experts are not supported")
     if not native_gemm:
         raise SamdError("mixture-of-experts layers exist only in the streaming kernels' packed form: native_gemm=False is not available")

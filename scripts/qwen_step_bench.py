@@ -1,5 +1,5 @@
 """qwen_step_bench.py -- graph-replay time of one verify forward per row bucket (L = 800 cached keys) for random-init Llama-3-8B, Qwen2.5-7B and
-Qwen3-8B (and Vicuna-7B: --models vicuna-7b) at full depth, in fp16 and with FP8, MXFP4 or INT4 projections (--formats fp16,fp8,mxfp4,int4g128).  Qwen runs the eight-launch layer with samd_rope_kv_write_epi (q|k|v bias / q-k
+Qwen3-8B (and Vicuna-7B: --models vicuna-7b) at full depth, in fp16 and with FP8, MXFP4, INT4 or INT8 projections (--formats fp16,fp8,mxfp4,int4g128,int8g128).  Qwen runs the eight-launch layer with samd_rope_kv_write_epi (q|k|v bias / q-k
 norm); Llama-3-8B is the yardstick.   usage: python scripts/qwen_step_bench.py [--reps 30] [--models llama3-8b,qwen2.5-7b,qwen3-8b]"""
 import argparse, gc, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,8 +50,8 @@ def main():
     a = ap.parse_args()
     for name in a.models.split(","):
         for fmt in a.formats.split(","):
-            if fmt not in ("fp16", "fp8", "mxfp4", "int4g128"):
-                raise SystemExit(f"--formats: unknown format {fmt!r} (fp16, fp8, mxfp4, int4g128)")
+            if fmt not in ("fp16", "fp8", "mxfp4", "int4g128", "int8g128"):
+                raise SystemExit(f"--formats: unknown format {fmt!r} (fp16, fp8, mxfp4, int4g128, int8g128)")
             runner = LlamaRunner.random_init(MODELS[name], 2048, torch.float16, seed=0, weight_format=fmt if fmt != "fp16" else None)
             sess = samd_hip.Session(4096)
             sess.reset()
