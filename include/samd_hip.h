@@ -792,6 +792,43 @@ int samd_moe_gate_up_silu_f8(const void *d_h, const void *d_Wgu8, const void *d_
                              int32_t top_k, void *d_act, int32_t dtype, void *stream);
 int samd_moe_down_combine_f8(const void *d_act, const void *d_Wdown8, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
                              int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream);
+/* The mixture-of-experts MLP over MANY rows at once (a prompt in one pass): 1 <= rows <= 4096, padded to a multiple of 64 inside (every
+ * buffer holds the padded rows); only rows < *d_n count.  The shapes are those of the calls above.  An expert's list may be longer than a
+ * 64-row tile and is served in several: the lists are followed by a tile table, and an expert GEMM workgroup is the 64-row tile of the
+ * calls above with its expert and its list taken from a tile record -- the same weight stream, MFMA sequence, epilogues and roundings, so
+ * every row gets the bits the <= 64-row calls give it, whatever shares the launch.  Fixed grids, counts read on the device, capturable; the
+ * <= 64-row calls, their workspace and their errors are untouched.
+ *   samd_moe_wide_workspace    bytes of d_ws: the routing part, then y [rows_pad * top_k][hidden] (model dtype); SAMD_E_INVALID (< 0) with
+ *                              the error text for rows or a shape outside the above.
+ *   samd_moe_wide_workspace_layout  for tests and profiling, in int32 words from the head of d_ws unless said otherwise.  Word 0 = number of
+ *                              tiles, word 1 = number of active experts.  field 0 = first word of the active experts (ascending), 1 = of
+ *                              their entry counts, 2 = of their first entry's place in the entry array, 3 = of the tile table, 4 = words
+ *                              per tile record {expert, first entry, entries <= 64} (the tiles of one expert adjacent, experts ascending),
+ *                              5 = first word of the entry array (p = row * top_k + slot, expert by expert, ascending within an expert),
+ *                              6 = words of the routing part for (rows, top_k), 7 = BYTE offset of y, 8 = the cap on rows, 9 = records
+ *                              the tile table holds.  Another field: -1.
+ *   samd_moe_wide_route        samd_moe_route's router over rows_pad rows (one workgroup per row; the arithmetic, the tie rule and the one
+ *                              rounding are that kernel's): d_topk_idx int32 [rows_pad][top_k], d_topk_w [rows_pad][top_k].  No lists.
+ *   samd_moe_wide_lists        lists and tile table from d_topk_idx; samd_moe_lists' ignore rules (rows >= *d_n, indices outside
+ *                              [0, n_experts), an expert repeated within a row).  Fixed orders: no atomic decides a position.
+ *   samd_moe_wide_gate_up_silu d_act [rows_pad * top_k][moe_inter] as samd_moe_gate_up_silu.  Grid (moe_inter / 64, min(n_experts,
+ *                              rows_pad * top_k) + rows_pad * top_k / 64): the bound on sum_e ceil(count_e / 64); workgroups past the tile
+ *                              count exit at once.
+ *   samd_moe_wide_down_combine as samd_moe_down_combine, d_out [rows_pad][hidden]; rows >= *d_n are zero.
+ *   expert_format              what d_Wgu / d_Wdown hold: 0 the model dtype (samd_moe_pack_experts), 1 mxfp4 (the _f4 calls' buffer),
+ *                              2 int4g128 (the _i4 calls'), 3 fp8b128 (the _f8 calls'; hidden and moe_inter <= 16384).
+ * SAMD_E_INVALID with the error text, before any device work: rows < 1 or > 4096, an unknown expert_format, a shape outside the above,
+ * a null pointer. */
+int64_t samd_moe_wide_workspace_layout(int32_t field, int32_t rows, int32_t top_k);
+int64_t samd_moe_wide_workspace(int32_t rows, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, int32_t dtype);
+int samd_moe_wide_route(const void *d_h, const void *d_router, const int32_t *d_n, int32_t rows, int32_t hidden, int32_t n_experts, int32_t top_k,
+                        int32_t norm_topk, int32_t *d_topk_idx, void *d_topk_w, int32_t dtype, void *stream);
+int samd_moe_wide_lists(const int32_t *d_topk_idx, const int32_t *d_n, int32_t rows, int32_t n_experts, int32_t top_k, void *d_ws, void *stream);
+int samd_moe_wide_gate_up_silu(const void *d_h, const void *d_Wgu, const void *d_ws, int32_t rows, int32_t hidden, int32_t moe_inter, int32_t n_experts,
+                               int32_t top_k, int32_t expert_format, void *d_act, int32_t dtype, void *stream);
+int samd_moe_wide_down_combine(const void *d_act, const void *d_Wdown, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                               int32_t rows, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, int32_t expert_format, void *d_out,
+                               int32_t dtype, void *stream);
 
 /* ---- scripted verifier (tests, smoke and bench only): replaces the LM arg-max of every draft node by
  * the next token of a target stream while the node's context (committed history + root->node path) is a

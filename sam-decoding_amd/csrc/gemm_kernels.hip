@@ -2166,6 +2166,16 @@ int samd_gemm_skinny_i8(const void *d_A, const void *d_W8p, int32_t rows_pad, in
 #define MOE_WS_LIST (MOE_WS_COUNT + MOE_MAX_E)
 #define MOE_WS_INTS (MOE_WS_LIST + MOE_MAX_E * MOE_MAX_ROWS)
 #define MOE_WS_Y_OFF (((MOE_WS_INTS * 4 + 255) / 256) * 256)
+// the wide calls' routing workspace (samd_moe_wide_*, at the end of the mixture-of-experts sections): fixed word offsets, so that the
+// expert GEMMs above read a tile record without knowing the shape
+#define MOEW_MAX_ROWS 4096
+#define MOEW_TILE_INTS 3
+#define MOEW_MAX_TILES (MOE_MAX_E + MOEW_MAX_ROWS * MOE_MAX_K / MOE_MAX_ROWS)
+#define MOEW_WS_ACTIVE 16
+#define MOEW_WS_COUNT (MOEW_WS_ACTIVE + MOE_MAX_E)
+#define MOEW_WS_OFFSET (MOEW_WS_COUNT + MOE_MAX_E)
+#define MOEW_WS_TILE (MOEW_WS_OFFSET + MOE_MAX_E)
+#define MOEW_WS_ENTRY (MOEW_WS_TILE + MOEW_TILE_INTS * MOEW_MAX_TILES)
 
 // Router logits stay in fp32 (HF's low-precision F.linear rounds them to the model dtype, which manufactures exact ties: a documented
 // difference).  Rows >= *d_n get index -1 and weight 0: they route nowhere.
@@ -2303,7 +2313,7 @@ __global__ __launch_bounds__(MOE_MAX_E) void k_moe_lists(const int *__restrict__
 // are single values defined once and every load is an in-out operand of that value, as in k_gemm_skinny_f4.
 // GU: W = gate|up tiles (64 gate | 64 up columns), A = h, epilogue silu(gate) * up -> out[p][N / 2]; otherwise W = down tiles, A = act,
 // out[p][N] = the product rounded to the model dtype.
-template <typename TT, int RT, bool GU>
+template <typename TT, int RT, bool GU, bool WIDE = false>          // WIDE: a tile record of the wide workspace names the expert and its list
 __device__ __forceinline__ void moe_expert_gemm(const typename TT::elem *__restrict__ A, const typename TT::elem *__restrict__ W, const int *__restrict__ ws,
                                                 typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
     typedef typename TT::elem E;
@@ -2320,11 +2330,13 @@ __device__ __forceinline__ void moe_expert_gemm(const typename TT::elem *__restr
 
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
     const int slot_a = blockIdx.y;
-    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts
-    const int expert = ws[MOE_WS_ACTIVE + slot_a];
-    int cnt = ws[MOE_WS_COUNT + slot_a];
+    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts (WIDE: of tiles; ws[0] = the tile count)
+    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
+    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
+    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
     cnt = cnt > R ? R : cnt;
-    if (tid < MOE_MAX_ROWS) lst[tid] = ws[MOE_WS_LIST + MOE_MAX_ROWS * slot_a + (tid < cnt ? tid : 0)];
+    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
+    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
     __syncthreads();
     // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
     int srow[XV];
@@ -2641,7 +2653,7 @@ int samd_moe_down_combine(const void *d_act, const void *d_Wdown, const int32_t 
 // ================================================================================================
 template <int RT> struct Moe4Depth { static constexpr int value = RT == 1 ? 8 : RT == 3 ? 2 : 3; };
 
-template <typename TT, int RT, bool GU>
+template <typename TT, int RT, bool GU, bool WIDE = false>          // WIDE: a tile record of the wide workspace names the expert and its list
 __device__ __forceinline__ void moe4_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
                                                  typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
     typedef typename TT::elem E;
@@ -2658,11 +2670,13 @@ __device__ __forceinline__ void moe4_expert_gemm(const typename TT::elem *__rest
 
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
     const int slot_a = blockIdx.y;
-    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts
-    const int expert = ws[MOE_WS_ACTIVE + slot_a];
-    int cnt = ws[MOE_WS_COUNT + slot_a];
+    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts (WIDE: of tiles; ws[0] = the tile count)
+    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
+    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
+    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
     cnt = cnt > R ? R : cnt;
-    if (tid < MOE_MAX_ROWS) lst[tid] = ws[MOE_WS_LIST + MOE_MAX_ROWS * slot_a + (tid < cnt ? tid : 0)];
+    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
+    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
     __syncthreads();
     // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
     int srow[XV];
@@ -2891,7 +2905,7 @@ int samd_moe_down_combine_f4(const void *d_act, const void *d_Wdown4, const int3
 // ================================================================================================
 template <int RT> struct MoeI4Depth { static constexpr int value = RT == 1 ? 8 : RT == 3 ? 2 : 3; };
 
-template <typename TT, int RT, bool GU>
+template <typename TT, int RT, bool GU, bool WIDE = false>          // WIDE: a tile record of the wide workspace names the expert and its list
 __device__ __forceinline__ void moe_i4_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
                                                  typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
     typedef typename TT::elem E;
@@ -2908,11 +2922,13 @@ __device__ __forceinline__ void moe_i4_expert_gemm(const typename TT::elem *__re
 
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
     const int slot_a = blockIdx.y;
-    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts
-    const int expert = ws[MOE_WS_ACTIVE + slot_a];
-    int cnt = ws[MOE_WS_COUNT + slot_a];
+    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts (WIDE: of tiles; ws[0] = the tile count)
+    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
+    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
+    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
     cnt = cnt > R ? R : cnt;
-    if (tid < MOE_MAX_ROWS) lst[tid] = ws[MOE_WS_LIST + MOE_MAX_ROWS * slot_a + (tid < cnt ? tid : 0)];
+    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
+    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
     __syncthreads();
     // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
     int srow[XV];
@@ -3150,7 +3166,7 @@ int samd_moe_down_combine_i4(const void *d_act, const void *d_Wdown4, const int3
 #define MOE8_MAX_KB 128                // k blocks of 128 per row: K <= 16384
 template <int RT> struct Moe8Depth { static constexpr int value = RT == 4 ? 3 : 4; };
 
-template <typename TT, int RT, bool GU>
+template <typename TT, int RT, bool GU, bool WIDE = false>          // WIDE: a tile record of the wide workspace names the expert and its list
 __device__ __forceinline__ void moe8_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8, const float *__restrict__ stab,
                                                  const int *__restrict__ ws, typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
     typedef typename TT::elem E;
@@ -3168,12 +3184,14 @@ __device__ __forceinline__ void moe8_expert_gemm(const typename TT::elem *__rest
 
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
     const int slot_a = blockIdx.y;
-    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts
-    const int expert = ws[MOE_WS_ACTIVE + slot_a];
-    int cnt = ws[MOE_WS_COUNT + slot_a];
+    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts (WIDE: of tiles; ws[0] = the tile count)
+    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
+    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
+    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
     cnt = cnt > R ? R : cnt;
     const size_t tile = (size_t)expert * (N / GEMM_COLS) + blockIdx.x;
-    if (tid < MOE_MAX_ROWS) lst[tid] = ws[MOE_WS_LIST + MOE_MAX_ROWS * slot_a + (tid < cnt ? tid : 0)];
+    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
+    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
     // the tile's scales: rows 2 tile (waves 0-3) and 2 tile + 1 (waves 4-7) of the table are contiguous, 2 * K / 128 floats
     if (tid < 4 * n_chunks) scl[tid >= 2 * n_chunks][tid >= 2 * n_chunks ? tid - 2 * n_chunks : tid] = stab[tile * 4 * n_chunks + tid];
     __syncthreads();
@@ -3584,6 +3602,256 @@ int samd_gemm_skinny_f8b(const void *d_A, const void *d_W8p, const float *d_sinv
 #undef ROWS
 #undef GO
     if (e != hipSuccess) { samd_set_error("samd_gemm_skinny_f8b: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================
+// Mixture-of-experts MLP over MANY rows (a prompt in one pass): samd_moe_wide_route / _lists / _gate_up_silu / _down_combine serve 1 ..
+// MOEW_MAX_ROWS rows (padded to 64 inside; rows >= *d_n route nowhere) with the kernels above.  An expert's list may now be longer than a
+// 64-row tile, so the lists are followed by a TILE TABLE -- one record {expert, first entry, entries <= 64} per 64 entries of an expert's
+// list, the tiles of one expert adjacent, experts ascending -- and an expert GEMM workgroup is moe_expert_gemm / moe4_ / moe_i4_ /
+// moe8_expert_gemm<TT, 4, GU, WIDE = true>: the 64-row tile's stream, MFMA sequence, epilogues and roundings, with `expert`, `cnt` and the
+// list taken from its tile record instead of an active slot.  A row's sum does not depend on the tile it sits in (chunk order over k, no
+// split-K), so every row gets the bits the <= 64-row calls give it.
+//   GRID (column tile, tile slot); the slot dimension is the shape's bound min(E, rows * k) + rows * k / 64 >= sum_e ceil(c_e / 64)
+//   (each active expert has at most one partly filled tile); workgroups past ws[0] = the tile count exit at once.  Nothing comes back to
+//   the host.  The row tiles of one expert are adjacent slots, 2 I / 128 or H / 128 workgroups apart in launch order: they run at about the
+//   same time and meet the expert's weights in the L2 / Infinity Cache; nothing in the kernel enforces that (profiles/moe_prefill.md).
+//   ROUTING WORKSPACE (int32 words at the head of d_ws, fixed offsets): [0] tiles; [1] active experts; [MOEW_WS_ACTIVE + a] expert of active
+//   slot a (ascending); [MOEW_WS_COUNT + a] its entries; [MOEW_WS_OFFSET + a] its first entry's place in the entry array;
+//   [MOEW_WS_TILE + 3 t ..] tile t's record; [MOEW_WS_ENTRY + i] the entries p = row * k + slot, expert by expert, ascending within an
+//   expert, rows * k ints at most.  The down products y [rows_pad * k][hidden] follow at the next multiple of 256 bytes.
+//   k_wmoe_lists: one workgroup per expert.  Every workgroup counts the entries of ALL experts (an LDS histogram: integer adds, the same
+//   sums in any order), takes its own place from the counts of the experts below it, and writes its entries in ascending order by ballot
+//   and prefix over 1024 entries at a time -- no atomic decides a position.  The ignore rules are k_moe_lists': rows >= *d_n, indices
+//   outside [0, E), an expert repeated within a row.
+// ================================================================================================
+#define MOEW_LIST_THREADS 1024
+
+__global__ __launch_bounds__(MOEW_LIST_THREADS) void k_wmoe_lists(const int *__restrict__ topk_idx, const int *__restrict__ d_n, int rows, int n_exp, int top_k, int *__restrict__ ws) {
+    __shared__ int hist[MOE_MAX_E];
+    __shared__ int wave_cnt[MOEW_LIST_THREADS / 64];
+    const int tid = threadIdx.x, own = blockIdx.x, total = rows * top_k;
+    int n = d_n[0];
+    n = n < 0 ? 0 : (n > rows ? rows : n);
+    if (tid < MOE_MAX_E) hist[tid] = 0;
+    __syncthreads();
+    auto expert_of = [&](int p) {
+        const int r = p / top_k;
+        int e = r < n ? topk_idx[p] : -1;
+        if (e >= n_exp) e = -1;
+        for (int q = r * top_k; q < p; q++) if (topk_idx[q] == e) e = -1;        // an expert counts once per row: its first slot
+        return e;
+    };
+    for (int p = tid; p < total; p += MOEW_LIST_THREADS) {
+        const int e = expert_of(p);
+        if (e >= 0) atomicAdd(&hist[e], 1);
+    }
+    __syncthreads();
+    int a = 0, off = 0, t0 = 0;                                  // active experts, entries and tiles below this expert
+    for (int e = 0; e < own; e++) { const int c = hist[e]; a += c > 0; off += c; t0 += (c + MOE_MAX_ROWS - 1) / MOE_MAX_ROWS; }
+    const int c = hist[own], nt = (c + MOE_MAX_ROWS - 1) / MOE_MAX_ROWS;
+    if (own == n_exp - 1 && tid < 2) ws[tid] = tid == 0 ? t0 + nt : a + (c > 0);
+    if (c == 0) return;                                          // (uniform)
+    if (tid < 3) ws[(tid == 0 ? MOEW_WS_ACTIVE : tid == 1 ? MOEW_WS_COUNT : MOEW_WS_OFFSET) + a] = tid == 0 ? own : tid == 1 ? c : off;
+    for (int t = tid; t < nt; t += MOEW_LIST_THREADS) {
+        int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * (t0 + t);
+        rec[0] = own; rec[1] = off + MOE_MAX_ROWS * t; rec[2] = c - MOE_MAX_ROWS * t < MOE_MAX_ROWS ? c - MOE_MAX_ROWS * t : MOE_MAX_ROWS;
+    }
+    int base = 0;
+    for (int p0 = 0; p0 < total; p0 += MOEW_LIST_THREADS) {
+        const int p = p0 + tid;
+        const bool mine = p < total && expert_of(p) == own;
+        const unsigned long long m = __ballot(mine);
+        if ((tid & 63) == 0) wave_cnt[tid >> 6] = __popcll(m);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int w = 0; w < MOEW_LIST_THREADS / 64; w++) { const int v = wave_cnt[w]; before += w < (tid >> 6) ? v : 0; all += v; }
+        const int at = base + before + __popcll(m & ((1ull << (tid & 63)) - 1ull));
+        if (mine && at < c) ws[MOEW_WS_ENTRY + off + at] = p;
+        base += all;
+        __syncthreads();
+    }
+}
+
+template <typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe_gu(const typename TT::elem *__restrict__ h, const typename TT::elem *__restrict__ W, const int *__restrict__ ws,
+                                                               typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
+    moe_expert_gemm<TT, 4, true, true>(h, W, ws, act, K, N, n_chunks, top_k);
+}
+template <typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe_dn(const typename TT::elem *__restrict__ act, const typename TT::elem *__restrict__ W, const int *__restrict__ ws,
+                                                               typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
+    moe_expert_gemm<TT, 4, false, true>(act, W, ws, y, K, N, n_chunks, top_k);
+}
+template <typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe4_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
+                                                                typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
+    moe4_expert_gemm<TT, 4, true, true>(h, W4, ws, act, K, N, n_chunks, top_k);
+}
+template <typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe4_dn(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
+                                                                typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
+    moe4_expert_gemm<TT, 4, false, true>(act, W4, ws, y, K, N, n_chunks, top_k);
+}
+template <typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe_i4_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
+                                                                  typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
+    moe_i4_expert_gemm<TT, 4, true, true>(h, W4, ws, act, K, N, n_chunks, top_k);
+}
+template <typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe_i4_dn(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
+                                                                  typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
+    moe_i4_expert_gemm<TT, 4, false, true>(act, W4, ws, y, K, N, n_chunks, top_k);
+}
+template <typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 1) void k_wmoe8_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W8, const float *__restrict__ stab,
+                                                                const int *__restrict__ ws, typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
+    moe8_expert_gemm<TT, 4, true, true>(h, W8, stab, ws, act, K, N, n_chunks, top_k);
+}
+template <typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 1) void k_wmoe8_dn(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W8, const float *__restrict__ stab,
+                                                                const int *__restrict__ ws, typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
+    moe8_expert_gemm<TT, 4, false, true>(act, W8, stab, ws, y, K, N, n_chunks, top_k);
+}
+
+// one wide expert launch: the 64-row tile's dynamic LDS of the format (reserved once per kernel and device), grid (N / 128, tile slots)
+template <auto KERN, typename... A>
+static hipError_t wmoe_launch(int lds, dim3 grid, hipStream_t st, A... args) {
+    static unsigned long long done = 0ull;                       // per-device (samd_common.h)
+    const hipError_t attr = samd_reserve_lds((const void *)KERN, lds, &done);
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(KERN, grid, dim3(64 * GEMM_WAVES), lds, st, args...);
+    return hipSuccess;
+}
+
+template <typename TT, bool GU>
+static hipError_t wmoe_gemm_format(int fmt, dim3 grid, hipStream_t st, const void *A, const void *W, size_t w_rows, const int *ws, void *out, int K, int N, int top_k) {
+    typedef typename TT::elem E;
+    constexpr int tile = 16 * 4 * GEMM_KC * 2;                   // one A buffer of the 64-row tile
+    const unsigned char *wb = (const unsigned char *)W;
+    const int nc = K / GEMM_KC;
+    if (fmt == 0) {
+        if constexpr (GU) return wmoe_launch<k_wmoe_gu<TT>>(3 * tile, grid, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, nc, top_k);
+        else return wmoe_launch<k_wmoe_dn<TT>>(3 * tile, grid, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, nc, top_k);
+    }
+    if (fmt == 1) {
+        constexpr int lds = (Moe4Depth<4>::value + 1) * tile;
+        if constexpr (GU) return wmoe_launch<k_wmoe4_gu<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
+        else return wmoe_launch<k_wmoe4_dn<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
+    }
+    if (fmt == 2) {
+        constexpr int lds = (MoeI4Depth<4>::value + 1) * tile;
+        if constexpr (GU) return wmoe_launch<k_wmoe_i4_gu<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
+        else return wmoe_launch<k_wmoe_i4_dn<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
+    }
+    constexpr int lds = (Moe8Depth<4>::value + 1) * tile;
+    const float *stab = reinterpret_cast<const float *>(reinterpret_cast<const char *>(W) + moe8_scale_offset(w_rows, (size_t)K));
+    if constexpr (GU) return wmoe_launch<k_wmoe8_gu<TT>>(lds, grid, st, (const E *)A, wb, stab, ws, (E *)out, K, N, nc, top_k);
+    else return wmoe_launch<k_wmoe8_dn<TT>>(lds, grid, st, (const E *)A, wb, stab, ws, (E *)out, K, N, nc, top_k);
+}
+
+static inline int moew_rows_pad(int rows) { return (rows + MOE_MAX_ROWS - 1) / MOE_MAX_ROWS * MOE_MAX_ROWS; }
+static inline int64_t moew_y_off(int rows_pad, int top_k) { return (((int64_t)MOEW_WS_ENTRY + (int64_t)rows_pad * top_k) * 4 + 255) / 256 * 256; }
+// the tile slots of a launch: every active expert has at most one partly filled tile
+static inline int moew_tile_bound(int rows_pad, int n_experts, int top_k) {
+    const int total = rows_pad * top_k;
+    return (n_experts < total ? n_experts : total) + total / MOE_MAX_ROWS;
+}
+// the checks shared by the wide calls, in the order the messages promise; sets the error text
+static bool moew_args_ok(const char *fn, bool pointers, int rows, int hidden, int moe_inter, int n_experts, int top_k, int dtype, int fmt) {
+    if (rows < 1 || rows > MOEW_MAX_ROWS) { samd_set_error("%s: rows %d outside 1 .. %d", fn, rows, MOEW_MAX_ROWS); return false; }
+    if (fmt < 0 || fmt > 3) { samd_set_error("%s: unknown expert_format %d (0 model dtype, 1 mxfp4, 2 int4g128, 3 fp8b128)", fn, fmt); return false; }
+    if (!moe_shape_ok(MOE_MAX_ROWS, hidden, moe_inter, n_experts, top_k, dtype) || (fmt == 3 && (hidden > 128 * MOE8_MAX_KB || moe_inter > 128 * MOE8_MAX_KB))) {
+        samd_set_error("%s: unsupported shape (hidden %% 256 == 0, moe_intermediate %% 256 == 0, both <= 16384 for fp8b128, experts <= 256, top-k <= 8, f16/bf16)", fn);
+        return false;
+    }
+    if (!pointers) { samd_set_error("%s: null pointer", fn); return false; }
+    return true;
+}
+
+extern "C" {
+
+int64_t samd_moe_wide_workspace_layout(int32_t field, int32_t rows, int32_t top_k) {
+    const int rp = moew_rows_pad(rows < 1 ? 1 : rows);
+    switch (field) {
+    case 0: return MOEW_WS_ACTIVE;
+    case 1: return MOEW_WS_COUNT;
+    case 2: return MOEW_WS_OFFSET;
+    case 3: return MOEW_WS_TILE;
+    case 4: return MOEW_TILE_INTS;
+    case 5: return MOEW_WS_ENTRY;
+    case 6: return (int64_t)MOEW_WS_ENTRY + (int64_t)rp * top_k;       // int32 words of the routing part
+    case 7: return moew_y_off(rp, top_k);                               // byte offset of the down products
+    case 8: return MOEW_MAX_ROWS;
+    case 9: return MOEW_MAX_TILES;
+    default: return -1;
+    }
+}
+
+int64_t samd_moe_wide_workspace(int32_t rows, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, int32_t dtype) {
+    if (!moew_args_ok("samd_moe_wide_workspace", true, rows, hidden, moe_inter, n_experts, top_k, dtype, 0)) return SAMD_E_INVALID;
+    const int rp = moew_rows_pad(rows);
+    return moew_y_off(rp, top_k) + (int64_t)rp * top_k * hidden * 2;
+}
+
+int samd_moe_wide_route(const void *d_h, const void *d_router, const int32_t *d_n, int32_t rows, int32_t hidden, int32_t n_experts, int32_t top_k, int32_t norm_topk,
+                        int32_t *d_topk_idx, void *d_topk_w, int32_t dtype, void *stream) {
+    if (!moew_args_ok("samd_moe_wide_route", d_h && d_router && d_n && d_topk_idx && d_topk_w, rows, hidden, GEMM_KC, n_experts, top_k, dtype, 0)) return SAMD_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const int rp = moew_rows_pad(rows);
+    if (dtype == SAMD_F16)
+        hipLaunchKernelGGL(k_moe_route<_Float16>, dim3(rp), dim3(64 * MOE_ROUTE_WAVES), 0, st, (const _Float16 *)d_h, (const _Float16 *)d_router, d_n, hidden, n_experts, top_k, norm_topk,
+                           d_topk_idx, (_Float16 *)d_topk_w);
+    else
+        hipLaunchKernelGGL(k_moe_route<__bf16>, dim3(rp), dim3(64 * MOE_ROUTE_WAVES), 0, st, (const __bf16 *)d_h, (const __bf16 *)d_router, d_n, hidden, n_experts, top_k, norm_topk,
+                           d_topk_idx, (__bf16 *)d_topk_w);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_moe_wide_lists(const int32_t *d_topk_idx, const int32_t *d_n, int32_t rows, int32_t n_experts, int32_t top_k, void *d_ws, void *stream) {
+    if (!moew_args_ok("samd_moe_wide_lists", d_topk_idx && d_n && d_ws, rows, GEMM_KC, GEMM_KC, n_experts, top_k, SAMD_F16, 0)) return SAMD_E_INVALID;
+    hipLaunchKernelGGL(k_wmoe_lists, dim3(n_experts), dim3(MOEW_LIST_THREADS), 0, (hipStream_t)stream, d_topk_idx, d_n, moew_rows_pad(rows), n_experts, top_k, (int *)d_ws);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_moe_wide_gate_up_silu(const void *d_h, const void *d_Wgu, const void *d_ws, int32_t rows, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k,
+                               int32_t expert_format, void *d_act, int32_t dtype, void *stream) {
+    if (!moew_args_ok("samd_moe_wide_gate_up_silu", d_h && d_Wgu && d_ws && d_act, rows, hidden, moe_inter, n_experts, top_k, dtype, expert_format)) return SAMD_E_INVALID;
+    const dim3 grid(2 * moe_inter / GEMM_COLS, moew_tile_bound(moew_rows_pad(rows), n_experts, top_k));
+    const size_t w_rows = (size_t)n_experts * 2 * moe_inter;
+    const hipError_t e = dtype == SAMD_F16
+        ? wmoe_gemm_format<GF16, true>(expert_format, grid, (hipStream_t)stream, d_h, d_Wgu, w_rows, (const int *)d_ws, d_act, hidden, 2 * moe_inter, top_k)
+        : wmoe_gemm_format<GBF16, true>(expert_format, grid, (hipStream_t)stream, d_h, d_Wgu, w_rows, (const int *)d_ws, d_act, hidden, 2 * moe_inter, top_k);
+    if (e != hipSuccess) { samd_set_error("samd_moe_wide_gate_up_silu: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_moe_wide_down_combine(const void *d_act, const void *d_Wdown, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws, int32_t rows,
+                               int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, int32_t expert_format, void *d_out, int32_t dtype, void *stream) {
+    if (!moew_args_ok("samd_moe_wide_down_combine", d_act && d_Wdown && d_topk_idx && d_topk_w && d_n && d_ws && d_out, rows, hidden, moe_inter, n_experts, top_k, dtype,
+                      expert_format)) return SAMD_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const int rp = moew_rows_pad(rows);
+    void *y = (char *)d_ws + moew_y_off(rp, top_k);
+    const dim3 grid(hidden / GEMM_COLS, moew_tile_bound(rp, n_experts, top_k));
+    const size_t w_rows = (size_t)n_experts * hidden;
+    const hipError_t e = dtype == SAMD_F16
+        ? wmoe_gemm_format<GF16, false>(expert_format, grid, st, d_act, d_Wdown, w_rows, (const int *)d_ws, y, moe_inter, hidden, top_k)
+        : wmoe_gemm_format<GBF16, false>(expert_format, grid, st, d_act, d_Wdown, w_rows, (const int *)d_ws, y, moe_inter, hidden, top_k);
+    if (e != hipSuccess) { samd_set_error("samd_moe_wide_down_combine: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    const dim3 cgrid((hidden / 8 + 255) / 256, rp);
+    if (dtype == SAMD_F16)
+        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
+    else
+        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
     LAUNCHCHK();
     return SAMD_OK;
 }

@@ -200,6 +200,12 @@ _PROTOS = {
     "samd_moe_down_combine_i4": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "samd_moe_gate_up_silu_f8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "samd_moe_down_combine_f8": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
+    "samd_moe_wide_workspace_layout": (_I64, [_I32, _I32, _I32]),
+    "samd_moe_wide_workspace": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    "samd_moe_wide_route": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
+    "samd_moe_wide_lists": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _VP]),
+    "samd_moe_wide_gate_up_silu": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
+    "samd_moe_wide_down_combine": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "samd_gemm_pack_qkv64": (C.c_int, [_VP, _VP, _I32, _I32, _VP]),
     "samd_gemm_pack_groups": (C.c_int, [_VP, _VP, _I32, _I32, _VP]),
     "samd_gemm_pairs_silu": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _I32, _VP]),

@@ -1192,19 +1192,25 @@ class LlamaRunner:
                 return b
         raise SamdError(f"draft of {n} nodes exceeds {MAX_DRAFT}")
 
-    def forward_rows(self, R, d_tokens, d_relpos, d_mask, d_L, d_n, x_in=None, d_vis=None):
+    def forward_rows(self, R, d_tokens, d_relpos, d_mask, d_L, d_n, x_in=None, d_vis=None, _span=None):
         """one forward over R rows; all of d_* are device pointers (ints / tensors).  Returns the buffers of bucket R
         (logits [R, V], argmax int32[64] with rows < n valid).  x_in [R, hidden]: the rows' input states instead of the
         token embedding (EAGLE draft heads feed fc([embed ; hidden])).  With `self.draft_head` the decoder is an EAGLE head:
-        layer 0 has no input norm and lm_head reads the residual stream itself (b["x"] = the head's output states)."""
+        layer 0 has no input norm and lm_head reads the residual stream itself (b["x"] = the head's output states).
+        _span (the one-pass mixture-of-experts prefill, _prefill_moe): run only a STRETCH of this forward for one 64-row slice -- the
+        launches from layer _span.first on, over _span.b (the bucket's buffers with x / h / cs replaced by the slice's own), with
+        _span.delta folded into the residual by the first norm, up to the first sparse layer's MLP (not run: it is one wide call over all
+        slices) or, past the last layer, the final norm / lm_head / arg-max if _span.head.  Returns (b, layer whose sparse MLP is due, or
+        the number of layers).  The launches of a stretch are this function's own, so a slice's bits are those of the chunked prefill."""
         if self.shape.moe:
             MOE.reject_unsupported(draft_head=getattr(self, "draft_head", False))     # (an attribute set after construction)
         if self._rows_pad(R) > self.native_gemm_max_rows and self.row_major_released:      # (before the bucket's buffers exist)
             raise SamdError(f"a {R}-row forward needs the row-major projection matrices (released: SAMD_RELEASE_ROW_MAJOR / release_row_major()); "
                             f"drafts above {self.native_gemm_max_rows} nodes and the library-GEMM path are unavailable on this runner")
-        L, s, b, dt, st = lib(), self.shape, self._buffers(R), self.dt, current_stream()
+        L, s, b, dt, st = lib(), self.shape, (self._buffers(R) if _span is None else _span.b), self.dt, current_stream()
         RP, part = b["rows_pad"], b["part"]
-        if (self.norm_fold and RP == 16 and x_in is None and d_vis is None and not getattr(self, "draft_head", False)
+        resumed = _span is not None and _span.first > 0           # embedding and the rows' cos | sin were made by the slice's first stretch
+        if (_span is None and self.norm_fold and RP == 16 and x_in is None and d_vis is None and not getattr(self, "draft_head", False)
                 and RP <= self.native_gemm_max_rows):
             return self._forward_rows_fold(R, b, d_tokens, d_relpos, d_mask, d_L, d_n)
 
@@ -1253,7 +1259,9 @@ class LlamaRunner:
                 check(L.samd_gemm_skinny_groups(_ptr(a), _ptr(wg if wg is not None else wp), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
             return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
 
-        if x_in is None:
+        if resumed:
+            pass
+        elif x_in is None:
             check(L.samd_embed_rows(_ptr(d_tokens), _ptr(self.w["embed"]), _ptr(b["x"]), R, s.hidden, s.vocab, dt, st))
         else:
             rows_in = min(R, x_in.shape[0])
@@ -1264,16 +1272,20 @@ class LlamaRunner:
         log_routes = s.moe and self.route_log is not None and not torch.cuda.is_current_stream_capturing()
         block = self.attention == "block"
         vt = self.v_transposed and not block          # the split launches over a transposed V cache (round 6)
-        if self.attention != "split3":
+        if self.attention != "split3" and not resumed:
             # cos / sin of every row's position (visible length + relative position), once per forward: the attention launches of all
             # layers read them without first having to wait for L
             check(L.samd_rope_rows(_ptr(d_relpos), _ptr(d_vis if d_vis is not None else d_L), _ptr(self.cos), _ptr(self.sin), _ptr(b["cs"]), R,
                                    s.head_dim, self.rope_rows, st))
         if d_vis is not None and not block:
             raise SamdError("a visible length different from the write position needs attention mode 'block'")
-        delta, dn, dstride = None, 0, 0
+        delta, dn, dstride = (None if _span is None else _span.delta), 0, 0
         packed = self.wp["layers"] if self.wp else [{}] * len(self.w["layers"])
         for li, w in enumerate(self.w["layers"]):
+            if _span is not None and li < _span.first:
+                continue
+            # (the engine sets layer_hook only while it captures a verify step's graphs and clears it behind the capture; a prefill never
+            # runs inside one, so a stretch of the one-pass prefill meets it as None like every other prefill)
             if self.layer_hook is not None:
                 self.layer_hook(li)
             wp = packed[li]
@@ -1325,6 +1337,8 @@ class LlamaRunner:
                                       None, st))           # (no warm-up hint: gate|up is packed group-major, the hint describes 128-column tiles)
             if "moe_gu" in wp:
                 # sparse layer: route -> gathered expert gate|up + SiLU -> gathered expert down + combine (csrc/gemm_kernels.hip, samd_hip/moe.py)
+                if _span is not None:
+                    return b, li
                 mb = b["moe"]
                 mb.route(b["h"], w["router"], d_n, s.norm_topk)
                 if log_routes:
@@ -1338,13 +1352,15 @@ class LlamaRunner:
                 src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"), f8b=wp.get("wgu_f8b"), f4=wp.get("wgu_f4"), i4=wp.get("wgu_i4"), i8=wp.get("wgu_i8"))     # wgu is only ever packed for the fused form (or FP8)
                 check(L.samd_silu_mul(_ptr(src), _ptr(b["act"]), R, s.inter, dt, n_p, stride, st))
             delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"), f8b=wp.get("wdown_f8b"), f4=wp.get("wdown_f4"), i4=wp.get("wdown_i4"), i8=wp.get("wdown_i8"))
+        if _span is not None and not _span.head:
+            return b, len(self.w["layers"])
         check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(delta), _ptr(self.w["norm"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, dn, dstride,
                                   hint(self.w["lm_head"], self.wp["lm_head"] if self.wp else None, is_head=True), st))
         # (for a draft head the call above only folds the last projection into the residual stream; its norm output is unused)
         gemm(b["x"] if head else b["h"], self.w["lm_head"], self.wp["lm_head"] if self.wp else None, b["logits"])
         if not head:                                              # a draft head's callers rank the logits themselves
             check(L.samd_argmax_rows(_ptr(b["logits"]), dt, R, s.vocab, s.vocab, None, _ptr(b["argmax"]), st))
-        return b
+        return b if _span is None else (b, len(self.w["layers"]))
 
     def _forward_rows_fold(self, R, b, d_tokens, d_relpos, d_mask, d_L, d_n):
         """forward_rows at <= 16 rows in the norm-fold form: the residual stream b["x"] is complete after every projection that adds to it
@@ -1391,13 +1407,16 @@ class LlamaRunner:
         64 rows with a causal chain mask; K/V land at [0, N).  Leaves cache_length = N in the session and the arg-max of
         the last prompt position in session.start_token.  on_chunk(tokens int32[64], logits [64,V], n, hidden [64,H]) is
         called per chunk (Token Recycle learns from the prompt logits, EAGLE-2 from the last hidden states:
-        S/samd_model.py:117-122)."""
+        S/samd_model.py:117-122).  Prompts of 128 tokens or more take a one-pass form unless SAMD_PREFILL=chunked: _prefill_wide on a
+        runner that holds its row-major matrices, _prefill_moe (same bits as the chunks) on a mixture-of-experts runner."""
         ids = input_ids.reshape(-1).to(device=self.device, dtype=torch.int32)
         N = ids.numel()
         if N < 1 or N > self.max_len:
             raise SamdError(f"prompt of {N} tokens does not fit max_cache_len {self.max_len}")
         if N >= 2 * TILE_ROWS and os.environ.get("SAMD_PREFILL", "wide") != "chunked" and not self.row_major_released:
             return self._prefill_wide(session, ids, on_chunk)
+        if N >= self.MOE_PF_MIN_ROWS and os.environ.get("SAMD_PREFILL", "wide") != "chunked" and self.shape.moe:
+            return self._prefill_moe(session, ids, on_chunk)
         v = session.device_views()
         b = None
         for c0 in range(0, N, TILE_ROWS):
@@ -1412,6 +1431,84 @@ class LlamaRunner:
         session.set_cache_length(N)
         session.set_start_token(b["argmax"][(N - 1) % TILE_ROWS:])
         return b["logits"][(N - 1) % TILE_ROWS]
+
+    # ---- mixture-of-experts runners: the prompt in one pass through the sparse layers (profiles/moe_prefill.md) ----
+    MOE_PF_MIN_ROWS = 2 * TILE_ROWS   # the switch-over: shorter prompts keep the chunked loop
+
+    def _moe_prefill_state(self, rows):
+        """staging of _prefill_moe for super-chunks of up to `rows` rows (a multiple of 64): the residual stream and the normed states of
+        all rows, every 64-row slice's cos | sin, tokens, cache length and row count, and the wide expert buffers.  Kept; grows on demand."""
+        st = getattr(self, "_moe_pf", None)
+        if st is not None and st["rows"] >= rows:
+            return st
+        s, dev, n_sl = self.shape, self.device, rows // TILE_ROWS
+        z = lambda *sz: torch.zeros(sz, dtype=self.dtype, device=dev)
+        zi = lambda *sz: torch.zeros(sz, dtype=torch.int32, device=dev)
+        self._moe_pf = st = dict(rows=rows, x=z(rows, s.hidden), h=z(rows, s.hidden), tok=zi(rows), L=zi(n_sl), n=zi(n_sl), n_all=zi(1),
+                                 cs=torch.zeros((n_sl, MAX_DRAFT, s.head_dim), dtype=torch.float32, device=dev),
+                                 first_row=torch.arange(n_sl, dtype=torch.int32, device=dev) * TILE_ROWS,
+                                 moe=MOE.MoeWideBuffers(rows, s.hidden, s.moe_inter, s.n_experts, s.top_k, self.dtype, self.dt, dev))
+        return st
+
+    class _Span:
+        """a stretch of forward_rows for one 64-row slice (see there)"""
+        __slots__ = ("b", "first", "delta", "head")
+
+        def __init__(self, b, first, delta, head):
+            self.b, self.first, self.delta, self.head = b, first, delta, head
+
+    def _prefill_moe(self, session: Session, ids, on_chunk=None):
+        """prefill() of a runner with sparse layers, layer-major: the hidden states of a super-chunk of up to SAMD_MOE_PREFILL_ROWS rows
+        (default 4096) are kept, and a sparse layer's MLP is ONE route, one lists, one gate|up and one down + combine over all of them
+        (samd_moe_wide_*), so the experts are streamed once per super-chunk and layer instead of once per 64 rows.  Everything else --
+        norms, q|k|v, RoPE + K/V write, tree attention with the chain mask against the cache, o, a dense layer's MLP, the final norm,
+        lm_head, arg-max -- runs as the chunked loop runs it, in 64-row launches over row slices (forward_rows' own launches, a stretch
+        of layers at a time; slices in order, so a slice finds the K/V of the slices before it as chunk-major order leaves them).  Bit for
+        bit the chunked prefill: K/V, logits, start token, on_chunk's tensors.  Without on_chunk only the last slice runs the head.
+        route_log gets one entry (layer, rows, topk_idx, topk_w) per sparse layer and super-chunk."""
+        s, N, T = self.shape, ids.numel(), TILE_ROWS
+        cap = MOE.prefill_rows()
+        st = self._moe_prefill_state(min(cap, MOE.wide_rows_pad(N)))
+        mb, base, n_layers = st["moe"], self._buffers(T), len(self.w["layers"])
+        log_routes = self.route_log is not None and not torch.cuda.is_current_stream_capturing()
+        b = j_last = None
+        for s0 in range(0, N, cap):
+            rows = min(cap, N - s0)
+            n_sl = -(-rows // T)
+            st["tok"][:n_sl * T].zero_()
+            st["tok"][:rows] = ids[s0:s0 + rows]
+            st["L"][:n_sl] = st["first_row"][:n_sl] + s0                   # a slice's cache length: the rows before it
+            st["n"][:n_sl] = (rows - st["first_row"][:n_sl]).clamp(max=T)
+            st["n_all"].fill_(rows)
+            slices = [dict(base, x=st["x"][j * T:(j + 1) * T], h=st["h"][j * T:(j + 1) * T], cs=st["cs"][j]) for j in range(n_sl)]
+            first = 0
+            while True:
+                due = n_layers
+                for j in range(n_sl):
+                    head = on_chunk is not None or (s0 + rows == N and j == n_sl - 1)
+                    if first == n_layers and not head:
+                        continue                                            # only the head is left, and nobody reads this slice's
+                    span = self._Span(slices[j], first, None if first == 0 else mb.out[j * T:(j + 1) * T], head)
+                    b, due = self.forward_rows(T, st["tok"][j * T:(j + 1) * T], self.pf_relpos, self.pf_mask, st["L"][j:j + 1], st["n"][j:j + 1], _span=span)
+                    if due == n_layers and head:
+                        j_last = j
+                        if on_chunk is not None:
+                            on_chunk(st["tok"][j * T:(j + 1) * T], b["logits"], min(T, rows - j * T), b["h"])
+                if due == n_layers:
+                    break
+                # the sparse MLP of layer `due` over every row of the super-chunk (csrc/gemm_kernels.hip: samd_moe_wide_*)
+                wp = self.wp["layers"][due]
+                mb.route(st["h"], self.w["layers"][due]["router"], st["n_all"], s.norm_topk, rows=rows)
+                if log_routes:
+                    RP = MOE.wide_rows_pad(rows)
+                    self.route_log.append((due, rows, mb.topk_idx[:RP].clone(), mb.topk_w[:RP].clone()))
+                mb.lists(st["n_all"], rows=rows)
+                mb.experts(st["h"], wp["moe_gu"], wp["moe_down"], st["n_all"], self.expert_format, rows=rows)
+                first = due + 1
+        base["h"].copy_(b["h"])                                             # hidden_rows(64): the last forward's states, as the chunked loop leaves them
+        session.set_cache_length(N)
+        session.set_start_token(base["argmax"][(N - 1) % T:])
+        return base["logits"][(N - 1) % T]
 
     # ---- the wide prefill's library calls, shaped for what the library does well on 256 CUs (profiles/r05_prefill.md) ----
     PF_SPLIT_MIN_ROWS = 1024          # below this no projection of the prompt is worth splitting (and short prompts keep one code path)

@@ -30,7 +30,13 @@ form the official Qwen3-MoE FP8 checkpoints load into; per-expert modules (`mlp.
 on-disk naming) are taken as well.  In a raw weights dict: experts_gu (float8_e4m3fn or its bytes), experts_gu_sinv, experts_down,
 experts_down_sinv -- the _sinv keys are what tells this format from the others.  Packed by pack_experts_fp8 (codes: samd_gemm_pack_f8 over
 E * N rows; then the fp32 scale table [E * N / 64][K / 128]) and streamed by samd_moe_gate_up_silu_f8 / samd_moe_down_combine_f8.  The
-buffer does not depend on the model dtype."""
+buffer does not depend on the model dtype.
+
+MoeBuffers serves one row bucket of at most 64 rows (decode, verify, the chunked prefill).  MoeWideBuffers serves 1 .. 4096 rows in one
+route, one lists, one gate|up and one down + combine (include/samd_hip.h: samd_moe_wide_*): an expert's list may be longer than a 64-row
+tile and is served in several through a tile table, every row with the bits MoeBuffers gives it, over the same packed expert buffers in
+all four formats.  LlamaRunner._prefill_moe runs a prompt of 128 tokens or more through it, SAMD_MOE_PREFILL_ROWS (prefill_rows) rows at a
+time; wide_lists_reference restates the lists and the tile table in plain Python."""
 import os
 
 import torch
@@ -524,3 +530,134 @@ class MoeBuffers:
         n = int(w[0])
         return (n, w[active:active + n].tolist(), w[count:count + n].tolist(),
                 [w[lst + stride * a:lst + stride * a + int(w[count + a])].tolist() for a in range(n)])
+
+
+# ---- the wide form: a sparse layer's MLP over all rows of a prompt (or of a super-chunk of it) in one route, one lists, one gate|up and one
+# down + combine (include/samd_hip.h: samd_moe_wide_*).  Every row gets the bits MoeBuffers gives it.
+WIDE_MAX_ROWS = 4096
+WIDE_TILE = 64
+PREFILL_ROWS_ENV = "SAMD_MOE_PREFILL_ROWS"
+# the C ABI's expert_format codes
+WIDE_FORMAT_CODES = {None: 0, "mxfp4": 1, "int4g128": 2, "fp8b128": 3}
+
+
+def prefill_rows(value=None):
+    """rows of a super-chunk of the one-pass prefill: `value`, else env SAMD_MOE_PREFILL_ROWS, else 4096.  A multiple of 64 in
+    [128, 4096]; anything else raises."""
+    raw = os.environ.get(PREFILL_ROWS_ENV) if value is None else value
+    if raw is None or raw == "":
+        return WIDE_MAX_ROWS
+    try:
+        n = int(raw)
+    except (TypeError, ValueError):
+        raise SamdError(f"{PREFILL_ROWS_ENV}={raw!r}: expected an integer") from None
+    if n % WIDE_TILE != 0 or not 2 * WIDE_TILE <= n <= WIDE_MAX_ROWS:
+        raise SamdError(f"{PREFILL_ROWS_ENV}={n}: expected a multiple of {WIDE_TILE} in [{2 * WIDE_TILE}, {WIDE_MAX_ROWS}]")
+    return n
+
+
+def wide_rows_pad(rows):
+    return (rows + WIDE_TILE - 1) // WIDE_TILE * WIDE_TILE
+
+
+def wide_tile_bound(rows, n_experts, top_k):
+    """tile slots of a wide expert launch: sum_e ceil(c_e / 64) <= active experts + total / 64, every active expert having at most one
+    partly filled tile"""
+    total = wide_rows_pad(rows) * top_k
+    return min(n_experts, total) + total // WIDE_TILE
+
+
+def wide_lists_reference(topk_idx, n, n_experts):
+    """what samd_moe_wide_lists writes, in plain Python from topk_idx (rows x top_k nested lists or a tensor): dict(active, counts, offsets,
+    entries, tiles) -- the active experts ascending, per active expert its entry count and its first entry's place, the entries
+    p = row * top_k + slot expert by expert and ascending within one, the tile records (expert, first entry, entries <= 64).  Ignored:
+    rows >= n, indices outside [0, n_experts), an expert (any value, in fact) that an earlier slot of the row already holds."""
+    rows = topk_idx.tolist() if hasattr(topk_idx, "tolist") else [list(r) for r in topk_idx]
+    per = {}
+    for r, row in enumerate(rows):
+        if r >= n:
+            break
+        for j, e in enumerate(row):
+            if 0 <= e < n_experts and e not in row[:j]:
+                per.setdefault(e, []).append(r * len(row) + j)
+    active = sorted(per)
+    counts = [len(per[e]) for e in active]
+    offsets = [sum(counts[:a]) for a in range(len(active))]
+    entries = [p for e in active for p in per[e]]
+    tiles = [(e, off + t, min(WIDE_TILE, c - t)) for e, c, off in zip(active, counts, offsets) for t in range(0, c, WIDE_TILE)]
+    return dict(active=active, counts=counts, offsets=offsets, entries=entries, tiles=tiles)
+
+
+class MoeWideBuffers:
+    """device buffers of the wide calls for up to `rows` rows (padded to 64): topk_idx / topk_w [RP, k], act [RP * k, I], the workspace
+    (lists + tile table + down products) and out [RP, hidden].  `rows` is fixed; *d_n says how many of them count in a call."""
+
+    def __init__(self, rows, hidden, moe_inter, n_experts, top_k, dtype, dt_code, device):
+        nbytes = lib().samd_moe_wide_workspace(rows, hidden, moe_inter, n_experts, top_k, dt_code)
+        check(0 if nbytes >= 0 else nbytes)
+        self.rows, self.rows_pad = rows, wide_rows_pad(rows)
+        self.hidden, self.moe_inter, self.n_experts, self.top_k, self.dt = hidden, moe_inter, n_experts, top_k, dt_code
+        RP = self.rows_pad
+        self.topk_idx = torch.full((RP, top_k), -1, dtype=torch.int32, device=device)
+        self.topk_w = torch.zeros((RP, top_k), dtype=dtype, device=device)
+        self.act = torch.zeros((RP * top_k, moe_inter), dtype=dtype, device=device)
+        self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        self.out = torch.zeros((RP, hidden), dtype=dtype, device=device)
+
+    def _rows(self, rows):
+        """a call may serve fewer rows than the buffers hold (smaller grids; every offset only shrinks)"""
+        if rows is None:
+            return self.rows
+        if not 1 <= rows <= self.rows:
+            raise SamdError(f"{rows} rows over wide expert buffers of {self.rows}")
+        return rows
+
+    def route(self, h, router, d_n, norm_topk, rows=None):
+        """topk_idx / topk_w of h [RP, hidden]; the lists are a call of their own"""
+        check(lib().samd_moe_wide_route(_ptr(h), _ptr(router), _ptr(d_n), self._rows(rows), self.hidden, self.n_experts, self.top_k, int(bool(norm_topk)),
+                                        _ptr(self.topk_idx), _ptr(self.topk_w), self.dt, current_stream()))
+
+    def lists(self, d_n, rows=None):
+        check(lib().samd_moe_wide_lists(_ptr(self.topk_idx), _ptr(d_n), self._rows(rows), self.n_experts, self.top_k, _ptr(self.ws), current_stream()))
+
+    def experts(self, h, wgu_packed, wdown_packed, d_n, expert_format=None, rows=None):
+        """the two expert launches over the buffers MoeBuffers.experts takes for `expert_format`; returns out [RP, hidden]"""
+        if expert_format not in EXPERT_FORMATS_KNOWN:
+            raise _format_error(expert_format)
+        _check_expert_buffers(self, wgu_packed, wdown_packed, expert_format)
+        L, st, code, rows = lib(), current_stream(), WIDE_FORMAT_CODES[expert_format], self._rows(rows)
+        check(L.samd_moe_wide_gate_up_silu(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), rows, self.hidden, self.moe_inter, self.n_experts, self.top_k,
+                                           code, _ptr(self.act), self.dt, st))
+        check(L.samd_moe_wide_down_combine(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws), rows,
+                                           self.hidden, self.moe_inter, self.n_experts, self.top_k, code, _ptr(self.out), self.dt, st))
+        return self.out
+
+    def routing_state(self):
+        """the workspace's routing part read back in wide_lists_reference's form, plus n_tiles / n_active: for tests and profiling"""
+        lay = [lib().samd_moe_wide_workspace_layout(f, self.rows, self.top_k) for f in range(8)]
+        active, count, offset, tile, tile_ints, entry, words = lay[:7]
+        w = self.ws[:4 * words].view(torch.int32).cpu()
+        n_tiles, n_active = int(w[0]), int(w[1])
+        counts = w[count:count + n_active].tolist()
+        return dict(n_tiles=n_tiles, n_active=n_active, active=w[active:active + n_active].tolist(), counts=counts,
+                    offsets=w[offset:offset + n_active].tolist(), entries=w[entry:entry + sum(counts)].tolist(),
+                    tiles=[tuple(w[tile + tile_ints * t:tile + tile_ints * (t + 1)].tolist()) for t in range(n_tiles)])
+
+    def routing_bytes(self):
+        """the routing part of the workspace as it stands (a copy)"""
+        return self.ws[:4 * lib().samd_moe_wide_workspace_layout(6, self.rows, self.top_k)].clone()
+
+
+def _check_expert_buffers(b, wgu_packed, wdown_packed, expert_format):
+    """the byte counts and marks MoeBuffers.experts asks of packed expert buffers, for the wide calls"""
+    if expert_format is None:
+        if wgu_packed.dtype == torch.uint8 or wdown_packed.dtype == torch.uint8:
+            raise SamdError("uint8 expert buffers are MXFP4 ones: pass expert_format='mxfp4'")
+        return
+    nbytes = {"fp8b128": F8.packed_block_bytes, "int4g128": I4.packed_bytes, "mxfp4": MX.packed_bytes}[expert_format]
+    for what, t, want in (("gate|up", wgu_packed, b.n_experts * nbytes(2 * b.moe_inter, b.hidden)), ("down", wdown_packed, b.n_experts * nbytes(b.hidden, b.moe_inter))):
+        if t.dtype != torch.uint8 or t.numel() != want:
+            raise SamdError(f"{expert_format} {what} expert buffer of {t.numel()} {t.dtype} elements; the packer gives {want} bytes for this shape")
+        if expert_format == "int4g128" and getattr(t, "expert_format", None) != "int4g128":
+            raise SamdError("expert_format 'int4g128' over a buffer that pack_experts_int4 did not return (an MXFP4 buffer of this shape "
+                            "has the same byte count and other contents; a copy or a view of an INT4 buffer loses the packer's mark)")
