@@ -41,7 +41,10 @@ __global__ __launch_bounds__(1024) void k_argmax_rows(const T *__restrict__ logi
         const uint4 raw = reinterpret_cast<const uint4 *>(x)[c];
         const T *e = reinterpret_cast<const T *>(&raw);
 #pragma unroll
-        for (int j = 0; j < VEC; j++) { const float v = to_f32(e[j]); if (v > best) { best = v; bi = c * VEC + j; } }
+        for (int j = 0; j < VEC; j++) {                    // (the index decides equal values here too: a row of -inf must report its FIRST element)
+            const float v = to_f32(e[j]); const long long i = c * VEC + j;
+            if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+        }
     }
     for (long long i = nvec * VEC + threadIdx.x; i < vocab; i += blockDim.x) {
         const float v = to_f32(x[i]);
@@ -912,23 +915,36 @@ struct samd_recycle {
 // list), the 256 x 8 survivors meet in LDS and 8 block arg-max rounds pick the winners.
 __device__ __forceinline__ bool topk_before(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
 
+__device__ __forceinline__ int topk_sortable_bits(int b) { return b ^ ((b >> 31) & 0x7fffffff); }      // its own inverse
+__device__ __forceinline__ int topk_sortable(float v) { return topk_sortable_bits(__float_as_int(v + 0.f)); }   // (+ 0: -0.0 and +0.0 are one value)
+__device__ __forceinline__ bool topk_before_i(int va, int ia, int vb, int ib) { return va > vb || (va == vb && ia < ib); }
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_topk8_rows(const T *__restrict__ logits, int rows, long long vocab, long long stride,
                                                     const int *__restrict__ d_rows, int *__restrict__ out) {
     const int row = blockIdx.x;
     if ((d_rows && row >= d_rows[0]) || row >= rows) return;
     const T *x = logits + (size_t)row * stride;
-    float bv[8]; int bi[8];
+    // The thread's list holds every value as a sortable int (the float's bits made monotonic), so that an empty entry (INT_MIN, 0x7fffffff)
+    // lies strictly below every element, -inf ones included.  With float values and an empty entry of (-inf, 0x7fffffff) a -inf element -- a
+    // masked vocabulary entry -- entered only by the tie clause against an empty entry, and the compiled insertion lost it there: a row with
+    // fewer than 8 finite elements reported index 0 in place of its first -inf ones (tests/test_gpu_select_planted.py, neg_inf_but_one).
+    int bm[8], bi[8];
 #pragma unroll
-    for (int k = 0; k < 8; k++) { bv[k] = -INFINITY; bi[k] = 0x7fffffff; }
+    for (int k = 0; k < 8; k++) { bm[k] = (int)0x80000000; bi[k] = 0x7fffffff; }
     for (long long i = threadIdx.x; i < vocab; i += blockDim.x) {
-        float v = to_f32(x[i]); int id = (int)i;
-        if (!topk_before(v, id, bv[7], bi[7])) continue;
+        const float f = to_f32(x[i]);
+        if (f != f) continue;                              // a NaN never enters the list
+        int v = topk_sortable(f), id = (int)i;
+        if (!topk_before_i(v, id, bm[7], bi[7])) continue;
 #pragma unroll
         for (int k = 0; k < 8; k++) {                      // sorted insertion: swap the carried element down the list
-            if (topk_before(v, id, bv[k], bi[k])) { const float tv = bv[k]; const int ti = bi[k]; bv[k] = v; bi[k] = id; v = tv; id = ti; }
+            if (topk_before_i(v, id, bm[k], bi[k])) { const int tv = bm[k]; const int ti = bi[k]; bm[k] = v; bi[k] = id; v = tv; id = ti; }
         }
     }
+    float bv[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) bv[k] = bi[k] == 0x7fffffff ? -INFINITY : __int_as_float(topk_sortable_bits(bm[k]));
     __shared__ float sv[256 * 8]; __shared__ int si[256 * 8];
     __shared__ float wv[4]; __shared__ int wi[4], wslot[4];
 #pragma unroll

@@ -78,7 +78,9 @@ def _sampled(logits, candidates, config):
             if token == -1 or token in seen:
                 continue
             seen.add(token)
-            if random.random() <= float(residual[token]):
+            # the reference's own expression (utils.py:163-167): the host scalar against a 0-dim tensor of the logits' dtype, which torch
+            # rounds into that dtype before it compares -- a uniform within half an ulp above p accepts, a comparison in double rejects it
+            if bool(random.random() <= residual[token]):
                 prefix = torch.cat((prefix, candidates[row, n_acc][None]))
                 n_acc, best, grown = n_acc + 1, row, True
                 break
