@@ -1216,6 +1216,26 @@ template <> struct F8Widen<GBF16> {
     }
 };
 
+// two A operands (16-byte units at a0, a1 of this lane's row) for each of the RT row tiles: the A-side read of the 8- and 4-bit streaming kernels
+template <int RT>
+__device__ __forceinline__ void gemm_read_a2(u32x4 (&r)[RT][2], uint32_t a0, uint32_t a1) {
+    if constexpr (RT == 1)
+        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r[0][0]), "=&v"(r[0][1]) : "v"(a0), "v"(a1));
+    else if constexpr (RT == 2)
+        asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %4 offset:8192\n\tds_read_b128 %3, %5 offset:8192\n\t"
+                     "s_waitcnt lgkmcnt(0)" : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]) : "v"(a0), "v"(a1));
+    else if constexpr (RT == 3)
+        asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %7\n\tds_read_b128 %2, %6 offset:8192\n\tds_read_b128 %3, %7 offset:8192\n\t"
+                     "ds_read_b128 %4, %6 offset:16384\n\tds_read_b128 %5, %7 offset:16384\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[2][0]), "=&v"(r[2][1]) : "v"(a0), "v"(a1));
+    else
+        asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %8 offset:8192\n\tds_read_b128 %3, %9 offset:8192\n\t"
+                     "ds_read_b128 %4, %8 offset:16384\n\tds_read_b128 %5, %9 offset:16384\n\tds_read_b128 %6, %8 offset:24576\n\t"
+                     "ds_read_b128 %7, %9 offset:24576\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[2][0]), "=&v"(r[2][1]), "=&v"(r[3][0]), "=&v"(r[3][1])
+                     : "v"(a0), "v"(a1));
+}
+
 template <typename TT, int RT, int DEPTH>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_f8(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8,
                                                                      const float *__restrict__ scale, float *__restrict__ partial,
@@ -1273,21 +1293,7 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_f8(const typ
         for (int b = 0; b < 4; b++) {
             const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
             u32x4 r[RT][2];
-            if constexpr (RT == 1)
-                asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r[0][0]), "=&v"(r[0][1]) : "v"(a0), "v"(a1));
-            else if constexpr (RT == 2)
-                asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %4 offset:8192\n\tds_read_b128 %3, %5 offset:8192\n\t"
-                             "s_waitcnt lgkmcnt(0)" : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]) : "v"(a0), "v"(a1));
-            else if constexpr (RT == 3)
-                asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %7\n\tds_read_b128 %2, %6 offset:8192\n\tds_read_b128 %3, %7 offset:8192\n\t"
-                             "ds_read_b128 %4, %6 offset:16384\n\tds_read_b128 %5, %7 offset:16384\n\ts_waitcnt lgkmcnt(0)"
-                             : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[2][0]), "=&v"(r[2][1]) : "v"(a0), "v"(a1));
-            else
-                asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %8 offset:8192\n\tds_read_b128 %3, %9 offset:8192\n\t"
-                             "ds_read_b128 %4, %8 offset:16384\n\tds_read_b128 %5, %9 offset:16384\n\tds_read_b128 %6, %8 offset:24576\n\t"
-                             "ds_read_b128 %7, %9 offset:24576\n\ts_waitcnt lgkmcnt(0)"
-                             : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[2][0]), "=&v"(r[2][1]), "=&v"(r[3][0]), "=&v"(r[3][1])
-                             : "v"(a0), "v"(a1));
+            gemm_read_a2<RT>(r, a0, a1);
             // the conversion is ordinary VALU code on the loaded registers: re-define them here, behind the counted wait (volatile asm keeps its
             // order), so that no conversion can be scheduled above the wait while the load is still in flight
             asm volatile("" : "+v"(cur[b]) : : "memory");
@@ -1422,222 +1428,11 @@ template <> struct F4Widen<GBF16> {
     }
 };
 
-// gemm_wait_younger for pipelines deeper than 4 chunks: wait until at most min(younger, DEPTH - 1) * PC memory operations are outstanding
-template <int DEPTH, int PC>
-__device__ __forceinline__ void gemm_wait_younger_deep(int younger) {
-    static_assert(DEPTH <= 8 && (DEPTH - 1) * PC <= 63, "vmcnt is a 6-bit counter");
-#define SAMD_WAIT_IF(i) if (DEPTH > i && younger >= i) { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(DEPTH > i ? i * PC : 0) : "memory"); return; }
-    SAMD_WAIT_IF(7) SAMD_WAIT_IF(6) SAMD_WAIT_IF(5) SAMD_WAIT_IF(4) SAMD_WAIT_IF(3) SAMD_WAIT_IF(2) SAMD_WAIT_IF(1)
-#undef SAMD_WAIT_IF
-    asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
-}
-
-// two A operands (16-byte units at a0, a1 of this lane's row) for each of the RT row tiles, as k_gemm_skinny_f8 reads them
-template <int RT>
-__device__ __forceinline__ void gemm_f4_read_a(u32x4 (&r)[RT][2], uint32_t a0, uint32_t a1) {
-    if constexpr (RT == 1)
-        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r[0][0]), "=&v"(r[0][1]) : "v"(a0), "v"(a1));
-    else if constexpr (RT == 2)
-        asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %4 offset:8192\n\tds_read_b128 %3, %5 offset:8192\n\t"
-                     "s_waitcnt lgkmcnt(0)" : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]) : "v"(a0), "v"(a1));
-    else if constexpr (RT == 3)
-        asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %7\n\tds_read_b128 %2, %6 offset:8192\n\tds_read_b128 %3, %7 offset:8192\n\t"
-                     "ds_read_b128 %4, %6 offset:16384\n\tds_read_b128 %5, %7 offset:16384\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[2][0]), "=&v"(r[2][1]) : "v"(a0), "v"(a1));
-    else
-        asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %8 offset:8192\n\tds_read_b128 %3, %9 offset:8192\n\t"
-                     "ds_read_b128 %4, %8 offset:16384\n\tds_read_b128 %5, %9 offset:16384\n\tds_read_b128 %6, %8 offset:24576\n\t"
-                     "ds_read_b128 %7, %9 offset:24576\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[2][0]), "=&v"(r[2][1]), "=&v"(r[3][0]), "=&v"(r[3][1])
-                     : "v"(a0), "v"(a1));
-}
-
-template <typename TT, int RT, int DEPTH>
-__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_f4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4,
-                                                                     float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
-                                                                     int n_chunks, int n_splits) {
-    typedef typename TT::elem E;
-    constexpr int R = 16 * RT;
-    constexpr int NT = 64 * GEMM_WAVES;
-    constexpr int XV = (R * 32) / NT;              // 16-byte units per thread to stage one A chunk (as k_gemm_skinny)
-    constexpr int NB = DEPTH + 1;
-    constexpr int PC = 3 + XV;                     // memory operations per thread and chunk: 2 element loads + 1 scale load + the A staging
-    constexpr size_t WCH = 17408, WU = 8192, WS = 16384;   // bytes of one (tile, chunk) block; of one j row inside it; offset of its scales
-    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
-    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
-
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
-    const int split = blockIdx.y;
-    const int c0 = (int)((long long)split * n_chunks / n_splits), c1 = (int)((long long)(split + 1) * n_chunks / n_splits);
-    const char *wtile = reinterpret_cast<const char *>(W4) + (size_t)blockIdx.x * n_chunks * WCH;
-    const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)tid * 2;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
-
-    floatx4 acc[RT];
-#pragma unroll
-    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-
-    // hand-issued nt weight and scale loads, counted waits and bare barriers: see k_gemm_skinny.  The destination registers are defined
-    // once, up front, and every load is an in-out ("+v") of that value: a load that a short split skips then leaves the SAME register
-    // behind, so the compiler has no two values to merge with a copy -- a v_mov of a register whose load is still in flight would move
-    // stale bits and leave the landing load to overwrite whatever lives there by then.
-    u32x4 wr[DEPTH][2];
-    unsigned ws[DEPTH];                            // the chunk's two e8m0 codes of this lane: bits 0-7 unit 0, bits 8-15 unit 1
-#pragma unroll
-    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(ws[d]));
-    auto load_wj = [&](u32x4 (&dst)[2], int c, int j) {
-        const char *p = wtile + (size_t)c * WCH;
-        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[j]) : "v"(wlane), "s"(p + WU * j) : "memory");
-    };
-    auto load_s = [&](unsigned &dst, int c) {
-        const char *p = wtile + (size_t)c * WCH + WS;
-        asm volatile("global_load_ushort %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
-    };
-    auto stage_xi = [&](int c, int buf, int i) {
-        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
-        const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
-        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
-        asm volatile("" ::: "memory");
-    };
-    auto load_w = [&](u32x4 (&dst)[2], unsigned &sdst, int c) {
-        load_wj(dst, c, 0); load_wj(dst, c, 1); load_s(sdst, c);
-    };
-    auto stage_x = [&](int c, int buf) {
-#pragma unroll
-        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
-    };
-    auto phase = [&](u32x4 (&cur)[2], unsigned &cs, int c, int buf) {
-        gemm_wait_younger_deep<DEPTH, PC>(c1 - 1 - c);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
-        // the conversion is ordinary VALU code on the loaded registers: re-define them here, behind the counted wait (volatile asm keeps its
-        // order), so that no conversion can be scheduled above the wait while the load is still in flight
-        asm volatile("" : "+v"(cs) : : "memory");
-        const unsigned e8s = cs;
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            asm volatile("" : "+v"(cur[j]) : : "memory");
-            const float sc = __builtin_bit_cast(float, ((e8s >> (8 * j)) & 0xffu) << 23);       // 2^(e8 - 127)
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int u = 16 * j + 4 * g + 2 * h;
-                const uint32_t a0 = xbase + (uint32_t)(u ^ n) * 16, a1 = xbase + (uint32_t)((u + 1) ^ n) * 16;
-                u32x4 r[RT][2];
-                gemm_f4_read_a<RT>(r, a0, a1);
-                const auto lo = F4Widen<TT>::cvt(cur[j][2 * h], sc), hi = F4Widen<TT>::cvt(cur[j][2 * h + 1], sc);
-#pragma unroll
-                for (int mt = 0; mt < RT; mt++) {
-                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
-                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, acc[mt]);
-                }
-            }
-            if (RT >= 3 && c + DEPTH < c1) {       // 48 / 64 rows: refill per unit (see k_gemm_skinny)
-                load_wj(cur, c + DEPTH, j);
-                if (j == 1) load_s(cs, c + DEPTH);
-#pragma unroll
-                for (int i = 2 * j; i < 2 * j + 2; i++)
-                    if (i < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, i);
-            }
-        }
-        if (RT < 3 && c + DEPTH < c1) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
-    };
-    if (c0 < c1) {
-#pragma unroll
-        for (int d = 0; d < DEPTH; d++)
-            if (c0 + d < c1) { load_w(wr[d], ws[d], c0 + d); stage_x(c0 + d, d); }
-        int buf = 0;
-        for (int c = c0; c < c1; c += DEPTH) {
-#pragma unroll
-            for (int d = 0; d < DEPTH; d++)
-                if (c + d < c1) { phase(wr[d], ws[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
-        }
-    }
-    // C layout of mfma_16x16: lane holds rows 4g + r of column n; the block scales went in with the conversion, so ONE rounding and nothing else
-#pragma unroll
-    for (int mt = 0; mt < RT; mt++) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int m = 16 * mt + 4 * g + r;
-            const float v = acc[mt][r];
-            if (out) out[(size_t)m * N + n0 + n] = (E)v;
-            else __hip_atomic_store(&partial[((size_t)split * R + m) * N + n0 + n], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
-// row-major q [N][K/2] bytes + e8 [N][K/32] codes -> the packed blocks of k_gemm_skinny_f4; one thread moves one 16-byte unit and its scale
-__global__ __launch_bounds__(256) void k_gemm_pack_f4(const uint4 *__restrict__ q, const unsigned char *__restrict__ e8, unsigned char *__restrict__ out,
-                                                      int N, int K) {
-    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;          // element unit = MX block
-    const long long total = (long long)N * K / 32;
-    if (u >= total) return;
-    const int n_chunks = K / GEMM_KC;
-    const long long blk = u >> 10;                                          // 1024 element units per block
-    const int in = (int)(u & 1023), j = in >> 9, tid = in & 511, w = tid >> 6, g = (tid >> 4) & 3, n = tid & 15;
-    const int t = (int)(blk / n_chunks), c = (int)(blk % n_chunks);
-    const long long row = 128LL * t + 16 * w + n, mxb = 8LL * c + 4 * j + g;      // weight row; its MX block along k
-    unsigned char *dst = out + blk * 17408;
-    reinterpret_cast<uint4 *>(dst)[in] = q[row * (K / 32) + mxb];
-    dst[16384 + 2 * tid + j] = e8[row * (K / 32) + mxb];
-}
-
-template <typename TT, int RT, int DEPTH>
-static hipError_t gemm_f4_launch(dim3 grid, hipStream_t st, const void *A, const void *W4, float *partial, void *out, int K, int N, int splits) {
-    constexpr int lds = (DEPTH + 1) * 16 * RT * GEMM_KC * 2;
-    if constexpr (lds > 65536) {
-        static unsigned long long done = 0ull;                     // per-device (samd_common.h)
-        const hipError_t attr = samd_reserve_lds((const void *)k_gemm_skinny_f4<TT, RT, DEPTH>, lds, &done);
-        if (attr != hipSuccess) return attr;
-    }
-    hipLaunchKernelGGL((k_gemm_skinny_f4<TT, RT, DEPTH>), grid, dim3(64 * GEMM_WAVES), lds, st, (const typename TT::elem *)A, (const unsigned char *)W4,
-                       partial, (typename TT::elem *)out, K, N, K / GEMM_KC, splits);
-    return hipSuccess;
-}
-
-extern "C" {
-
-int samd_gemm_pack_f4(const void *d_q, const void *d_e8, void *d_out, int32_t N, int32_t K, void *stream) {
-    if (!d_q || !d_e8 || !d_out || d_q == d_out || d_e8 == d_out || N < GEMM_COLS || N % GEMM_COLS != 0 || K < GEMM_KC || K % GEMM_KC != 0) {
-        samd_set_error("samd_gemm_pack_f4: needs N %% 128 == 0, K %% 256 == 0 and distinct buffers"); return SAMD_E_INVALID;
-    }
-    const long long units = (long long)N * K / 32;
-    hipLaunchKernelGGL(k_gemm_pack_f4, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)d_q,
-                       (const unsigned char *)d_e8, (unsigned char *)d_out, N, K);
-    LAUNCHCHK();
-    return SAMD_OK;
-}
-
-int samd_gemm_skinny_f4(const void *d_A, const void *d_W4p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
-                        int32_t dtype, void *stream) {
-    if (!d_A || !d_W4p || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS || N % GEMM_COLS != 0 ||
-        K < GEMM_KC || K % GEMM_KC != 0 || splits < 1 || splits > K / GEMM_KC || (splits == 1 ? !d_out : !d_partial) || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
-        samd_set_error("samd_gemm_skinny_f4: unsupported shape (rows 16/32/48/64, N %% 128 == 0, K %% 256 == 0) or null pointer"); return SAMD_E_INVALID;
-    }
-    const dim3 grid(N / GEMM_COLS, splits);
-    const hipStream_t st = (hipStream_t)stream;
-    float *part = splits == 1 ? nullptr : d_partial;
-    void *out = splits == 1 ? d_out : nullptr;
-#define GO(TT, RT, D) e = gemm_f4_launch<TT, RT, D>(grid, st, d_A, d_W4p, part, out, K, N, splits)
-#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1, 8); else if (rows_pad == 32) GO(TT, 2, 4); else if (rows_pad == 48) GO(TT, 3, 5); else GO(TT, 4, 3); } while (0)
-    hipError_t e;
-    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
-#undef ROWS
-#undef GO
-    if (e != hipSuccess) { samd_set_error("samd_gemm_skinny_f4: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
-    LAUNCHCHK();
-    return SAMD_OK;
-}
-
-}  // extern "C"
-
 // ================================================================================================
 // INT4 (AWQ / GPTQ: unsigned 4-bit codes, one scale and one 4-bit zero point per 128 elements along k) weight-only projection:
 // out[m][n] = sum_k A[m][k] * W[n][k], W[n][k] = rne_dtype((q[n][k] - z[n][k/128]) * s[n][k/128]), A and s in the model dtype
 // (samd_hip/int4.py has the numeric contract).  Grid, A staging by LDS-DMA, A-side swizzle, counted waits, in-out load destinations and
-// MFMA sequence are k_gemm_skinny_f4's; the weight block and the widening differ: integer arithmetic with a zero point and a scale that
+// MFMA sequence are MXFP4's (one body, gemm_skinny_w4 below); the weight block and the widening differ: integer arithmetic with a zero point and a scale that
 // is no power of two, which v_cvt_scalef32_pk_*_fp4 cannot do.
 //   PACKED LAYOUT (samd_gemm_pack_i4): block (tile t = 128 columns, chunk c = 256 k) is 17 KiB contiguous at (t * K/256 + c) * 17408 bytes:
 //   16 KiB of elements, then 1 KiB of group data.  Element unit j * 512 + tid (16 bytes, j = 0, 1) holds the 32 codes
@@ -1652,7 +1447,7 @@ int samd_gemm_skinny_f4(const void *d_A, const void *d_W4p, int32_t rows_pad, in
 // once (fp16 denormals on).  bf16: (q << 16) | 0x43000000 is the fp32 128 + q; subtract the fp32 128 + z (exact), multiply by float(s)
 // (exact in fp32: 5 x 8 significant bits), v_cvt_pk_bf16_f32 rounds once -- gfx950 has no packed bf16 arithmetic; this is the only new
 // inline assembly besides the 8-byte sibling of the nt loads.  The conversion sits behind the counted wait, as f4's.
-// DEPTH: k_gemm_skinny_f4's table (16 rows 8, 32 rows 4, 48 rows 5, 64 rows 3): the group data costs one more VGPR per chunk in flight than
+// DEPTH: MXFP4's table (16 rows 8, 32 rows 4, 48 rows 5, 64 rows 3): the group data costs one more VGPR per chunk in flight than
 // f4's scales, and no instantiation spills (tests/test_int4_codeobject_cpu.py reads it from the code object's metadata).
 // ================================================================================================
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -1696,17 +1491,65 @@ template <> struct I4Widen<GBF16> {
     }
 };
 
-template <typename TT, int RT, int DEPTH>
-__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4,
-                                                                     float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
-                                                                     int n_chunks, int n_splits) {
+// ================================================================================================
+// The 4-bit streaming body shared by MXFP4 and INT4.  Both formats stream 17 KiB (tile, chunk) blocks -- 16 KiB of elements, then 1 KiB of
+// per-chunk side data -- over the grid, the LDS-DMA A staging, the A-side swizzle and the MFMA order of k_gemm_skinny_f8.  A format is a
+// small policy: the type of a lane's side data (side_t), its byte offset behind the elements (slane), the ONE nt load that fetches it
+// (load_side), and the widening (group: the side data of unit j; cvt: one dword of 8 codes -> one MFMA operand).
+// ================================================================================================
+struct W4Mx {                                      // side data: the chunk's two e8m0 codes of this lane, bits 0-7 unit 0, bits 8-15 unit 1
+    typedef unsigned side_t;
+    static constexpr bool mx = true;
+    static __device__ __forceinline__ uint32_t slane(int tid, int, int) { return (uint32_t)tid * 2; }
+    static __device__ __forceinline__ void load_side(side_t &dst, uint32_t slane, const char *p) {
+        asm volatile("global_load_ushort %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
+    }
+    template <typename TT> static __device__ __forceinline__ float group(side_t e8s, int j) {
+        return __builtin_bit_cast(float, ((e8s >> (8 * j)) & 0xffu) << 23);                     // 2^(e8 - 127)
+    }
+    template <typename TT> static __device__ __forceinline__ auto cvt(unsigned x, float sc) { return F4Widen<TT>::cvt(x, sc); }
+};
+struct W4Int {                                     // side data: the group data of this lane's row, {s0 | s1 << 16, zb0 | zb1 << 16}
+    typedef u32x2 side_t;
+    static constexpr bool mx = false;
+    static __device__ __forceinline__ uint32_t slane(int, int w, int n) { return (uint32_t)(16 * w + n) * 8; }
+    static __device__ __forceinline__ void load_side(side_t &dst, uint32_t slane, const char *p) {
+        asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
+    }
+    template <typename TT> static __device__ __forceinline__ auto group(side_t gd, int j) { return I4Widen<TT>::group(gd, j); }
+    template <typename TT> static __device__ __forceinline__ auto cvt(unsigned x, typename I4Widen<TT>::G g) { return I4Widen<TT>::cvt(x, g); }
+};
+
+// gemm_wait_younger for pipelines deeper than 4 chunks: wait until at most min(younger, DEPTH - 1) * PC memory operations are outstanding
+template <int DEPTH, int PC>
+__device__ __forceinline__ void gemm_wait_younger_deep(int younger) {
+    static_assert(DEPTH <= 8 && (DEPTH - 1) * PC <= 63, "vmcnt is a 6-bit counter");
+#define SAMD_WAIT_IF(i) if (DEPTH > i && younger >= i) { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(DEPTH > i ? i * PC : 0) : "memory"); return; }
+    SAMD_WAIT_IF(7) SAMD_WAIT_IF(6) SAMD_WAIT_IF(5) SAMD_WAIT_IF(4) SAMD_WAIT_IF(3) SAMD_WAIT_IF(2) SAMD_WAIT_IF(1)
+#undef SAMD_WAIT_IF
+    asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+}
+
+// THE PIPELINE (this block speaks for moe_w4_expert_gemm too, which differs only in where A rows and the weight tile come from).
+//   Hand-issued nt element and side-data loads, counted waits and bare barriers: see k_gemm_skinny.  3 + XV memory operations per lane and
+//   chunk: 2 element loads, 1 side-data load, the A staging.
+//   In-out destinations: the destination registers are defined once, up front, and every load is an in-out ("+v") of that value.  A load
+//   that a short split (or a short expert stream) skips then leaves the SAME register behind, so the compiler has no two values to merge
+//   with a copy -- a v_mov of a register whose load is still in flight would move stale bits and leave the landing load to overwrite
+//   whatever lives there by then.  This fault was met once, with a split whose prologue skipped a load.
+//   Re-definition behind the wait: the widening is ordinary VALU code on the loaded registers, so they are re-defined behind the counted
+//   wait (volatile asm keeps its order) and no conversion can be scheduled above the wait while the load is still in flight.
+template <typename F, typename TT, int RT, int DEPTH>
+__device__ __forceinline__ void gemm_skinny_w4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4, float *__restrict__ partial,
+                                               typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int n_splits) {
     typedef typename TT::elem E;
+    typedef typename F::side_t side_t;
     constexpr int R = 16 * RT;
     constexpr int NT = 64 * GEMM_WAVES;
     constexpr int XV = (R * 32) / NT;              // 16-byte units per thread to stage one A chunk (as k_gemm_skinny)
     constexpr int NB = DEPTH + 1;
-    constexpr int PC = 3 + XV;                     // memory operations per thread and chunk: 2 element loads + 1 group-data load + the A staging
-    constexpr size_t WCH = 17408, WU = 8192, WS = 16384;   // bytes of one (tile, chunk) block; of one j row inside it; offset of its group data
+    constexpr int PC = 3 + XV;                     // memory operations per thread and chunk: 2 element loads + 1 side-data load + the A staging
+    constexpr size_t WCH = 17408, WU = 8192, WS = 16384;   // bytes of one (tile, chunk) block; of one j row inside it; offset of its side data
     extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
     E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
 
@@ -1715,26 +1558,22 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i4(const typ
     const int split = blockIdx.y;
     const int c0 = (int)((long long)split * n_chunks / n_splits), c1 = (int)((long long)(split + 1) * n_chunks / n_splits);
     const char *wtile = reinterpret_cast<const char *>(W4) + (size_t)blockIdx.x * n_chunks * WCH;
-    const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)(16 * w + n) * 8;
+    const uint32_t wlane = (uint32_t)tid * 16, slane = F::slane(tid, w, n);
     const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
 
     floatx4 acc[RT];
 #pragma unroll
     for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
 
-    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
     u32x4 wr[DEPTH][2];
-    u32x2 ws[DEPTH];                               // the chunk's group data of this lane's row: {s0 | s1 << 16, zb0 | zb1 << 16}
+    side_t ws[DEPTH];
 #pragma unroll
     for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(ws[d]));
     auto load_wj = [&](u32x4 (&dst)[2], int c, int j) {
         const char *p = wtile + (size_t)c * WCH;
         asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[j]) : "v"(wlane), "s"(p + WU * j) : "memory");
     };
-    auto load_s = [&](u32x2 &dst, int c) {
-        const char *p = wtile + (size_t)c * WCH + WS;
-        asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
-    };
+    auto load_s = [&](side_t &dst, int c) { F::load_side(dst, slane, wtile + (size_t)c * WCH + WS); };
     auto stage_xi = [&](int c, int buf, int i) {
         const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
         const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
@@ -1742,33 +1581,31 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i4(const typ
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
         asm volatile("" ::: "memory");
     };
-    auto load_w = [&](u32x4 (&dst)[2], u32x2 &sdst, int c) {
+    auto load_w = [&](u32x4 (&dst)[2], side_t &sdst, int c) {
         load_wj(dst, c, 0); load_wj(dst, c, 1); load_s(sdst, c);
     };
     auto stage_x = [&](int c, int buf) {
 #pragma unroll
         for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
     };
-    auto phase = [&](u32x4 (&cur)[2], u32x2 &cs, int c, int buf) {
+    auto phase = [&](u32x4 (&cur)[2], side_t &cs, int c, int buf) {
         gemm_wait_younger_deep<DEPTH, PC>(c1 - 1 - c);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
-        // the widening is ordinary VALU code on the loaded registers: re-define them here, behind the counted wait (volatile asm keeps its
-        // order), so that no conversion can be scheduled above the wait while the load is still in flight
         asm volatile("" : "+v"(cs) : : "memory");
-        const u32x2 gd = cs;
+        const side_t side = cs;
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             asm volatile("" : "+v"(cur[j]) : : "memory");
-            const auto grp = I4Widen<TT>::group(gd, j);
+            const auto grp = F::template group<TT>(side, j);
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const int u = 16 * j + 4 * g + 2 * h;
                 const uint32_t a0 = xbase + (uint32_t)(u ^ n) * 16, a1 = xbase + (uint32_t)((u + 1) ^ n) * 16;
                 u32x4 r[RT][2];
-                gemm_f4_read_a<RT>(r, a0, a1);
-                const auto lo = I4Widen<TT>::cvt(cur[j][2 * h], grp), hi = I4Widen<TT>::cvt(cur[j][2 * h + 1], grp);
+                gemm_read_a2<RT>(r, a0, a1);
+                const auto lo = F::template cvt<TT>(cur[j][2 * h], grp), hi = F::template cvt<TT>(cur[j][2 * h + 1], grp);
 #pragma unroll
                 for (int mt = 0; mt < RT; mt++) {
                     acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
@@ -1796,7 +1633,8 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i4(const typ
                 if (c + d < c1) { phase(wr[d], ws[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
         }
     }
-    // C layout of mfma_16x16: lane holds rows 4g + r of column n; scale and zero point went in with the widening, so ONE rounding and nothing else
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n; block scales / scale and zero point went in with the widening, so ONE
+    // rounding and nothing else
 #pragma unroll
     for (int mt = 0; mt < RT; mt++) {
 #pragma unroll
@@ -1807,6 +1645,36 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i4(const typ
             else __hip_atomic_store(&partial[((size_t)split * R + m) * N + n0 + n], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+
+template <typename TT, int RT, int DEPTH>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_f4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4,
+                                                                     float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
+                                                                     int n_chunks, int n_splits) {
+    gemm_skinny_w4<W4Mx, TT, RT, DEPTH>(A, W4, partial, out, K, N, n_chunks, n_splits);
+}
+
+template <typename TT, int RT, int DEPTH>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4,
+                                                                     float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
+                                                                     int n_chunks, int n_splits) {
+    gemm_skinny_w4<W4Int, TT, RT, DEPTH>(A, W4, partial, out, K, N, n_chunks, n_splits);
+}
+
+// row-major q [N][K/2] bytes + e8 [N][K/32] codes -> the packed blocks of k_gemm_skinny_f4; one thread moves one 16-byte unit and its scale
+__global__ __launch_bounds__(256) void k_gemm_pack_f4(const uint4 *__restrict__ q, const unsigned char *__restrict__ e8, unsigned char *__restrict__ out,
+                                                      int N, int K) {
+    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;          // element unit = MX block
+    const long long total = (long long)N * K / 32;
+    if (u >= total) return;
+    const int n_chunks = K / GEMM_KC;
+    const long long blk = u >> 10;                                          // 1024 element units per block
+    const int in = (int)(u & 1023), j = in >> 9, tid = in & 511, w = tid >> 6, g = (tid >> 4) & 3, n = tid & 15;
+    const int t = (int)(blk / n_chunks), c = (int)(blk % n_chunks);
+    const long long row = 128LL * t + 16 * w + n, mxb = 8LL * c + 4 * j + g;      // weight row; its MX block along k
+    unsigned char *dst = out + blk * 17408;
+    reinterpret_cast<uint4 *>(dst)[in] = q[row * (K / 32) + mxb];
+    dst[16384 + 2 * tid + j] = e8[row * (K / 32) + mxb];
 }
 
 // row-major q [N][K/2] bytes, z [N][K/128] bytes, s [N][K/128] 16-bit words -> the packed blocks of k_gemm_skinny_i4; one thread moves one
@@ -1841,20 +1709,54 @@ __global__ __launch_bounds__(256) void k_gemm_pack_i4(const uint4 *__restrict__ 
     }
 }
 
-template <typename TT, int RT, int DEPTH>
-static hipError_t gemm_i4_launch(dim3 grid, hipStream_t st, const void *A, const void *W4, float *partial, void *out, int K, int N, int splits) {
-    constexpr int lds = (DEPTH + 1) * 16 * RT * GEMM_KC * 2;
-    if constexpr (lds > 65536) {
+// one launch of a 4-bit streaming kernel: dynamic LDS above 64 KiB is reserved once per kernel instantiation and device
+template <auto KERN, int LDS, typename... A>
+static hipError_t w4_launch(dim3 grid, hipStream_t st, A... args) {
+    if constexpr (LDS > 65536) {
         static unsigned long long done = 0ull;                     // per-device (samd_common.h)
-        const hipError_t attr = samd_reserve_lds((const void *)k_gemm_skinny_i4<TT, RT, DEPTH>, lds, &done);
+        const hipError_t attr = samd_reserve_lds((const void *)KERN, LDS, &done);
         if (attr != hipSuccess) return attr;
     }
-    hipLaunchKernelGGL((k_gemm_skinny_i4<TT, RT, DEPTH>), grid, dim3(64 * GEMM_WAVES), lds, st, (const typename TT::elem *)A, (const unsigned char *)W4,
-                       partial, (typename TT::elem *)out, K, N, K / GEMM_KC, splits);
+    hipLaunchKernelGGL(KERN, grid, dim3(64 * GEMM_WAVES), LDS, st, args...);
     return hipSuccess;
 }
 
+// samd_gemm_skinny_f4 / _i4: the checks, the grid and the row-tile / dtype dispatch with the DEPTH table of both formats
+template <typename F>
+static int gemm_skinny_w4_call(const char *fn, const void *d_A, const void *d_W4p, int rows_pad, int N, int K, int splits, float *d_partial, void *d_out, int dtype,
+                               void *stream) {
+    if (!d_A || !d_W4p || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS || N % GEMM_COLS != 0 ||
+        K < GEMM_KC || K % GEMM_KC != 0 || splits < 1 || splits > K / GEMM_KC || (splits == 1 ? !d_out : !d_partial) || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("%s: unsupported shape (rows 16/32/48/64, N %% 128 == 0, K %% 256 == 0) or null pointer", fn); return SAMD_E_INVALID;
+    }
+    const dim3 grid(N / GEMM_COLS, splits);
+    const hipStream_t st = (hipStream_t)stream;
+    float *part = splits == 1 ? nullptr : d_partial;
+    void *out = splits == 1 ? d_out : nullptr;
+#define GO(TT, RT, D) e = w4_launch<(F::mx ? k_gemm_skinny_f4<TT, RT, D> : k_gemm_skinny_i4<TT, RT, D>), (D + 1) * 16 * RT * GEMM_KC * 2>( \
+        grid, st, (const typename TT::elem *)d_A, (const unsigned char *)d_W4p, part, (typename TT::elem *)out, K, N, K / GEMM_KC, splits)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1, 8); else if (rows_pad == 32) GO(TT, 2, 4); else if (rows_pad == 48) GO(TT, 3, 5); else GO(TT, 4, 3); } while (0)
+    hipError_t e;
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
+    if (e != hipSuccess) { samd_set_error("%s: %s", fn, hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
 extern "C" {
+
+int samd_gemm_pack_f4(const void *d_q, const void *d_e8, void *d_out, int32_t N, int32_t K, void *stream) {
+    if (!d_q || !d_e8 || !d_out || d_q == d_out || d_e8 == d_out || N < GEMM_COLS || N % GEMM_COLS != 0 || K < GEMM_KC || K % GEMM_KC != 0) {
+        samd_set_error("samd_gemm_pack_f4: needs N %% 128 == 0, K %% 256 == 0 and distinct buffers"); return SAMD_E_INVALID;
+    }
+    const long long units = (long long)N * K / 32;
+    hipLaunchKernelGGL(k_gemm_pack_f4, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)d_q,
+                       (const unsigned char *)d_e8, (unsigned char *)d_out, N, K);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
 
 int samd_gemm_pack_i4(const void *d_q, const void *d_z, const void *d_s, void *d_out, int32_t N, int32_t K, int32_t dtype, void *stream) {
     if (!d_q || !d_z || !d_s || !d_out || d_q == d_out || d_z == d_out || d_s == d_out || N < GEMM_COLS || N % GEMM_COLS != 0 || K < GEMM_KC ||
@@ -1868,25 +1770,14 @@ int samd_gemm_pack_i4(const void *d_q, const void *d_z, const void *d_s, void *d
     return SAMD_OK;
 }
 
+int samd_gemm_skinny_f4(const void *d_A, const void *d_W4p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
+                        int32_t dtype, void *stream) {
+    return gemm_skinny_w4_call<W4Mx>("samd_gemm_skinny_f4", d_A, d_W4p, rows_pad, N, K, splits, d_partial, d_out, dtype, stream);
+}
+
 int samd_gemm_skinny_i4(const void *d_A, const void *d_W4p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
                         int32_t dtype, void *stream) {
-    if (!d_A || !d_W4p || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS || N % GEMM_COLS != 0 ||
-        K < GEMM_KC || K % GEMM_KC != 0 || splits < 1 || splits > K / GEMM_KC || (splits == 1 ? !d_out : !d_partial) || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
-        samd_set_error("samd_gemm_skinny_i4: unsupported shape (rows 16/32/48/64, N %% 128 == 0, K %% 256 == 0) or null pointer"); return SAMD_E_INVALID;
-    }
-    const dim3 grid(N / GEMM_COLS, splits);
-    const hipStream_t st = (hipStream_t)stream;
-    float *part = splits == 1 ? nullptr : d_partial;
-    void *out = splits == 1 ? d_out : nullptr;
-#define GO(TT, RT, D) e = gemm_i4_launch<TT, RT, D>(grid, st, d_A, d_W4p, part, out, K, N, splits)
-#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1, 8); else if (rows_pad == 32) GO(TT, 2, 4); else if (rows_pad == 48) GO(TT, 3, 5); else GO(TT, 4, 3); } while (0)
-    hipError_t e;
-    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
-#undef ROWS
-#undef GO
-    if (e != hipSuccess) { samd_set_error("samd_gemm_skinny_i4: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
-    LAUNCHCHK();
-    return SAMD_OK;
+    return gemm_skinny_w4_call<W4Int>("samd_gemm_skinny_i4", d_A, d_W4p, rows_pad, N, K, splits, d_partial, d_out, dtype, stream);
 }
 
 }  // extern "C"
@@ -1980,7 +1871,7 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i8(const typ
 #pragma unroll
     for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
 
-    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
+    // the load destinations: one value each, defined once; every load is an in-out operand of it (see gemm_skinny_w4)
     u32x4 wr[DEPTH][4];
     u32x2 ws[DEPTH];                               // the chunk's group data of this lane's row: {s0 | s1 << 16, zb0 | zb1 << 16}
 #pragma unroll
@@ -2022,7 +1913,7 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i8(const typ
         for (int b = 0; b < 4; b++) {
             const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
             u32x4 r[RT][2];
-            gemm_f4_read_a<RT>(r, a0, a1);
+            gemm_read_a2<RT>(r, a0, a1);
             asm volatile("" : "+v"(cur[b]) : : "memory");
             const auto grp = I8Widen<TT>::group(gd, b >> 1);
             const auto lo = I8Widen<TT>::cvt(cur[b][0], cur[b][1], grp), hi = I8Widen<TT>::cvt(cur[b][2], cur[b][3], grp);
@@ -2386,7 +2277,7 @@ __device__ __forceinline__ void moe_expert_gemm(const typename TT::elem *__restr
         for (int b = 0; b < 4; b++) {
             const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
             u32x4 r[RT][2];
-            gemm_f4_read_a<RT>(r, a0, a1);
+            gemm_read_a2<RT>(r, a0, a1);
             // re-defined behind the counted wait (volatile asm keeps its order): no use can be scheduled above it
             asm volatile("" : "+v"(cur[b][0]), "+v"(cur[b][1]) : : "memory");
 #pragma unroll
@@ -2632,38 +2523,48 @@ int samd_moe_down_combine(const void *d_act, const void *d_Wdown, const int32_t 
 }  // extern "C"
 
 // ================================================================================================
-// Mixture-of-experts MLP with MXFP4 experts: the gathered expert GEMMs of moe_expert_gemm over k_gemm_skinny_f4's 4.25-bit weight stream.
-//   samd_moe_gate_up_silu_f4 / samd_moe_down_combine_f4: the grids, the routing workspace, the early exit of inactive slots, the gathered
-//   LDS-DMA A tile, both epilogues (HF's roundings) and k_moe_combine are those of the model-dtype calls; the weight side is
-//   k_gemm_skinny_f4's: 17 KiB (tile, chunk) blocks, two 16-byte nt element loads and one 2-byte nt scale load per lane and chunk, the
-//   conversion with the block scale, the A-side unit order (16 j + 4 g + i) ^ n.  No split-K, no atomics: a row's output has the same bits
-//   whatever shares the launch.
-//   PACKED LAYOUT: the experts laid end to end are ONE matrix of E * N rows in samd_gemm_pack_f4's layout; expert e's tile t is global tile
-//   e * N / 128 + t, at ((e * N / 128 + t) * K / 256 + c) * 17408 bytes for chunk c.  gate|up: packed row 128 t + r of an expert is its gate
-//   row 64 t + r for r < 64 and its up row I + 64 t + r - 64 otherwise (samd_hip/moe.py permutes q and e8 before packing; MX blocks run
+// Mixture-of-experts MLP with 4-bit experts: the gathered expert GEMMs of moe_expert_gemm over gemm_skinny_w4's 4.25-bit weight stream,
+// ONE body (moe_w4_expert_gemm) for both formats with the weight-side policies W4Mx / W4Int.
+//   samd_moe_gate_up_silu_f4 / _i4, samd_moe_down_combine_f4 / _i4: the fixed grid (N / 128, min(E, rows_pad * top_k)), the routing
+//   workspace, the early exit of slots >= ws[0], the list in static LDS, the gathered LDS-DMA A tile (srow), both epilogues (HF's roundings;
+//   rows >= cnt not stored) and k_moe_combine are those of the model-dtype calls; the weight side is gemm_skinny_w4's: 17 KiB (tile, chunk)
+//   blocks, two 16-byte nt element loads and one nt side-data load per lane and chunk, the widening behind the counted wait, the A-side unit
+//   order (16 j + 4 g + i) ^ n, fp32 accumulation in chunk order.  No split-K, no atomics: a row's output has the same bits whatever shares
+//   the launch.
+//   PACKED LAYOUT, MXFP4: the experts laid end to end are ONE matrix of E * N rows in samd_gemm_pack_f4's layout; expert e's tile t is global
+//   tile e * N / 128 + t, at ((e * N / 128 + t) * K / 256 + c) * 17408 bytes for chunk c.  gate|up: packed row 128 t + r of an expert is its
+//   gate row 64 t + r for r < 64 and its up row I + 64 t + r - 64 otherwise (samd_hip/moe.py permutes q and e8 before packing; MX blocks run
 //   along k, so whole blocks move), which is the interleave of k_moe_pack: waves 0-3 hold gate columns, waves 4-7 the up columns they meet.
-//   DEPTH (chunks of 16 KiB + 1 KiB in flight per workgroup), chosen per row tile under (DEPTH - 1) * PC <= 63 (vmcnt), (DEPTH + 1) A
-//   buffers of R * 512 bytes + the list (256 bytes, 1 KiB of static LDS after alignment) inside 160 KiB of LDS for the intended workgroups
-//   per CU: 16 rows 8 (9 x 8 KiB = 72 KiB, two workgroups per CU; an expert's whole gate|up stream of hidden 2048 is in flight from the
-//   prologue), 32 rows 3 (4 x 16 = 64 KiB, two per CU -- k_gemm_skinny_f4's 4 would need 2 x (80 + 1) KiB > 160 KiB with the list), 48 rows
-//   2 (3 x 24 = 72 KiB, two per CU: expert streams are 1-8 chunks long, so a second workgroup that covers the first one's prologue and
-//   epilogue is worth more than depth; one per CU would allow 5), 64 rows 3 (4 x 32 = 128 KiB, one per CU: two never fit).  An expert's
-//   stream is often SHORTER than the depth (3 chunks for down at moe_inter 768, 1 at 256): the skipped prologue loads leave their in-out
-//   destination registers as they are (see k_gemm_skinny_f4).  Not swept on a GPU; profiles/moe_experts_mxfp4.md has the timings.
+//   PACKED LAYOUT, INT4 (AWQ / GPTQ; W = rne_dtype((q - z) * s), one rounding): the same in samd_gemm_pack_i4's layout (the pack call with
+//   N := E * N), the same tile addresses.  gate|up: the rows are permuted before packing as for MXFP4 (samd_hip/moe.py: gate_up_tile_order;
+//   groups run along k, so whole rows move with their zero points and scales).  The buffer is dtype-specific (the scales and the pre-biased
+//   zero points are in the model dtype).
+//   DEPTH (chunks of 16 KiB + 1 KiB in flight per workgroup), one table for both formats, chosen per row tile under (DEPTH - 1) * PC <= 63
+//   (vmcnt: 28, 10, 6, 14), (DEPTH + 1) A buffers of R * 512 bytes + the list (256 bytes, 1 KiB of static LDS after alignment) inside 160 KiB
+//   of LDS for the intended workgroups per CU, and no spills: 16 rows 8 (9 x 8 KiB = 72 KiB, two workgroups per CU; an expert's whole gate|up
+//   stream of hidden 2048 is in flight from the prologue), 32 rows 3 (4 x 16 = 64 KiB, two per CU -- the dense 4 would need 2 x (80 + 1) KiB
+//   > 160 KiB with the list), 48 rows 2 (3 x 24 = 72 KiB, two per CU: expert streams are 1-8 chunks long, so a second workgroup that covers
+//   the first one's prologue and epilogue is worth more than depth; one per CU would allow 5), 64 rows 3 (4 x 32 = 128 KiB, one per CU: two
+//   never fit).  INT4's group data costs one VGPR per chunk in flight more than MXFP4's scales (8 more at 16 rows) and every instantiation
+//   still compiles without scratch (tests/test_moe_int4_cpu.py reads it from the code object's metadata).  An expert's stream is often
+//   SHORTER than the depth (3 chunks for down at moe_inter 768, 1 at 256): the skipped prologue loads leave their in-out destination
+//   registers as they are (see gemm_skinny_w4).  Not swept on a GPU; profiles/moe_experts_mxfp4.md and profiles/moe_experts_int4.md have
+//   the timings.
 // ================================================================================================
-template <int RT> struct Moe4Depth { static constexpr int value = RT == 1 ? 8 : RT == 3 ? 2 : 3; };
+template <int RT> struct MoeW4Depth { static constexpr int value = RT == 1 ? 8 : RT == 3 ? 2 : 3; };
 
-template <typename TT, int RT, bool GU, bool WIDE = false>          // WIDE: a tile record of the wide workspace names the expert and its list
-__device__ __forceinline__ void moe4_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
-                                                 typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
+template <typename F, typename TT, int RT, bool GU, bool WIDE>      // WIDE: a tile record of the wide workspace names the expert and its list
+__device__ __forceinline__ void moe_w4_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
+                                                   typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
     typedef typename TT::elem E;
-    constexpr int DEPTH = Moe4Depth<RT>::value;
+    typedef typename F::side_t side_t;
+    constexpr int DEPTH = MoeW4Depth<RT>::value;
     constexpr int R = 16 * RT;
     constexpr int NT = 64 * GEMM_WAVES;
     constexpr int XV = (R * 32) / NT;
     constexpr int NB = DEPTH + 1;
-    constexpr int PC = 3 + XV;                     // memory operations per thread and chunk: 2 element loads + 1 scale load + the A staging
-    constexpr size_t WCH = 17408, WU = 8192, WS = 16384;   // bytes of one (tile, chunk) block; of one j row inside it; offset of its scales
+    constexpr int PC = 3 + XV;                     // memory operations per thread and chunk: 2 element loads + 1 side-data load + the A staging
+    constexpr size_t WCH = 17408, WU = 8192, WS = 16384;   // bytes of one (tile, chunk) block; of one j row inside it; offset of its side data
     extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
     E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
     __shared__ int lst[MOE_MAX_ROWS];
@@ -2685,25 +2586,22 @@ __device__ __forceinline__ void moe4_expert_gemm(const typename TT::elem *__rest
 
     const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
     const char *wtile = reinterpret_cast<const char *>(W4) + ((size_t)expert * (N / GEMM_COLS) + blockIdx.x) * n_chunks * WCH;
-    const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)tid * 2;
+    const uint32_t wlane = (uint32_t)tid * 16, slane = F::slane(tid, w, n);
     const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
 
     floatx4 acc[RT];
 #pragma unroll
     for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
+    // the pipeline of gemm_skinny_w4, statement for statement: in-out load destinations defined once, re-defined behind the counted wait
     u32x4 wr[DEPTH][2];
-    unsigned sc8[DEPTH];                           // the chunk's two e8m0 codes of this lane: bits 0-7 unit 0, bits 8-15 unit 1
+    side_t sd[DEPTH];
 #pragma unroll
-    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(sc8[d]));
+    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(sd[d]));
     auto load_wj = [&](u32x4 (&dst)[2], int c, int j) {
         const char *p = wtile + (size_t)c * WCH;
         asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[j]) : "v"(wlane), "s"(p + WU * j) : "memory");
     };
-    auto load_s = [&](unsigned &dst, int c) {
-        const char *p = wtile + (size_t)c * WCH + WS;
-        asm volatile("global_load_ushort %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
-    };
+    auto load_s = [&](side_t &dst, int c) { F::load_side(dst, slane, wtile + (size_t)c * WCH + WS); };
     auto stage_xi = [&](int c, int buf, int i) {
         const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
         const E *src = A + (size_t)srow[i] * K + (size_t)c * GEMM_KC + 8 * unit;
@@ -2711,32 +2609,31 @@ __device__ __forceinline__ void moe4_expert_gemm(const typename TT::elem *__rest
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
         asm volatile("" ::: "memory");
     };
-    auto load_w = [&](u32x4 (&dst)[2], unsigned &sdst, int c) {
+    auto load_w = [&](u32x4 (&dst)[2], side_t &sdst, int c) {
         load_wj(dst, c, 0); load_wj(dst, c, 1); load_s(sdst, c);
     };
     auto stage_x = [&](int c, int buf) {
 #pragma unroll
         for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
     };
-    auto phase = [&](u32x4 (&cur)[2], unsigned &cs, int c, int buf) {
+    auto phase = [&](u32x4 (&cur)[2], side_t &cs, int c, int buf) {
         gemm_wait_younger_deep<DEPTH, PC>(n_chunks - 1 - c);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
-        // re-defined behind the counted wait (volatile asm keeps its order): no conversion can be scheduled above it
         asm volatile("" : "+v"(cs) : : "memory");
-        const unsigned e8s = cs;
+        const side_t side = cs;
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             asm volatile("" : "+v"(cur[j]) : : "memory");
-            const float sc = __builtin_bit_cast(float, ((e8s >> (8 * j)) & 0xffu) << 23);       // 2^(e8 - 127)
+            const auto grp = F::template group<TT>(side, j);
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const int u = 16 * j + 4 * g + 2 * h;
                 const uint32_t a0 = xbase + (uint32_t)(u ^ n) * 16, a1 = xbase + (uint32_t)((u + 1) ^ n) * 16;
                 u32x4 r[RT][2];
-                gemm_f4_read_a<RT>(r, a0, a1);
-                const auto lo = F4Widen<TT>::cvt(cur[j][2 * h], sc), hi = F4Widen<TT>::cvt(cur[j][2 * h + 1], sc);
+                gemm_read_a2<RT>(r, a0, a1);
+                const auto lo = F::template cvt<TT>(cur[j][2 * h], grp), hi = F::template cvt<TT>(cur[j][2 * h + 1], grp);
 #pragma unroll
                 for (int mt = 0; mt < RT; mt++) {
                     acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
@@ -2755,14 +2652,14 @@ __device__ __forceinline__ void moe4_expert_gemm(const typename TT::elem *__rest
     };
 #pragma unroll
     for (int d = 0; d < DEPTH; d++)
-        if (d < n_chunks) { load_w(wr[d], sc8[d], d); stage_x(d, d); }
+        if (d < n_chunks) { load_w(wr[d], sd[d], d); stage_x(d, d); }
     int buf = 0;
     for (int c = 0; c < n_chunks; c += DEPTH) {
 #pragma unroll
         for (int d = 0; d < DEPTH; d++)
-            if (c + d < n_chunks) { phase(wr[d], sc8[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+            if (c + d < n_chunks) { phase(wr[d], sd[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
     }
-    // C layout of mfma_16x16: lane holds rows 4g + r of column n; the block scales went in with the conversion
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n; block scales / scale and zero point went in with the widening
     if constexpr (GU) {
         float *ex = reinterpret_cast<float *>(gemm_lds);            // [R][64] up values; the A tiles are dead by now
         __syncthreads();
@@ -2801,334 +2698,103 @@ template <typename TT, int RT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe4_gate_up_silu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4,
                                                                          const int *__restrict__ ws, typename TT::elem *__restrict__ act,
                                                                          int K, int N, int n_chunks, int top_k) {
-    moe4_expert_gemm<TT, RT, true>(h, W4, ws, act, K, N, n_chunks, top_k);
+    moe_w4_expert_gemm<W4Mx, TT, RT, true, false>(h, W4, ws, act, K, N, n_chunks, top_k);
 }
 
 template <typename TT, int RT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe4_down(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4,
                                                                  const int *__restrict__ ws, typename TT::elem *__restrict__ y,
                                                                  int K, int N, int n_chunks, int top_k) {
-    moe4_expert_gemm<TT, RT, false>(act, W4, ws, y, K, N, n_chunks, top_k);
+    moe_w4_expert_gemm<W4Mx, TT, RT, false, false>(act, W4, ws, y, K, N, n_chunks, top_k);
 }
 
-template <typename TT, int RT, bool GU>
-static hipError_t moe4_gemm_launch(dim3 grid, hipStream_t st, const void *A, const void *W4, const int *ws, void *out, int K, int N, int top_k) {
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i4_gate_up_silu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4,
+                                                                           const int *__restrict__ ws, typename TT::elem *__restrict__ act,
+                                                                           int K, int N, int n_chunks, int top_k) {
+    moe_w4_expert_gemm<W4Int, TT, RT, true, false>(h, W4, ws, act, K, N, n_chunks, top_k);
+}
+
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i4_down(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4,
+                                                                   const int *__restrict__ ws, typename TT::elem *__restrict__ y,
+                                                                   int K, int N, int n_chunks, int top_k) {
+    moe_w4_expert_gemm<W4Int, TT, RT, false, false>(act, W4, ws, y, K, N, n_chunks, top_k);
+}
+
+template <typename F, typename TT, int RT, bool GU>
+static hipError_t moe_w4_gemm_launch(dim3 grid, hipStream_t st, const void *A, const void *W4, const int *ws, void *out, int K, int N, int top_k) {
     typedef typename TT::elem E;
-    constexpr int lds = (Moe4Depth<RT>::value + 1) * 16 * RT * GEMM_KC * 2;
-    if constexpr (GU) {
-        if constexpr (lds > 65536) {
-            static unsigned long long done = 0ull;                 // per-device (samd_common.h)
-            const hipError_t attr = samd_reserve_lds((const void *)k_moe4_gate_up_silu<TT, RT>, lds, &done);
-            if (attr != hipSuccess) return attr;
-        }
-        hipLaunchKernelGGL((k_moe4_gate_up_silu<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const unsigned char *)W4, ws, (E *)out, K, N,
-                           K / GEMM_KC, top_k);
-    } else {
-        if constexpr (lds > 65536) {
-            static unsigned long long done = 0ull;
-            const hipError_t attr = samd_reserve_lds((const void *)k_moe4_down<TT, RT>, lds, &done);
-            if (attr != hipSuccess) return attr;
-        }
-        hipLaunchKernelGGL((k_moe4_down<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const unsigned char *)W4, ws, (E *)out, K, N,
-                           K / GEMM_KC, top_k);
-    }
-    return hipSuccess;
+    constexpr auto kern = F::mx ? (GU ? k_moe4_gate_up_silu<TT, RT> : k_moe4_down<TT, RT>) : (GU ? k_moe_i4_gate_up_silu<TT, RT> : k_moe_i4_down<TT, RT>);
+    return w4_launch<kern, (MoeW4Depth<RT>::value + 1) * 16 * RT * GEMM_KC * 2>(grid, st, (const E *)A, (const unsigned char *)W4, ws, (E *)out, K, N, K / GEMM_KC, top_k);
 }
 
-template <bool GU>
-static hipError_t moe4_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W4, const int *ws, void *out, int K, int N, int top_k) {
-#define GO(TT, RT) return moe4_gemm_launch<TT, RT, GU>(grid, st, A, W4, ws, out, K, N, top_k)
+template <typename F, bool GU>
+static hipError_t moe_w4_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W4, const int *ws, void *out, int K, int N, int top_k) {
+#define GO(TT, RT) return moe_w4_gemm_launch<F, TT, RT, GU>(grid, st, A, W4, ws, out, K, N, top_k)
 #define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
     if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
 #undef ROWS
 #undef GO
+}
+
+template <typename F>
+static int moe_w4_gate_up_silu(const char *fn, const void *d_h, const void *d_Wgu4, const void *d_ws, int rows_pad, int hidden, int moe_inter, int n_experts, int top_k,
+                               void *d_act, int dtype, void *stream) {
+    if (!d_h || !d_Wgu4 || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
+        samd_set_error("%s: " MOE_SHAPE_MSG, fn); return SAMD_E_INVALID;
+    }
+    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const hipError_t e = moe_w4_gemm_dispatch<F, true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu4, (const int *)d_ws, d_act,
+                                                       hidden, 2 * moe_inter, top_k);
+    if (e != hipSuccess) { samd_set_error("%s: %s", fn, hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+template <typename F>
+static int moe_w4_down_combine(const char *fn, const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                               int rows_pad, int hidden, int moe_inter, int n_experts, int top_k, void *d_out, int dtype, void *stream) {
+    if (!d_act || !d_Wdown4 || !d_topk_idx || !d_topk_w || !d_n || !d_ws || !d_out || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
+        samd_set_error("%s: " MOE_SHAPE_MSG, fn); return SAMD_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    void *y = (char *)d_ws + MOE_WS_Y_OFF;
+    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const hipError_t e = moe_w4_gemm_dispatch<F, false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown4, (const int *)d_ws, y, moe_inter, hidden, top_k);
+    if (e != hipSuccess) { samd_set_error("%s: %s", fn, hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
+    if (dtype == SAMD_F16)
+        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
+    else
+        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
+    LAUNCHCHK();
+    return SAMD_OK;
 }
 
 extern "C" {
 
 int samd_moe_gate_up_silu_f4(const void *d_h, const void *d_Wgu4, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
                              int32_t top_k, void *d_act, int32_t dtype, void *stream) {
-    if (!d_h || !d_Wgu4 || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
-        samd_set_error("samd_moe_gate_up_silu_f4: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
-    }
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
-    const hipError_t e = moe4_gemm_dispatch<true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu4, (const int *)d_ws, d_act,
-                                                  hidden, 2 * moe_inter, top_k);
-    if (e != hipSuccess) { samd_set_error("samd_moe_gate_up_silu_f4: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
-    LAUNCHCHK();
-    return SAMD_OK;
+    return moe_w4_gate_up_silu<W4Mx>("samd_moe_gate_up_silu_f4", d_h, d_Wgu4, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_act, dtype, stream);
 }
 
 int samd_moe_down_combine_f4(const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
                              int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream) {
-    if (!d_act || !d_Wdown4 || !d_topk_idx || !d_topk_w || !d_n || !d_ws || !d_out || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
-        samd_set_error("samd_moe_down_combine_f4: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    void *y = (char *)d_ws + MOE_WS_Y_OFF;
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
-    const hipError_t e = moe4_gemm_dispatch<false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown4, (const int *)d_ws, y, moe_inter, hidden, top_k);
-    if (e != hipSuccess) { samd_set_error("samd_moe_down_combine_f4: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
-    LAUNCHCHK();
-    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
-    if (dtype == SAMD_F16)
-        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
-    else
-        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
-    LAUNCHCHK();
-    return SAMD_OK;
+    return moe_w4_down_combine<W4Mx>("samd_moe_down_combine_f4", d_act, d_Wdown4, d_topk_idx, d_topk_w, d_n, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_out, dtype,
+                                     stream);
 }
-
-}  // extern "C"
-
-// ================================================================================================
-// Mixture-of-experts MLP with INT4 (AWQ / GPTQ) experts: the gathered expert GEMMs over k_gemm_skinny_i4's 4.25-bit weight stream.
-//   samd_moe_gate_up_silu_i4 / samd_moe_down_combine_i4: the fixed grid (N / 128, min(E, rows_pad * top_k)), the early exit of slots
-//   >= ws[0], the list in static LDS, the gathered LDS-DMA A tile (srow), the A-side unit order (16 j + 4 g + i) ^ n, the counted waits
-//   with in-out load destinations, both epilogues (HF's roundings; rows >= cnt not stored) and k_moe_combine are moe4_expert_gemm's,
-//   statement for statement; the weight side is k_gemm_skinny_i4's: 17 KiB (tile, chunk) blocks, two 16-byte nt element loads and ONE
-//   8-byte nt group-data load per lane and chunk (slane = (16 w + n) * 8: the four g lanes of a row read the same 8 bytes),
-//   I4Widen<TT>::group / cvt behind the counted wait -- W = rne_dtype((q - z) * s), one rounding, fp32 accumulation in chunk order.  No
-//   split-K, no atomics: a row's output has the same bits whatever shares the launch.
-//   A function of its own, not a weight-side policy of moe4_expert_gemm: the MXFP4 expert kernels are left textually alone, so their
-//   gfx950 ISA cannot move.
-//   PACKED LAYOUT: the experts laid end to end are ONE matrix of E * N rows in samd_gemm_pack_i4's layout (the pack call with N := E * N);
-//   expert e's tile t is global tile e * N / 128 + t, at ((e * N / 128 + t) * K / 256 + c) * 17408 bytes for chunk c.  gate|up: the rows
-//   are permuted before packing as for MXFP4 (samd_hip/moe.py: gate_up_tile_order; groups run along k, so whole rows move with their
-//   zero points and scales).  The buffer is dtype-specific (the scales and the pre-biased zero points are in the model dtype).
-//   DEPTH per row tile: Moe4Depth's table (16 rows 8, 32 rows 3, 48 rows 2, 64 rows 3) under the same three constraints -- (DEPTH - 1) *
-//   PC <= 63 (28, 10, 6, 14), (DEPTH + 1) A buffers of R * 512 bytes + the list inside 160 KiB for the intended workgroups per CU (72 KiB
-//   x 2, 64 KiB x 2, 72 KiB x 2, 128 KiB x 1), no spills: the group data costs one VGPR per chunk in flight more than MXFP4's scales (8
-//   more at 16 rows) and every instantiation still compiles without scratch (tests/test_moe_int4_cpu.py reads it from the code object's
-//   metadata).  An expert's stream is often SHORTER than the depth (1 chunk for down at moe_inter 256): the skipped prologue loads leave
-//   their in-out destination registers as they are.  The table is NOT swept on a GPU; profiles/moe_experts_int4.md says what was measured.
-// ================================================================================================
-template <int RT> struct MoeI4Depth { static constexpr int value = RT == 1 ? 8 : RT == 3 ? 2 : 3; };
-
-template <typename TT, int RT, bool GU, bool WIDE = false>          // WIDE: a tile record of the wide workspace names the expert and its list
-__device__ __forceinline__ void moe_i4_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
-                                                 typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
-    typedef typename TT::elem E;
-    constexpr int DEPTH = MoeI4Depth<RT>::value;
-    constexpr int R = 16 * RT;
-    constexpr int NT = 64 * GEMM_WAVES;
-    constexpr int XV = (R * 32) / NT;
-    constexpr int NB = DEPTH + 1;
-    constexpr int PC = 3 + XV;                     // memory operations per thread and chunk: 2 element loads + 1 group-data load + the A staging
-    constexpr size_t WCH = 17408, WU = 8192, WS = 16384;   // bytes of one (tile, chunk) block; of one j row inside it; offset of its group data
-    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
-    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
-    __shared__ int lst[MOE_MAX_ROWS];
-
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    const int slot_a = blockIdx.y;
-    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts (WIDE: of tiles; ws[0] = the tile count)
-    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
-    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
-    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
-    cnt = cnt > R ? R : cnt;
-    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
-    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
-    __syncthreads();
-    // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
-    int srow[XV];
-#pragma unroll
-    for (int i = 0; i < XV; i++) { const int p = lst[(tid >> 5) + 16 * i]; srow[i] = GU ? p / top_k : p; }
-
-    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
-    const char *wtile = reinterpret_cast<const char *>(W4) + ((size_t)expert * (N / GEMM_COLS) + blockIdx.x) * n_chunks * WCH;
-    const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)(16 * w + n) * 8;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
-
-    floatx4 acc[RT];
-#pragma unroll
-    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
-    u32x4 wr[DEPTH][2];
-    u32x2 gdr[DEPTH];                              // the chunk's group data of this lane's row: {s0 | s1 << 16, zb0 | zb1 << 16}
-#pragma unroll
-    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(gdr[d]));
-    auto load_wj = [&](u32x4 (&dst)[2], int c, int j) {
-        const char *p = wtile + (size_t)c * WCH;
-        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[j]) : "v"(wlane), "s"(p + WU * j) : "memory");
-    };
-    auto load_s = [&](u32x2 &dst, int c) {
-        const char *p = wtile + (size_t)c * WCH + WS;
-        asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
-    };
-    auto stage_xi = [&](int c, int buf, int i) {
-        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
-        const E *src = A + (size_t)srow[i] * K + (size_t)c * GEMM_KC + 8 * unit;
-        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
-        asm volatile("" ::: "memory");
-    };
-    auto load_w = [&](u32x4 (&dst)[2], u32x2 &sdst, int c) {
-        load_wj(dst, c, 0); load_wj(dst, c, 1); load_s(sdst, c);
-    };
-    auto stage_x = [&](int c, int buf) {
-#pragma unroll
-        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
-    };
-    auto phase = [&](u32x4 (&cur)[2], u32x2 &cs, int c, int buf) {
-        gemm_wait_younger_deep<DEPTH, PC>(n_chunks - 1 - c);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
-        // re-defined behind the counted wait (volatile asm keeps its order): no widening can be scheduled above it (see k_gemm_skinny_i4)
-        asm volatile("" : "+v"(cs) : : "memory");
-        const u32x2 gd = cs;
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            asm volatile("" : "+v"(cur[j]) : : "memory");
-            const auto grp = I4Widen<TT>::group(gd, j);
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int u = 16 * j + 4 * g + 2 * h;
-                const uint32_t a0 = xbase + (uint32_t)(u ^ n) * 16, a1 = xbase + (uint32_t)((u + 1) ^ n) * 16;
-                u32x4 r[RT][2];
-                gemm_f4_read_a<RT>(r, a0, a1);
-                const auto lo = I4Widen<TT>::cvt(cur[j][2 * h], grp), hi = I4Widen<TT>::cvt(cur[j][2 * h + 1], grp);
-#pragma unroll
-                for (int mt = 0; mt < RT; mt++) {
-                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
-                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, acc[mt]);
-                }
-            }
-            if (RT >= 3 && c + DEPTH < n_chunks) {             // 48 / 64 rows: refill per unit (see k_gemm_skinny)
-                load_wj(cur, c + DEPTH, j);
-                if (j == 1) load_s(cs, c + DEPTH);
-#pragma unroll
-                for (int i = 2 * j; i < 2 * j + 2; i++)
-                    if (i < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, i);
-            }
-        }
-        if (RT < 3 && c + DEPTH < n_chunks) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
-    };
-#pragma unroll
-    for (int d = 0; d < DEPTH; d++)
-        if (d < n_chunks) { load_w(wr[d], gdr[d], d); stage_x(d, d); }
-    int buf = 0;
-    for (int c = 0; c < n_chunks; c += DEPTH) {
-#pragma unroll
-        for (int d = 0; d < DEPTH; d++)
-            if (c + d < n_chunks) { phase(wr[d], gdr[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
-    }
-    // C layout of mfma_16x16: lane holds rows 4g + r of column n; scale and zero point went in with the widening
-    if constexpr (GU) {
-        float *ex = reinterpret_cast<float *>(gemm_lds);            // [R][64] up values; the A tiles are dead by now
-        __syncthreads();
-        if (w >= 4) {
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) ex[(16 * mt + 4 * g + r) * 64 + 16 * (w - 4) + n] = acc[mt][r];
-        }
-        __syncthreads();
-        if (w < 4) {
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int m = 16 * mt + 4 * g + r;
-                    if (m >= cnt) continue;
-                    // the roundings of HF's act_fn(gate) * up in the model dtype (same as moe_expert_gemm)
-                    const float gf = (float)(E)acc[mt][r], uf = (float)(E)ex[m * 64 + 16 * w + n];
-                    const E sv = (E)(gf / (1.f + __expf(-gf)));
-                    out[(size_t)lst[m] * (N / 2) + blockIdx.x * 64 + 16 * w + n] = (E)((float)sv * uf);
-                }
-        }
-    } else {
-#pragma unroll
-        for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int m = 16 * mt + 4 * g + r;
-                if (m < cnt) out[(size_t)lst[m] * N + n0 + n] = (E)acc[mt][r];
-            }
-    }
-}
-
-template <typename TT, int RT>
-__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i4_gate_up_silu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4,
-                                                                         const int *__restrict__ ws, typename TT::elem *__restrict__ act,
-                                                                         int K, int N, int n_chunks, int top_k) {
-    moe_i4_expert_gemm<TT, RT, true>(h, W4, ws, act, K, N, n_chunks, top_k);
-}
-
-template <typename TT, int RT>
-__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i4_down(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4,
-                                                                 const int *__restrict__ ws, typename TT::elem *__restrict__ y,
-                                                                 int K, int N, int n_chunks, int top_k) {
-    moe_i4_expert_gemm<TT, RT, false>(act, W4, ws, y, K, N, n_chunks, top_k);
-}
-
-template <typename TT, int RT, bool GU>
-static hipError_t moe_i4_gemm_launch(dim3 grid, hipStream_t st, const void *A, const void *W4, const int *ws, void *out, int K, int N, int top_k) {
-    typedef typename TT::elem E;
-    constexpr int lds = (MoeI4Depth<RT>::value + 1) * 16 * RT * GEMM_KC * 2;
-    if constexpr (GU) {
-        if constexpr (lds > 65536) {
-            static unsigned long long done = 0ull;                 // per-device (samd_common.h)
-            const hipError_t attr = samd_reserve_lds((const void *)k_moe_i4_gate_up_silu<TT, RT>, lds, &done);
-            if (attr != hipSuccess) return attr;
-        }
-        hipLaunchKernelGGL((k_moe_i4_gate_up_silu<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const unsigned char *)W4, ws, (E *)out, K, N,
-                           K / GEMM_KC, top_k);
-    } else {
-        if constexpr (lds > 65536) {
-            static unsigned long long done = 0ull;
-            const hipError_t attr = samd_reserve_lds((const void *)k_moe_i4_down<TT, RT>, lds, &done);
-            if (attr != hipSuccess) return attr;
-        }
-        hipLaunchKernelGGL((k_moe_i4_down<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const unsigned char *)W4, ws, (E *)out, K, N,
-                           K / GEMM_KC, top_k);
-    }
-    return hipSuccess;
-}
-
-template <bool GU>
-static hipError_t moe_i4_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W4, const int *ws, void *out, int K, int N, int top_k) {
-#define GO(TT, RT) return moe_i4_gemm_launch<TT, RT, GU>(grid, st, A, W4, ws, out, K, N, top_k)
-#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
-    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
-#undef ROWS
-#undef GO
-}
-
-extern "C" {
 
 int samd_moe_gate_up_silu_i4(const void *d_h, const void *d_Wgu4, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
                              int32_t top_k, void *d_act, int32_t dtype, void *stream) {
-    if (!d_h || !d_Wgu4 || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
-        samd_set_error("samd_moe_gate_up_silu_i4: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
-    }
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
-    const hipError_t e = moe_i4_gemm_dispatch<true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu4, (const int *)d_ws, d_act,
-                                                  hidden, 2 * moe_inter, top_k);
-    if (e != hipSuccess) { samd_set_error("samd_moe_gate_up_silu_i4: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
-    LAUNCHCHK();
-    return SAMD_OK;
+    return moe_w4_gate_up_silu<W4Int>("samd_moe_gate_up_silu_i4", d_h, d_Wgu4, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_act, dtype, stream);
 }
 
 int samd_moe_down_combine_i4(const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
                              int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream) {
-    if (!d_act || !d_Wdown4 || !d_topk_idx || !d_topk_w || !d_n || !d_ws || !d_out || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
-        samd_set_error("samd_moe_down_combine_i4: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    void *y = (char *)d_ws + MOE_WS_Y_OFF;
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
-    const hipError_t e = moe_i4_gemm_dispatch<false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown4, (const int *)d_ws, y, moe_inter, hidden, top_k);
-    if (e != hipSuccess) { samd_set_error("samd_moe_down_combine_i4: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
-    LAUNCHCHK();
-    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
-    if (dtype == SAMD_F16)
-        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
-    else
-        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
-    LAUNCHCHK();
-    return SAMD_OK;
+    return moe_w4_down_combine<W4Int>("samd_moe_down_combine_i4", d_act, d_Wdown4, d_topk_idx, d_topk_w, d_n, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_out, dtype,
+                                      stream);
 }
 
 }  // extern "C"
@@ -3209,7 +2875,7 @@ __device__ __forceinline__ void moe8_expert_gemm(const typename TT::elem *__rest
     floatx4 acc[RT];
 #pragma unroll
     for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
+    // the load destinations: one value each, defined once; every load is an in-out operand of it (see gemm_skinny_w4)
     u32x4 wr[DEPTH][4];
 #pragma unroll
     for (int d = 0; d < DEPTH; d++)
@@ -3249,7 +2915,7 @@ __device__ __forceinline__ void moe8_expert_gemm(const typename TT::elem *__rest
             }
             const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
             u32x4 r[RT][2];
-            gemm_f4_read_a<RT>(r, a0, a1);
+            gemm_read_a2<RT>(r, a0, a1);
             // re-defined behind the counted wait (volatile asm keeps its order): no conversion can be scheduled above it
             asm volatile("" : "+v"(cur[b]) : : "memory");
             const auto lo = F8Widen<TT>::cvt(cur[b][0], cur[b][1]), hi = F8Widen<TT>::cvt(cur[b][2], cur[b][3]);
@@ -3477,7 +3143,7 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT <= 2 ? 4 : 2) void k_gemm_skinn
     floatx4 acc[RT];
 #pragma unroll
     for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    // the load destinations: one value each, defined once; every load is an in-out operand of it (see k_gemm_skinny_f4)
+    // the load destinations: one value each, defined once; every load is an in-out operand of it (see gemm_skinny_w4)
     u32x4 wr[DEPTH][4];
 #pragma unroll
     for (int d = 0; d < DEPTH; d++)
@@ -3518,7 +3184,7 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT <= 2 ? 4 : 2) void k_gemm_skinn
             }
             const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
             u32x4 r[RT][2];
-            gemm_f4_read_a<RT>(r, a0, a1);
+            gemm_read_a2<RT>(r, a0, a1);
             // re-defined behind the counted wait (volatile asm keeps its order): no conversion can be scheduled above it
             asm volatile("" : "+v"(cur[b]) : : "memory");
             if (b == 3 && c + 1 < c1) snext = srow[c + 1];     // behind this phase's last A read (whose wait would otherwise cover it)
@@ -3612,7 +3278,7 @@ int samd_gemm_skinny_f8b(const void *d_A, const void *d_W8p, const float *d_sinv
 // Mixture-of-experts MLP over MANY rows (a prompt in one pass): samd_moe_wide_route / _lists / _gate_up_silu / _down_combine serve 1 ..
 // MOEW_MAX_ROWS rows (padded to 64 inside; rows >= *d_n route nowhere) with the kernels above.  An expert's list may now be longer than a
 // 64-row tile, so the lists are followed by a TILE TABLE -- one record {expert, first entry, entries <= 64} per 64 entries of an expert's
-// list, the tiles of one expert adjacent, experts ascending -- and an expert GEMM workgroup is moe_expert_gemm / moe4_ / moe_i4_ /
+// list, the tiles of one expert adjacent, experts ascending -- and an expert GEMM workgroup is moe_expert_gemm / moe_w4_ /
 // moe8_expert_gemm<TT, 4, GU, WIDE = true>: the 64-row tile's stream, MFMA sequence, epilogues and roundings, with `expert`, `cnt` and the
 // list taken from its tile record instead of an active slot.  A row's sum does not depend on the tile it sits in (chunk order over k, no
 // split-K), so every row gets the bits the <= 64-row calls give it.
@@ -3690,22 +3356,22 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe_dn(const typename T
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe4_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
                                                                 typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
-    moe4_expert_gemm<TT, 4, true, true>(h, W4, ws, act, K, N, n_chunks, top_k);
+    moe_w4_expert_gemm<W4Mx, TT, 4, true, true>(h, W4, ws, act, K, N, n_chunks, top_k);
 }
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe4_dn(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
                                                                 typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
-    moe4_expert_gemm<TT, 4, false, true>(act, W4, ws, y, K, N, n_chunks, top_k);
+    moe_w4_expert_gemm<W4Mx, TT, 4, false, true>(act, W4, ws, y, K, N, n_chunks, top_k);
 }
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe_i4_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
                                                                   typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
-    moe_i4_expert_gemm<TT, 4, true, true>(h, W4, ws, act, K, N, n_chunks, top_k);
+    moe_w4_expert_gemm<W4Int, TT, 4, true, true>(h, W4, ws, act, K, N, n_chunks, top_k);
 }
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe_i4_dn(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
                                                                   typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
-    moe_i4_expert_gemm<TT, 4, false, true>(act, W4, ws, y, K, N, n_chunks, top_k);
+    moe_w4_expert_gemm<W4Int, TT, 4, false, true>(act, W4, ws, y, K, N, n_chunks, top_k);
 }
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 1) void k_wmoe8_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W8, const float *__restrict__ stab,
@@ -3738,15 +3404,11 @@ static hipError_t wmoe_gemm_format(int fmt, dim3 grid, hipStream_t st, const voi
         if constexpr (GU) return wmoe_launch<k_wmoe_gu<TT>>(3 * tile, grid, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, nc, top_k);
         else return wmoe_launch<k_wmoe_dn<TT>>(3 * tile, grid, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, nc, top_k);
     }
-    if (fmt == 1) {
-        constexpr int lds = (Moe4Depth<4>::value + 1) * tile;
-        if constexpr (GU) return wmoe_launch<k_wmoe4_gu<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
-        else return wmoe_launch<k_wmoe4_dn<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
-    }
-    if (fmt == 2) {
-        constexpr int lds = (MoeI4Depth<4>::value + 1) * tile;
-        if constexpr (GU) return wmoe_launch<k_wmoe_i4_gu<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
-        else return wmoe_launch<k_wmoe_i4_dn<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
+    if (fmt == 1 || fmt == 2) {
+        constexpr int lds = (MoeW4Depth<4>::value + 1) * tile;
+        constexpr auto mx = GU ? k_wmoe4_gu<TT> : k_wmoe4_dn<TT>, i4 = GU ? k_wmoe_i4_gu<TT> : k_wmoe_i4_dn<TT>;
+        return fmt == 1 ? wmoe_launch<mx>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k)
+                        : wmoe_launch<i4>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
     }
     constexpr int lds = (Moe8Depth<4>::value + 1) * tile;
     const float *stab = reinterpret_cast<const float *>(reinterpret_cast<const char *>(W) + moe8_scale_offset(w_rows, (size_t)K));

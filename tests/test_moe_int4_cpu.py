@@ -330,7 +330,7 @@ def test_a_weights_dict_with_int4_experts_is_checked_before_device_work():
 
 
 # ------------------------------------------------------------------------------------------------ the compiled kernels
-DEPTH = {1: 8, 2: 3, 3: 2, 4: 3}                                 # MoeI4Depth (csrc/gemm_kernels.hip), per row tile RT = rows / 16
+DEPTH = {1: 8, 2: 3, 3: 2, 4: 3}                                 # MoeW4Depth (csrc/gemm_kernels.hip), per row tile RT = rows / 16
 WORKGROUPS_PER_CU = {1: 2, 2: 2, 3: 2, 4: 1}                     # what the depth table is chosen for
 LIST_LDS = 1024                                                  # the list: 64 ints of static LDS, 1 KiB after the dynamic part's alignment
 
@@ -362,7 +362,7 @@ def test_int4_expert_kernels_are_in_the_library_use_no_scratch_and_fit_their_lds
     for name, v in sorted(kernels.items()):
         rt = int(re.search(r"Li(\d)E", name).group(1))
         # the code object holds the static part only (the list).  The (DEPTH + 1) A buffers of R * 512 bytes are dynamic LDS, whose size is
-        # the launch's argument and is NOT in the code object: DEPTH above restates MoeI4Depth, so this line checks the documented table
+        # the launch's argument and is NOT in the code object: DEPTH above restates MoeW4Depth, so this line checks the documented table
         # against the 160 KiB budget and cannot notice the kernel's table and the launch's size drifting apart (the GPU tests run every
         # row tile with streams longer than the ring, which a too-small dynamic size would not survive bit for bit)
         lds = (DEPTH[rt] + 1) * 16 * rt * 512 + v["static_lds"]
