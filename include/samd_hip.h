@@ -770,6 +770,22 @@ int samd_moe_gate_up_silu_i4(const void *d_h, const void *d_Wgu4, const void *d_
                              int32_t top_k, void *d_act, int32_t dtype, void *stream);
 int samd_moe_down_combine_i4(const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
                              int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream);
+/* The same two expert launches over INT8 (GPTQ 8-bit) experts: unsigned 8-bit codes, one per byte, with one scale (model dtype) and one 8-bit
+ * zero point per 128 along k.  The numeric contract is samd_hip/int8.py's, as for samd_gemm_skinny_i8: W = rne_dtype((q - z) * s) -- ONE
+ * rounding, to the model dtype -- fp32 accumulation in chunk order, the epilogues' roundings unchanged.  Routing, the workspace,
+ * samd_moe_route / samd_moe_lists and the combine are the calls above; signatures, shapes (rows_pad 16/32/48/64, hidden and moe_inter
+ * multiples of 256, experts <= 256, top-k <= 8), grids and errors are those of the _i4 calls; both are capturable.
+ *   d_Wgu8 / d_Wdown8      the E experts laid end to end as ONE matrix of E * N rows in samd_gemm_pack_i8's layout (samd_gemm_pack_i8 with
+ *                          N := E * N; N = 2 * moe_inter, K = hidden for gate|up; N = hidden, K = moe_inter for down): E * N * K * 33 / 32
+ *                          bytes, expert e's tile t being tile e * N / 128 + t.  For gate|up the rows (codes, zero points and scales: groups
+ *                          run along k) are permuted BEFORE packing exactly as for the _i4 call (samd_hip/moe.py: pack_experts_int8).  The
+ *                          buffer is specific to the dtype it was packed for.
+ *   samd_moe_gate_up_silu_i8   as samd_moe_gate_up_silu.
+ *   samd_moe_down_combine_i8   as samd_moe_down_combine: the 8-bit down launch, then the same combine kernel. */
+int samd_moe_gate_up_silu_i8(const void *d_h, const void *d_Wgu8, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
+                             int32_t top_k, void *d_act, int32_t dtype, void *stream);
+int samd_moe_down_combine_i8(const void *d_act, const void *d_Wdown8, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                             int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream);
 /* The same two expert launches over block-scaled FP8 experts (the official Qwen3-MoE FP8 checkpoints): OCP e4m3fn codes q with one fp32
  * scale s per 128 x 128 block.  The numeric contract is samd_hip/fp8.py's: W[n][k] = float(q[n][k]) * s[n / 128][k / 128], s finite and
  * positive; W is never formed: out = sum_b s_b * (sum_{k in block b} A[m][k] * q[n][k]), the inner sum an fp32 MFMA accumulation over the
@@ -816,7 +832,8 @@ int samd_moe_down_combine_f8(const void *d_act, const void *d_Wdown8, const int3
  *                              count exit at once.
  *   samd_moe_wide_down_combine as samd_moe_down_combine, d_out [rows_pad][hidden]; rows >= *d_n are zero.
  *   expert_format              what d_Wgu / d_Wdown hold: 0 the model dtype (samd_moe_pack_experts), 1 mxfp4 (the _f4 calls' buffer),
- *                              2 int4g128 (the _i4 calls'), 3 fp8b128 (the _f8 calls'; hidden and moe_inter <= 16384).
+ *                              2 int4g128 (the _i4 calls'), 3 fp8b128 (the _f8 calls'; hidden and moe_inter <= 16384), 5 int8g128 (the
+ *                              _i8 calls').  4 is not assigned and is refused as unknown, as every other value is.
  * SAMD_E_INVALID with the error text, before any device work: rows < 1 or > 4096, an unknown expert_format, a shape outside the above,
  * a null pointer. */
 int64_t samd_moe_wide_workspace_layout(int32_t field, int32_t rows, int32_t top_k);

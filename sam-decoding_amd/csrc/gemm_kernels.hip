@@ -2800,6 +2800,250 @@ int samd_moe_down_combine_i4(const void *d_act, const void *d_Wdown4, const int3
 }  // extern "C"
 
 // ================================================================================================
+// Mixture-of-experts MLP with INT8 experts (GPTQ: unsigned 8-bit codes, one scale and one 8-bit zero point per 128 elements along k): the
+// gathered expert GEMMs of moe_expert_gemm over k_gemm_skinny_i8's 8.25-bit weight stream.
+//   samd_moe_gate_up_silu_i8 / samd_moe_down_combine_i8: the expert side is moe_w4_expert_gemm's, statement for statement -- the fixed grid
+//   (N / 128, min(E, rows_pad * top_k)), the routing workspace, the early exit of slots >= ws[0], the list in static LDS, the gathered
+//   LDS-DMA A tile (srow), both epilogues (HF's roundings; rows >= cnt not stored) and k_moe_combine.  The weight side is k_gemm_skinny_i8's:
+//   33 KiB (tile, chunk) blocks, four 16-byte nt code loads and one 8-byte nt group-data load per lane and chunk with in-out destinations,
+//   I8Widen behind the counted wait (W = rne_dtype((q - z) * s), ONE rounding), the A-side unit order (8 b + 2 g) ^ n, fp32 accumulation in
+//   chunk order.  No split-K, no atomics: a row's output has the same bits whatever shares the launch.
+//   A body of its own, not a policy of moe_w4_expert_gemm: the 8-bit stream has four code loads per chunk where the 4-bit one has two, one
+//   A unit pair per load where that one has two, another A-side unit order and another refill cadence at 48 / 64 rows; a policy would have
+//   to carry the whole phase.
+//   PACKED LAYOUT: the experts laid end to end are ONE matrix of E * N rows in samd_gemm_pack_i8's layout (the pack call with N := E * N);
+//   expert e's tile t is global tile e * N / 128 + t, at ((e * N / 128 + t) * K / 256 + c) * 33792 bytes for chunk c.  gate|up: the rows are
+//   permuted before packing as for INT4 (samd_hip/moe.py: gate_up_tile_order; groups run along k, so whole rows move with their zero points
+//   and scales).  E * N * K * 33 / 32 bytes; dtype-specific (the scales and the pre-biased zero points are in the model dtype).
+//   DEPTH (chunks of 32 KiB + 1 KiB in flight per workgroup), per row tile under (DEPTH - 1) * PC <= 63 with PC = 5 + RT (vmcnt: 18, 14, 8,
+//   0), (DEPTH + 1) A buffers of R * 512 bytes + the list (1 KiB of static LDS after alignment) inside 160 KiB for TWO workgroups per CU at
+//   every row tile, and 18 VGPRs per chunk in flight inside the 128 registers two workgroups per CU leave a wave, without scratch: 16 rows
+//   4 (5 x 8 = 40 KiB; 8 as for 4-bit would need 144 VGPRs), 32 rows 3 (4 x 16 = 64 KiB -- the dense 4 would need 2 x (80 + 1) KiB >
+//   160 KiB), 48 rows 2 (3 x 24 = 72 KiB, the 4-bit table's reasoning: expert streams are 1-8 chunks long, so a second workgroup that
+//   covers the first one's prologue and epilogue is worth more than depth), 64 rows 1 (2 x 32 = 64 KiB: the per-k-block refill keeps the
+//   next chunk's loads in flight behind the block in use, and the second workgroup does the rest).  The 64-row entry was compared on an
+//   MI355X against 3 at one workgroup per CU (4 x 32 = 128 KiB, 146 VGPRs), the 4-bit and FP8 tables' choice: 170 against 207 us (bf16)
+//   and 164 against 189 us (fp16) for the three-call layer at A3B geometry (profiles/moe_experts_int8.md); the other entries were not
+//   swept.  An expert's stream is often SHORTER than the depth (3 chunks for down at moe_inter 768, 1 at 256): the skipped prologue loads
+//   leave their in-out destination registers as they are (see gemm_skinny_w4).
+//   The one-pass-prefill forms are the WIDE instantiations at the 64-row tile (k_moew_i8_gu / k_moew_i8_dn, expert_format code 5: 4 stays
+//   unassigned, callers pin it as an unknown code).
+// ================================================================================================
+template <int RT> struct MoeI8Depth { static constexpr int value = RT == 1 ? 4 : RT == 3 ? 2 : RT == 4 ? 1 : 3; };
+
+template <typename TT, int RT, bool GU, bool WIDE>      // WIDE: a tile record of the wide workspace names the expert and its list
+__device__ __forceinline__ void moe_i8_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8, const int *__restrict__ ws,
+                                                   typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
+    typedef typename TT::elem E;
+    constexpr int DEPTH = MoeI8Depth<RT>::value;
+    constexpr int R = 16 * RT;
+    constexpr int NT = 64 * GEMM_WAVES;
+    constexpr int XV = (R * 32) / NT;
+    constexpr int NB = DEPTH + 1;
+    constexpr int PC = 5 + XV;                     // memory operations per thread and chunk: 4 code loads + 1 group-data load + the A staging
+    constexpr size_t WCH = 33792, WU = 8192, WS = 32768;   // bytes of one (tile, chunk) block; of one b row inside it; offset of its group data
+    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
+    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
+    __shared__ int lst[MOE_MAX_ROWS];
+
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
+    const int slot_a = blockIdx.y;
+    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts (WIDE: of tiles; ws[0] = the tile count)
+    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
+    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
+    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
+    cnt = cnt > R ? R : cnt;
+    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
+    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
+    __syncthreads();
+    // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
+    int srow[XV];
+#pragma unroll
+    for (int i = 0; i < XV; i++) { const int p = lst[(tid >> 5) + 16 * i]; srow[i] = GU ? p / top_k : p; }
+
+    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    const char *wtile = reinterpret_cast<const char *>(W8) + ((size_t)expert * (N / GEMM_COLS) + blockIdx.x) * n_chunks * WCH;
+    const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)(16 * w + n) * 8;
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
+
+    floatx4 acc[RT];
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    // the pipeline of k_gemm_skinny_i8, statement for statement: in-out load destinations defined once, re-defined behind the counted wait
+    u32x4 wr[DEPTH][4];
+    u32x2 gs[DEPTH];                               // the chunk's group data of this lane's row: {s0 | s1 << 16, zb0 | zb1 << 16}
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(wr[d][2]), "=v"(wr[d][3]), "=v"(gs[d]));
+    auto load_wb = [&](u32x4 (&dst)[4], int c, int b) {
+        const char *p = wtile + (size_t)c * WCH;
+        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[b]) : "v"(wlane), "s"(p + WU * b) : "memory");
+    };
+    auto load_s = [&](u32x2 &dst, int c) {
+        const char *p = wtile + (size_t)c * WCH + WS;
+        asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
+    };
+    auto stage_xi = [&](int c, int buf, int i) {
+        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
+        const E *src = A + (size_t)srow[i] * K + (size_t)c * GEMM_KC + 8 * unit;
+        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        asm volatile("" ::: "memory");
+    };
+    auto load_w = [&](u32x4 (&dst)[4], u32x2 &sdst, int c) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) load_wb(dst, c, b);
+        load_s(sdst, c);
+    };
+    auto stage_x = [&](int c, int buf) {
+#pragma unroll
+        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
+    };
+    auto phase = [&](u32x4 (&cur)[4], u32x2 &cs, int c, int buf) {
+        gemm_wait_younger_deep<DEPTH, PC>(n_chunks - 1 - c);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
+        asm volatile("" : "+v"(cs) : : "memory");
+        const u32x2 gd = cs;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
+            u32x4 r[RT][2];
+            gemm_read_a2<RT>(r, a0, a1);
+            asm volatile("" : "+v"(cur[b]) : : "memory");
+            const auto grp = I8Widen<TT>::group(gd, b >> 1);
+            const auto lo = I8Widen<TT>::cvt(cur[b][0], cur[b][1], grp), hi = I8Widen<TT>::cvt(cur[b][2], cur[b][3], grp);
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++) {
+                acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
+                acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, acc[mt]);
+            }
+            if (RT >= 3 && c + DEPTH < n_chunks) {             // 48 / 64 rows: refill per k block (see k_gemm_skinny)
+                load_wb(cur, c + DEPTH, b);
+                if (b < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, b);
+                if (b == 3) load_s(cs, c + DEPTH);             // (after the group data's last use)
+            }
+        }
+        if (RT < 3 && c + DEPTH < n_chunks) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
+    };
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++)
+        if (d < n_chunks) { load_w(wr[d], gs[d], d); stage_x(d, d); }
+    int buf = 0;
+    for (int c = 0; c < n_chunks; c += DEPTH) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++)
+            if (c + d < n_chunks) { phase(wr[d], gs[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+    }
+    // C layout of mfma_16x16: lane holds rows 4g + r of column n; scale and zero point went in with the widening
+    if constexpr (GU) {
+        float *ex = reinterpret_cast<float *>(gemm_lds);            // [R][64] up values; the A tiles are dead by now
+        __syncthreads();
+        if (w >= 4) {
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) ex[(16 * mt + 4 * g + r) * 64 + 16 * (w - 4) + n] = acc[mt][r];
+        }
+        __syncthreads();
+        if (w < 4) {
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int m = 16 * mt + 4 * g + r;
+                    if (m >= cnt) continue;
+                    // the roundings of HF's act_fn(gate) * up in the model dtype (same as moe_expert_gemm)
+                    const float gf = (float)(E)acc[mt][r], uf = (float)(E)ex[m * 64 + 16 * w + n];
+                    const E sv = (E)(gf / (1.f + __expf(-gf)));
+                    out[(size_t)lst[m] * (N / 2) + blockIdx.x * 64 + 16 * w + n] = (E)((float)sv * uf);
+                }
+        }
+    } else {
+#pragma unroll
+        for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int m = 16 * mt + 4 * g + r;
+                if (m < cnt) out[(size_t)lst[m] * N + n0 + n] = (E)acc[mt][r];
+            }
+    }
+}
+
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i8_gate_up_silu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W8,
+                                                                           const int *__restrict__ ws, typename TT::elem *__restrict__ act,
+                                                                           int K, int N, int n_chunks, int top_k) {
+    moe_i8_expert_gemm<TT, RT, true, false>(h, W8, ws, act, K, N, n_chunks, top_k);
+}
+
+template <typename TT, int RT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i8_down(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W8,
+                                                                   const int *__restrict__ ws, typename TT::elem *__restrict__ y,
+                                                                   int K, int N, int n_chunks, int top_k) {
+    moe_i8_expert_gemm<TT, RT, false, false>(act, W8, ws, y, K, N, n_chunks, top_k);
+}
+
+// the one-pass-prefill forms (samd_moe_wide_*, expert_format 5): the 64-row tile over the wide workspace's tile records
+template <typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moew_i8_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W8, const int *__restrict__ ws,
+                                                                  typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
+    moe_i8_expert_gemm<TT, 4, true, true>(h, W8, ws, act, K, N, n_chunks, top_k);
+}
+template <typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moew_i8_dn(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W8, const int *__restrict__ ws,
+                                                                  typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
+    moe_i8_expert_gemm<TT, 4, false, true>(act, W8, ws, y, K, N, n_chunks, top_k);
+}
+
+template <bool GU>
+static hipError_t moe_i8_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W8, const int *ws, void *out, int K, int N, int top_k) {
+#define GO(TT, RT) return w4_launch<(GU ? k_moe_i8_gate_up_silu<TT, RT> : k_moe_i8_down<TT, RT>), (MoeI8Depth<RT>::value + 1) * 16 * RT * GEMM_KC * 2>( \
+        grid, st, (const typename TT::elem *)A, (const unsigned char *)W8, ws, (typename TT::elem *)out, K, N, K / GEMM_KC, top_k)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
+}
+
+extern "C" {
+
+int samd_moe_gate_up_silu_i8(const void *d_h, const void *d_Wgu8, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
+                             int32_t top_k, void *d_act, int32_t dtype, void *stream) {
+    if (!d_h || !d_Wgu8 || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
+        samd_set_error("samd_moe_gate_up_silu_i8: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
+    }
+    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const hipError_t e = moe_i8_gemm_dispatch<true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu8, (const int *)d_ws, d_act,
+                                                    hidden, 2 * moe_inter, top_k);
+    if (e != hipSuccess) { samd_set_error("samd_moe_gate_up_silu_i8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_moe_down_combine_i8(const void *d_act, const void *d_Wdown8, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                             int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream) {
+    if (!d_act || !d_Wdown8 || !d_topk_idx || !d_topk_w || !d_n || !d_ws || !d_out || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
+        samd_set_error("samd_moe_down_combine_i8: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    void *y = (char *)d_ws + MOE_WS_Y_OFF;
+    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const hipError_t e = moe_i8_gemm_dispatch<false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown8, (const int *)d_ws, y, moe_inter, hidden, top_k);
+    if (e != hipSuccess) { samd_set_error("samd_moe_down_combine_i8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
+    LAUNCHCHK();
+    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
+    if (dtype == SAMD_F16)
+        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
+    else
+        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================
 // Mixture-of-experts MLP with block-scaled FP8 experts (OCP e4m3fn codes, one fp32 scale per 128 x 128 block: the official Qwen3-MoE FP8
 // checkpoints' weight / weight_scale_inv): the gathered expert GEMMs of moe_expert_gemm over k_gemm_skinny_f8's 8-bit weight stream.
 //   NUMERIC CONTRACT (samd_hip/fp8.py): W[n][k] = float(q[n][k]) * s[n / 128][k / 128], s fp32, finite, positive.  W is never formed:
@@ -3410,6 +3654,11 @@ static hipError_t wmoe_gemm_format(int fmt, dim3 grid, hipStream_t st, const voi
         return fmt == 1 ? wmoe_launch<mx>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k)
                         : wmoe_launch<i4>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
     }
+    if (fmt == 5) {
+        constexpr int lds = (MoeI8Depth<4>::value + 1) * tile;
+        if constexpr (GU) return wmoe_launch<k_moew_i8_gu<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
+        else return wmoe_launch<k_moew_i8_dn<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
+    }
     constexpr int lds = (Moe8Depth<4>::value + 1) * tile;
     const float *stab = reinterpret_cast<const float *>(reinterpret_cast<const char *>(W) + moe8_scale_offset(w_rows, (size_t)K));
     if constexpr (GU) return wmoe_launch<k_wmoe8_gu<TT>>(lds, grid, st, (const E *)A, wb, stab, ws, (E *)out, K, N, nc, top_k);
@@ -3426,7 +3675,9 @@ static inline int moew_tile_bound(int rows_pad, int n_experts, int top_k) {
 // the checks shared by the wide calls, in the order the messages promise; sets the error text
 static bool moew_args_ok(const char *fn, bool pointers, int rows, int hidden, int moe_inter, int n_experts, int top_k, int dtype, int fmt) {
     if (rows < 1 || rows > MOEW_MAX_ROWS) { samd_set_error("%s: rows %d outside 1 .. %d", fn, rows, MOEW_MAX_ROWS); return false; }
-    if (fmt < 0 || fmt > 3) { samd_set_error("%s: unknown expert_format %d (0 model dtype, 1 mxfp4, 2 int4g128, 3 fp8b128)", fn, fmt); return false; }
+    if (fmt < 0 || fmt > 5 || fmt == 4) {                        // (4 is left unassigned: callers pin it as an unknown code)
+        samd_set_error("%s: unknown expert_format %d (0 model dtype, 1 mxfp4, 2 int4g128, 3 fp8b128, 5 int8g128)", fn, fmt); return false;
+    }
     if (!moe_shape_ok(MOE_MAX_ROWS, hidden, moe_inter, n_experts, top_k, dtype) || (fmt == 3 && (hidden > 128 * MOE8_MAX_KB || moe_inter > 128 * MOE8_MAX_KB))) {
         samd_set_error("%s: unsupported shape (hidden %% 256 == 0, moe_intermediate %% 256 == 0, both <= 16384 for fp8b128, experts <= 256, top-k <= 8, f16/bf16)", fn);
         return false;

@@ -198,6 +198,8 @@ _PROTOS = {
     "samd_moe_down_combine_f4": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "samd_moe_gate_up_silu_i4": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "samd_moe_down_combine_i4": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
+    "samd_moe_gate_up_silu_i8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
+    "samd_moe_down_combine_i8": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "samd_moe_gate_up_silu_f8": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "samd_moe_down_combine_f8": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "samd_moe_wide_workspace_layout": (_I64, [_I32, _I32, _I32]),

@@ -168,14 +168,17 @@ class LlamaRunner:
         # tell them from MXFP4's "_scale"); INT4 expert tensors make the runner "int4g128" by themselves
         # expert_format "fp8b128": the experts as block-scaled FP8 (float8_e4m3fn codes, or their bytes, + "_sinv" fp32 scales per 128 x 128
         # block: the _sinv keys tell them from the others); such tensors make the runner "fp8b128" by themselves
+        # expert_format "int8g128": the experts as GPTQ INT8 (uint8 codes [E, N, K] + "_z8" zero points + "_s8" scales in the model dtype: the
+        # dense INT8 projections' suffixes, which no other expert format uses); such tensors make the runner "int8g128" by themselves
         sparse_l = [l for l in weights["layers"] if "experts_gu" in l]
+        experts_i8 = [any(k in l for k in ("experts_gu_z8", "experts_gu_s8", "experts_down_z8", "experts_down_s8")) for l in sparse_l]
         experts_i4 = [any(k in l for k in ("experts_gu_z", "experts_gu_s", "experts_down_z", "experts_down_s")) for l in sparse_l]
         experts_f8 = [any(k in l for k in ("experts_gu_sinv", "experts_down_sinv")) or F8.is_fp8_dtype(l["experts_gu"].dtype)
                       or F8.is_fp8_dtype(l["experts_down"].dtype) for l in sparse_l]
-        experts4 = [not i4e and not f8e and (MOE.is_4bit(l["experts_gu"]) or MOE.is_4bit(l["experts_down"]))
-                    for l, i4e, f8e in zip(sparse_l, experts_i4, experts_f8)]
+        experts4 = [not i4e and not f8e and not i8e and (MOE.is_4bit(l["experts_gu"]) or MOE.is_4bit(l["experts_down"]))
+                    for l, i4e, f8e, i8e in zip(sparse_l, experts_i4, experts_f8, experts_i8)]
         self.expert_format = MOE.resolve_expert_format(expert_format, any(experts4), shape.moe, carries_int4=any(experts_i4),
-                                                       carries_fp8=any(experts_f8))                  # (before any device work, as the next)
+                                                       carries_fp8=any(experts_f8), carries_int8=any(experts_i8))   # (before any device work, as the next)
         if shape.moe:
             MOE.reject_unsupported(_weight_format(weight_format, weights, dtype), native_gemm, draft_head)
         if any(experts4):
@@ -194,6 +197,14 @@ class LlamaRunner:
                 if "experts_gu" in l:
                     MOE.check_int4_experts((l["experts_gu"], l.get("experts_gu_z"), l.get("experts_gu_s")),
                                            (l["experts_down"], l.get("experts_down_z"), l.get("experts_down_s")), dtype, f"layer {i} experts")
+        if any(experts_i8):
+            if not all(experts_i8):
+                raise SamdError(f"a mix of INT8 and other sparse layers ({sum(experts_i8)} of {len(experts_i8)} carry INT8 experts): "
+                                "the runner takes the experts of all sparse layers in one format")
+            for i, l in enumerate(weights["layers"]):
+                if "experts_gu" in l:
+                    MOE.check_int8_experts((l["experts_gu"], l.get("experts_gu_z8"), l.get("experts_gu_s8")),
+                                           (l["experts_down"], l.get("experts_down_z8"), l.get("experts_down_s8")), dtype, f"layer {i} experts")
         if any(experts_f8):
             if not all(experts_f8):
                 raise SamdError(f"a mix of block-scaled FP8 and other sparse layers ({sum(experts_f8)} of {len(experts_f8)} carry FP8 experts): "
@@ -462,7 +473,7 @@ class LlamaRunner:
                     and not moe)
             if sparse:
                 # the experts packed once (per expert the 128-column tiles of the streaming GEMM, gate | up interleaved); no row-major copy stays
-                gu_cols = s.hidden // 2 if MOE.is_4bit(l["experts_gu"]) and "experts_gu_sinv" not in l else s.hidden
+                gu_cols = s.hidden // 2 if MOE.is_4bit(l["experts_gu"]) and "experts_gu_sinv" not in l and "experts_gu_z8" not in l else s.hidden
                 if tuple(l["router"].shape) != (s.n_experts, s.hidden) or tuple(l["experts_gu"].shape) != (s.n_experts, 2 * s.moe_inter, gu_cols):
                     raise SamdError(f"sparse layer weights of shapes {tuple(l['router'].shape)}, {tuple(l['experts_gu'].shape)} do not match the shape")
                 if self.expert_format == "mxfp4":
@@ -485,6 +496,18 @@ class LlamaRunner:
                     else:
                         gu3, dn3 = MOE.quantize_experts_int4(l["experts_gu"], l["experts_down"], dtype, f"layer {len(layers)} experts")
                     lp["moe_gu"], lp["moe_down"] = MOE.pack_experts_int4(gu3, dn3, dtype)
+                    for k, t in zip(gkeys + dkeys, gu3 + dn3):
+                        l[k] = torch.empty(t.shape, dtype=t.dtype, device="meta")
+                    del gu3, dn3
+                elif self.expert_format == "int8g128":
+                    # the experts as 8-bit codes + zero points + scales (the checkpoint's own, already checked, or quantised here), packed once
+                    # for this dtype; only shapes stay
+                    gkeys, dkeys = ("experts_gu", "experts_gu_z8", "experts_gu_s8"), ("experts_down", "experts_down_z8", "experts_down_s8")
+                    if "experts_gu_z8" in l:
+                        gu3, dn3 = (tuple(l[k].to(self.device).contiguous() for k in ks) for ks in (gkeys, dkeys))
+                    else:
+                        gu3, dn3 = MOE.quantize_experts_int8(l["experts_gu"], l["experts_down"], dtype, f"layer {len(layers)} experts")
+                    lp["moe_gu"], lp["moe_down"] = MOE.pack_experts_int8(gu3, dn3, dtype)
                     for k, t in zip(gkeys + dkeys, gu3 + dn3):
                         l[k] = torch.empty(t.shape, dtype=t.dtype, device="meta")
                     del gu3, dn3
@@ -712,7 +735,8 @@ class LlamaRunner:
         projections per layer are all 8-bit GPTQ modules (the `...-GPTQ-Int8` releases: bits 8 by config.quantization_config, by the module's
         own `bits`, or by qweight's shape [K/4, N]) is imported as it is through int8.linear_int8 and makes the runner "int8g128" by itself
         (samd_hip/int8.py: group sizes, zero-point conventions and what raises); a mix of 8-bit and 4-bit or plain projections raises, and so
-        does a module with sparse layers that carries 8-bit projections or experts (nothing is dequantised silently).
+        does a module with sparse layers that carries 8-bit modules anywhere but as described under expert_format "int8g128" below (nothing
+        is dequantised silently).
         expert_format (default: env SAMD_EXPERT_FORMAT, unset = the model dtype; models with sparse layers only): "mxfp4" quantises the EXPERTS
         of every sparse layer on load (uncalibrated: for benches and tests); router, attention, dense MLP layers, embedding and lm_head stay in
         the model dtype.  A module whose sparse layers carry 4-bit expert tensors with their block scales (samd_hip/moe.py has the convention)
@@ -736,6 +760,17 @@ class LlamaRunner:
         The module's FP8 attention and dense-MLP projections (block-scaled, or per row / per tensor `weight_scale`) are dequantised ONCE at
         import to rne_dtype(fl32(float(q) * s)) and run on the model-dtype kernels; the router must be a plain `weight`.  Weight-only: the
         checkpoint's dynamic activation quantisation is not reproduced.  FP8 projections beside non-FP8 experts stay rejected.
+        "int8g128" quantises the experts per group of 128 with an 8-bit zero point on load (uncalibrated, for benches and tests).  An 8-bit
+        GPTQ Qwen3-MoE checkpoint (the `Qwen3-30B-A3B-GPTQ-Int8` kind) holds, in every sparse layer, an indexable `mlp.experts` of E modules
+        whose gate_proj / up_proj / down_proj are 8-bit GPTQ modules (qweight / qzeros / scales): each is imported through int8.linear_int8
+        with the config's quantization_config (so act-order, group sizes 32 / 64, AWQ or a stored 255 under "gptq" raise by module name),
+        gate|up are fused per expert, the experts stacked, the scales rounded once for a bf16 runner, and the runner is "int8g128" by itself;
+        any other explicit expert_format against such a module raises.  A sparse layer of which only some experts or projections are 8-bit
+        raises by module name, and so does an 8-bit router.  The checkpoint's 8-bit attention projections and dense-layer MLP projections
+        are NOT streamed as INT8 (weight_format stays rejected for mixture-of-experts models): they are dequantised ONCE at import by
+        int8.dequantize_groups to the model dtype -- one rounding, the weights an INT8 launch would multiply by -- and run on the
+        model-dtype kernels, at 16 bits instead of 8.25 per weight of those projections (Qwen3-30B-A3B: 48 layers x 37.7 M attention
+        weights = 3.6 GB instead of 1.9 GB; the experts, 97 % of the model, stay 8-bit).
         share_weights does not apply to
         dequantised projections (there is no HF `weight` to re-point); INT4 attention beside model-dtype or MXFP4 experts stays rejected."""
         weight_format = _env_weight_format(weight_format)
@@ -746,12 +781,27 @@ class LlamaRunner:
                    if hasattr(getattr(lyr, a), b)]               # (a sparse layer's MLP has no gate / up / down projections of its own)
         qcfg = I4.quant_config(getattr(lm, "config", None))
         # 8-bit GPTQ modules are decided first: they carry qweight / qzeros / scales too, so the INT4 test below is true for them
-        if any(cls._hf_sparse_layers(m.layers)):
-            for i, lyr in enumerate(m.layers):
+        # In a module with sparse layers they are taken when EVERY sparse layer's experts are 8-bit GPTQ modules throughout (expert_format
+        # "int8g128"); then the attention and dense-MLP projections may be 8-bit too (dequantised once at import, the docstring).  Anywhere
+        # else in such a module -- some experts or projections of a layer only, a router, 8-bit projections beside other experts -- an 8-bit
+        # module raises by name
+        sparse0 = cls._hf_sparse_layers(m.layers)
+        full8 = [sp and cls._hf_experts_are_int8(lyr, qcfg) for lyr, sp in zip(m.layers, sparse0)]
+        moe_i8 = any(sparse0) and full8 == sparse0
+        if any(sparse0):
+            served = {f"{a}.{b}" for a, b in parts} if moe_i8 else set()
+            for i in sorted(range(len(m.layers)), key=lambda i: full8[i]):       # (a layer whose experts are 8-bit only in part is named first)
+                lyr = m.layers[i]
                 for n, mod in lyr.named_modules():
-                    if n and I8.is_int8_module(mod, qcfg):
-                        raise SamdError(f"layers.{i}.{n}: an 8-bit GPTQ module in a mixture-of-experts model: 8-bit projections and experts are "
-                                        "not supported there (weight_format 'int8g128' covers dense models only, and nothing is dequantised silently)")
+                    if n and I8.is_int8_module(mod, qcfg) and n not in served and not (moe_i8 and sparse0[i] and n.startswith("mlp.experts.")):
+                        if moe_i8 and n == "mlp.gate":
+                            raise SamdError(f"layers.{i}.{n}: an 8-bit router is not supported: the router stays a plain `weight` in the model dtype")
+                        if moe_i8:
+                            raise SamdError(f"layers.{i}.{n}: an 8-bit GPTQ module in a mixture-of-experts model with INT8 experts: only the "
+                                            "experts, the attention projections and a dense layer's MLP projections may be 8-bit")
+                        raise SamdError(f"layers.{i}.{n}: an 8-bit GPTQ module in a mixture-of-experts model whose sparse layers' experts are not "
+                                        "all 8-bit GPTQ modules throughout: 8-bit modules are taken there only beside such experts (expert_format "
+                                        "'int8g128'); weight_format 'int8g128' covers dense models only, and nothing is dequantised silently")
         ckpt_i8 = I8.checkpoint_is_int8(linears, qcfg)           # all seven projections of every layer, or a SamdError for a mix
         ckpt_i4 = (not ckpt_i8) and I4.checkpoint_is_int4(linears)   # AWQ / GPTQ modules (qweight / qzeros / scales, no `weight`)
         # a module with block-scaled FP8 EXPERTS (the official Qwen3-MoE FP8 checkpoints) is not a weight_format "fp8" one: its FP8 attention
@@ -783,22 +833,28 @@ class LlamaRunner:
         # a module with INT4 EXPERTS whose attention / dense-MLP projections are INT4 too (an AWQ / GPTQ mixture-of-experts checkpoint):
         # these are dequantised once at import (the docstring), so the runner is not a weight_format "int4g128" one.  INT4 projections
         # beside model-dtype or MXFP4 experts stay rejected as before
-        experts_i4 = [cls._hf_experts_are_int4(lyr, i) for i, lyr in enumerate(m.layers) if sparse[i]]
+        experts_i4 = [not moe_i8 and cls._hf_experts_are_int4(lyr, i) for i, lyr in enumerate(m.layers) if sparse[i]]
         moe_i4_dense = ckpt_i4 and any(experts_i4)
         if moe_i4_dense:
             ckpt_i4 = False
+        # the same for a module with INT8 EXPERTS whose attention / dense-MLP projections are 8-bit too (a GPTQ-Int8 mixture-of-experts
+        # checkpoint): dequantised once at import, the runner is not a weight_format "int8g128" one
+        moe_i8_dense = ckpt_i8 and moe_i8
+        if moe_i8_dense:
+            ckpt_i8 = False
         if any(sparse) or shape.moe:
             if sparse != list(shape.sparse):
                 raise SamdError(f"the module's sparse MLP layers {[i for i, x in enumerate(sparse) if x]} are not the ones its config implies "
                                 f"{[i for i, x in enumerate(shape.sparse) if x]} (model_type '{shape.model_type}')")
-            MOE.reject_unsupported("int4g128" if ckpt_i4 else "fp8" if ckpt_f8 else "fp8b128" if ckpt_f8b else ("mxfp4" if ckpt_f4 else weight_format), kw.get("native_gemm", True),
+            MOE.reject_unsupported("int8g128" if ckpt_i8 else "int4g128" if ckpt_i4 else "fp8" if ckpt_f8 else "fp8b128" if ckpt_f8b else ("mxfp4" if ckpt_f4 else weight_format), kw.get("native_gemm", True),
                                    kw.get("draft_head", False))
         # 4-bit experts: decided and checked on the module's own tensors, before anything moves to the device (the runner resolves the
         # format again from the weights it is given)
-        experts4 = [not i4e and not layer_f8[i] and cls._hf_experts_are_4bit(lyr, i)
+        experts4 = [not i4e and not moe_i8 and not layer_f8[i] and cls._hf_experts_are_4bit(lyr, i)
                     for (i, lyr), i4e in zip(((i, lyr) for i, lyr in enumerate(m.layers) if sparse[i]), experts_i4)]
         experts_f8 = [layer_f8[i] for i in range(len(m.layers)) if sparse[i]]
-        MOE.resolve_expert_format(expert_format, any(experts4), any(sparse) or shape.moe, carries_int4=any(experts_i4), carries_fp8=any(experts_f8))
+        MOE.resolve_expert_format(expert_format, any(experts4), any(sparse) or shape.moe, carries_int4=any(experts_i4), carries_fp8=any(experts_f8),
+                                  carries_int8=moe_i8)
         if any(experts_f8):
             if not all(experts_f8):
                 plain = [i for i, sp in enumerate(sparse) if sp and not layer_f8[i]][:3]
@@ -819,7 +875,7 @@ class LlamaRunner:
             raise SamdError(f"a mix of INT4 and other sparse layers ({sum(experts_i4)} of {len(experts_i4)} carry INT4 experts; e.g. layers "
                             f"{plain} do not): the runner takes the experts of all sparse layers in one format")
         for i, lyr in enumerate(m.layers):
-            if sparse[i] and any(experts_i4) and len(lyr.mlp.experts) != shape.n_experts:
+            if sparse[i] and (any(experts_i4) or moe_i8) and len(lyr.mlp.experts) != shape.n_experts:
                 raise SamdError(f"layers.{i}.mlp.experts: {len(lyr.mlp.experts)} expert modules, the config says num_experts = {shape.n_experts}")
             if sparse[i] and I4.is_int4_module(getattr(lyr.mlp, "gate", None)):
                 raise SamdError(f"layers.{i}.mlp.gate: an INT4 router is not supported: the router stays a plain `weight` in the model dtype")
@@ -852,11 +908,14 @@ class LlamaRunner:
                 return F8.linear_fp8_dequantized(mod, name, qcfg8).to(dtype)
             if not I4.is_int4_module(mod):
                 return mod.weight
+            if I8.is_int8_module(mod, qcfg):                     # beside INT8 experts: rne_dtype((q - z) * s) again, through int8.py
+                q, z, sc = I8.linear_int8(mod, name, config=qcfg)
+                return I8.dequantize_groups(q, z, I8.as_scales(sc, dtype, name)).to(dtype)
             q, z, sc = I4.linear_int4(mod, name, config=qcfg)
             return I4.dequantize_groups(q, z, I4.as_scales(sc, dtype, name)).to(dtype)
 
         def fuse(linears, names=None):
-            if moe_i4_dense or (moe_f8_dense and any(F8.is_fp8_dtype(l.weight.dtype) for l in linears)):
+            if moe_i4_dense or moe_i8_dense or (moe_f8_dense and any(F8.is_fp8_dtype(l.weight.dtype) for l in linears)):
                 return get(torch.cat([lin_w(l, n).to(dtype) for l, n in zip(linears, names)], dim=0))
             ws = [l.weight for l in linears]
             cat = get(torch.cat(ws, dim=0))
@@ -925,6 +984,12 @@ class LlamaRunner:
                     **MOE.import_experts_int4(f.experts, f"layers.{li}.mlp.experts", dtype, dev, qcfg),
                     ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
                 continue
+            if sparse[li] and moe_i8:                            # router + the experts' canonical 8-bit (q, z, s), fused and stacked
+                layers.append(dict(
+                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
+                    **MOE.import_experts_int8(f.experts, f"layers.{li}.mlp.experts", dtype, dev, qcfg),
+                    ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
+                continue
             if sparse[len(layers)] and any(experts4):            # router + the 4-bit expert tensors and their block scales, as they are
                 ex, raw = f.experts, lambda t: MX._bytes(t.detach()).to(dev).contiguous()
                 layers.append(dict(
@@ -984,6 +1049,15 @@ class LlamaRunner:
             raise SamdError(f"layers.{i}.mlp.experts: a mix of FP8 and other expert tensors ({n8} of {len(kinds)} are FP8; e.g. "
                             f"{', '.join(plain)} are not): FP8 experts need every expert tensor float8_e4m3fn")
         return n8 > 0
+
+    @classmethod
+    def _hf_experts_are_int8(cls, lyr, config=None):
+        """does the layer hold per-expert 8-bit GPTQ modules -- an indexable `mlp.experts` of modules whose gate_proj, up_proj and down_proj
+        are ALL 8-bit (int8.is_int8_module)?  Anything less is False: from_hf then refuses whatever 8-bit module it finds, by name"""
+        ex = getattr(getattr(lyr, "mlp", None), "experts", None)
+        if ex is None or hasattr(ex, "gate_up_proj") or not hasattr(ex, "__len__") or not hasattr(ex, "__getitem__") or len(ex) == 0:
+            return False
+        return all(I8.is_int8_module(getattr(ex[e], p, None), config) for e in range(len(ex)) for p in MOE.INT4_EXPERT_PROJECTIONS)
 
     @classmethod
     def _hf_experts_are_int4(cls, lyr, i):
@@ -1131,7 +1205,7 @@ class LlamaRunner:
         128 x 128 block; an MXFP4 projection: half a byte per weight + one scale byte per 32; an
         INT4 projection: half a byte per weight + 4 bytes of scale and zero point per 128; an INT8 projection: one byte per weight + the same 4 bytes per 128).
         A sparse (mixture-of-experts) layer counts `experts` of its experts in the format they are held in (MXFP4 experts: elements + block
-        scales; block-scaled FP8 experts: one byte per weight + one fp32 scale per 128 x 128 block -- the packed table repeats each scale for
+        scales; INT8 experts: the packed 33 / 32 bytes per weight; block-scaled FP8 experts: one byte per weight + one fp32 scale per 128 x 128 block -- the packed table repeats each scale for
         the two 64-row halves of its block, another 4 bytes per 16384 weights;
         default: num_experts_per_tok, what the 1-row step streams; a wider step streams the experts its rows are routed to, at most
         all of them: pass experts=shape.n_experts for that bound)."""
@@ -1145,6 +1219,8 @@ class LlamaRunner:
             return n
         for l in self.w["layers"]:
             n += sum(nb(t) for t in l.values())
+        if self.expert_format == "int8g128":                     # the packed bytes, N K 33 / 32: a zero point is a 16-bit word there
+            n += sum(nb(l[k]) for l in self.w["layers"] for k in ("experts_gu_z8", "experts_down_z8") if k in l)
         if self.weight_format == "fp8":
             n += sum(nb(l[k + "_f8"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
         if self.weight_format == "fp8b128":                      # one byte per weight (counted above) + 4 bytes per 128 x 128 block

@@ -32,10 +32,20 @@ experts_down_sinv -- the _sinv keys are what tells this format from the others. 
 E * N rows; then the fp32 scale table [E * N / 64][K / 128]) and streamed by samd_moe_gate_up_silu_f8 / samd_moe_down_combine_f8.  The
 buffer does not depend on the model dtype.
 
+expert_format "int8g128" keeps the EXPERTS as GPTQ INT8 (samd_hip/int8.py: 8-bit codes, one per byte, one 8-bit zero point and one scale in
+the model dtype per 128 along k, W = rne_dtype((q - z) * s)): (q [E, N, K], z [E, N, K/128], s [E, N, K/128]) per fused tensor, packed by
+samd_gemm_pack_i8 as one matrix of E * N rows (E * N * K * 33 / 32 bytes; the buffer is dtype-specific) and streamed by
+samd_moe_gate_up_silu_i8 / samd_moe_down_combine_i8.  An 8-bit GPTQ Qwen3-MoE checkpoint holds an indexable `mlp.experts` of E modules with
+8-bit GPTQ gate_proj / up_proj / down_proj, which LlamaRunner.from_hf imports through int8.linear_int8; in a raw weights dict: experts_gu
+uint8 [E, 2 I, H], experts_gu_z8 uint8 [E, 2 I, H/128], experts_gu_s8 model dtype [E, 2 I, H/128], and experts_down / _z8 / _s8 likewise
+with [E, H, I...] -- the _z8 / _s8 keys (the dense INT8 projections' suffixes) are what tells INT8 from INT4 (_z / _s), MXFP4 (_scale) and
+FP8 (_sinv).  The pinned tuples above stay as they are; EXPERT_FORMATS_SERVED is EXPERT_FORMATS_KNOWN plus "int8g128" and is what an
+expert_format is validated against (WIDE_FORMAT_CODES_SERVED likewise for the wide calls' codes).
+
 MoeBuffers serves one row bucket of at most 64 rows (decode, verify, the chunked prefill).  MoeWideBuffers serves 1 .. 4096 rows in one
 route, one lists, one gate|up and one down + combine (include/samd_hip.h: samd_moe_wide_*): an expert's list may be longer than a 64-row
 tile and is served in several through a tile table, every row with the bits MoeBuffers gives it, over the same packed expert buffers in
-all four formats.  LlamaRunner._prefill_moe runs a prompt of 128 tokens or more through it, SAMD_MOE_PREFILL_ROWS (prefill_rows) rows at a
+every format.  LlamaRunner._prefill_moe runs a prompt of 128 tokens or more through it, SAMD_MOE_PREFILL_ROWS (prefill_rows) rows at a
 time; wide_lists_reference restates the lists and the tile table in plain Python."""
 import os
 
@@ -44,6 +54,7 @@ import torch
 from . import SamdError, _ptr, check, current_stream, lib, torch_dtype_code
 from . import fp8 as F8
 from . import int4 as I4
+from . import int8 as I8
 from . import mxfp4 as MX
 
 MAX_EXPERTS = 256
@@ -57,6 +68,8 @@ EXPERT_SCALE_PARAMS = ("mlp.experts.gate_up_proj_scale", "mlp.experts.down_proj_
 EXPERT_FORMATS = (None, "mxfp4")
 EXPERT_FORMATS_ALL = EXPERT_FORMATS + ("int4g128",)
 EXPERT_FORMATS_KNOWN = EXPERT_FORMATS_ALL + ("fp8b128",)
+# the three tuples above are pinned by their callers; this one is what an expert_format is validated against
+EXPERT_FORMATS_SERVED = EXPERT_FORMATS_KNOWN + ("int8g128",)
 # the scale tensors of transformers' FP8Experts: consumed only beside float8_e4m3fn expert tensors
 FP8_EXPERT_SCALE_PARAMS = ("mlp.experts.gate_up_proj_scale_inv", "mlp.experts.down_proj_scale_inv")
 # the projections of one expert module of an INT4 (AWQ / GPTQ) checkpoint: mlp.experts.{e}.gate_proj / up_proj / down_proj
@@ -103,21 +116,32 @@ def reject_unsupported(weight_format=None, native_gemm=True, draft_head=False):
 
 def _format_error(expert_format):
     hint = " ('fp8' is weight_format's spelling of per-row FP8; block-scaled FP8 experts are 'fp8b128')" if expert_format == "fp8" else ""
-    return SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS_KNOWN)}{hint}")
+    return SamdError(f"expert_format {expert_format!r}: expected one of {', '.join(repr(f) for f in EXPERT_FORMATS_SERVED)}{hint}")
 
 
-def resolve_expert_format(expert_format, carries_4bit, has_sparse, carries_int4=False, carries_fp8=False):
-    """None, "mxfp4", "int4g128" or "fp8b128" from the argument (AUTO: env SAMD_EXPERT_FORMAT, for callers that cannot pass one) and from
-    what the weights carry: MXFP4 expert tensors (carries_4bit) make the runner "mxfp4" by themselves, INT4 ones (carries_int4) "int4g128",
-    block-scaled FP8 ones (carries_fp8) "fp8b128"; any other explicit format against them raises.  Raises before any device work."""
+def resolve_expert_format(expert_format, carries_4bit, has_sparse, carries_int4=False, carries_fp8=False, carries_int8=False):
+    """None, "mxfp4", "int4g128", "fp8b128" or "int8g128" from the argument (AUTO: env SAMD_EXPERT_FORMAT, for callers that cannot pass one)
+    and from what the weights carry: MXFP4 expert tensors (carries_4bit) make the runner "mxfp4" by themselves, INT4 ones (carries_int4)
+    "int4g128", block-scaled FP8 ones (carries_fp8) "fp8b128", 8-bit GPTQ ones (carries_int8) "int8g128"; any other explicit format against
+    them raises.  Raises before any device work."""
     explicit = expert_format is not AUTO
     if not explicit:
         expert_format = os.environ.get("SAMD_EXPERT_FORMAT") or None
-    if expert_format not in EXPERT_FORMATS_KNOWN:
+    if expert_format not in EXPERT_FORMATS_SERVED:
         raise _format_error(expert_format)
     if expert_format is not None and not has_sparse:
         raise SamdError(f"expert_format '{expert_format}' on a model without mixture-of-experts (sparse) layers: it covers the experts only; "
                         "weight_format covers the dense projections")
+    if carries_int8:
+        if carries_4bit or carries_int4 or carries_fp8:
+            raise SamdError("a mix of INT8 and other quantised expert tensors: the runner takes the experts of all sparse layers in one format")
+        if explicit and expert_format != "int8g128":
+            raise SamdError(f"the sparse layers carry INT8 (GPTQ) expert tensors; expert_format={expert_format!r} would need them "
+                            "dequantised or re-quantised (leave it out or pass 'int8g128')")
+        return "int8g128"
+    if explicit and expert_format == "int8g128" and (carries_4bit or carries_int4 or carries_fp8):
+        raise SamdError("the sparse layers carry quantised expert tensors of another format; expert_format='int8g128' would need them "
+                        "re-quantised (leave it out)")
     if carries_4bit and carries_int4:
         raise SamdError("a mix of MXFP4 and INT4 expert tensors: the runner takes the experts of all sparse layers in one format")
     if carries_fp8 and (carries_4bit or carries_int4):
@@ -317,6 +341,105 @@ def import_experts_int4(experts, name, dtype, device, config=None):
     return out
 
 
+def quantize_experts_int8(gate_up, down, dtype, name="experts"):
+    """((q, z, s) of gate|up, (q, z, s) of down) of HF's fused expert tensors [E, 2 I, H] / [E, H, I]: int8.quantize_groups on every expert
+    (asymmetric min / max per group of 128 along K, round to nearest, no calibration: for benches and tests).  q uint8 [E, N, K], z uint8
+    [E, N, K/128], s `dtype` [E, N, K/128]."""
+    E, N2, H = gate_up.shape
+    if tuple(down.shape) != (E, H, N2 // 2):
+        raise SamdError(f"{name}: expert tensors of shapes {tuple(gate_up.shape)} and {tuple(down.shape)} do not belong together")
+    out = []
+    for t in (gate_up, down):
+        _, N, K = t.shape
+        if K % I8.GROUP != 0:
+            raise SamdError(f"{name}: INT8 needs K % 128 == 0, got [{E}, {N}, {K}] experts")
+        q = torch.empty((E, N, K), dtype=torch.uint8, device=t.device)
+        z = torch.empty((E, N, K // I8.GROUP), dtype=torch.uint8, device=t.device)
+        s = torch.empty((E, N, K // I8.GROUP), dtype=dtype, device=t.device)
+        for e in range(E):                                       # (expert by expert: the fp32 temporaries stay small)
+            q[e], z[e], s[e] = I8.quantize_groups(t[e], dtype)
+        out.append((q, z, s))
+    return tuple(out)
+
+
+def dequantize_experts_int8(q, z, s, dtype=None):
+    """rne_{s.dtype}((q - z) * s), [E, N, K] in fp32 (or `dtype`): the weights the INT8 expert kernels of a runner in s.dtype multiply by"""
+    E, N, K = q.shape
+    w = I8.dequantize_groups(q.reshape(E * N, K), z.reshape(E * N, -1), s.reshape(E * N, -1)).reshape(E, N, K)
+    return w if dtype is None else w.to(dtype)
+
+
+def check_int8_experts(gu, down, dtype, name="experts"):
+    """the shapes, dtypes and scales of INT8 expert tensors (gu, down: (q, z, s) each) for a runner in `dtype`; raises SamdError by tensor
+    name.  Plain torch, any device."""
+    for what, (q, z, s) in ((f"{name}.gate_up_proj", gu), (f"{name}.down_proj", down)):
+        if z is None or s is None:
+            raise SamdError(f"{what}: INT8 expert tensor without its zero points and scales")
+        if q.dtype != torch.uint8 or z.dtype != torch.uint8 or q.dim() != 3:
+            raise SamdError(f"{what}: INT8 codes and zero points are uint8 tensors (q [E, N, K], z [E, N, K/128]), got {q.dtype} "
+                            f"{tuple(q.shape)} and {z.dtype} {tuple(z.shape)}")
+        E, N, K = q.shape
+        if N % 128 != 0 or K % 256 != 0:
+            raise SamdError(f"{what} of shape ({E}, {N}, {K}): the INT8 expert kernels need N % 128 == 0 and K % 256 == 0")
+        want = (E, N, K // I8.GROUP)
+        if tuple(z.shape) != want or tuple(s.shape) != want:
+            raise SamdError(f"{what}: zero points {tuple(z.shape)} / scales {tuple(s.shape)} for [{E}, {N}, {K}] experts; one per 128 "
+                            f"along K is {want}")
+        if s.dtype != dtype:
+            raise SamdError(f"{what}: scales of dtype {s.dtype} for a {dtype} runner (int8.as_scales rounds a checkpoint's fp16 scales once)")
+        I8.check_scales(s, dtype, what)
+    E, N2, H = gu[0].shape
+    if tuple(down[0].shape) != (E, H, N2 // 2):
+        raise SamdError(f"{name}: INT8 expert tensors of shapes {tuple(gu[0].shape)} and {tuple(down[0].shape)} do not belong together "
+                        f"(gate_up_proj [E, 2 I, H], down_proj [E, H, I])")
+
+
+def pack_experts_int8(gu, down, dtype):
+    """(packed gate|up, packed down) of (q, z, s) triples: uint8 buffers of E * int8.packed_bytes(N, K) = E * N * K * 33 / 32 bytes each in
+    samd_gemm_pack_i8's layout, the experts end to end as one matrix of E * N rows (tile e * N / 128 + t is expert e's tile t).  The gate|up
+    rows are permuted first (gate_up_tile_order; groups run along k, so whole rows move with their zero points and scales).  The buffers
+    are specific to `dtype` (scales and pre-biased zero points are stored in it).  Tensors already on the GPU.  The two returned tensors
+    carry the mark MoeBuffers.experts(..., expert_format="int8g128") asks for; pass them on as they are."""
+    check_int8_experts(gu, down, dtype)
+    E, N2, H = gu[0].shape
+    I = N2 // 2
+    order = gate_up_tile_order(I, gu[0].device)
+    dt_code = torch_dtype_code(dtype)
+    out = []
+    for (q, z, s), N, K in ((tuple(t[:, order] for t in gu), N2, H), (down, H, I)):
+        q, z, s = q.contiguous(), z.contiguous(), s.contiguous()
+        buf = torch.empty(E * I8.packed_bytes(N, K), dtype=torch.uint8, device=q.device)
+        check(lib().samd_gemm_pack_i8(_ptr(q), _ptr(z), _ptr(s), _ptr(buf), E * N, K, dt_code, current_stream()))
+        # the byte count does not name the dtype the buffer was packed for, nor tells a packed buffer from raw bytes of that length: the
+        # launches take only tensors that carry this mark.  A copy, a view or a slice does not carry it and is refused -- the guard fails
+        # closed; hand over the tensors this function returned
+        buf.expert_format = "int8g128"
+        out.append(buf)
+    return tuple(out)
+
+
+def import_experts_int8(experts, name, dtype, device, config=None):
+    """the raw-weights-dict entries (experts_gu / _z8 / _s8, experts_down / _z8 / _s8) of an indexable of E expert modules whose gate_proj /
+    up_proj / down_proj are 8-bit GPTQ modules: each imported by int8.linear_int8 (`config`: the model's quantization_config; its rejections
+    reach the caller by module name), gate|up fused per expert, the experts stacked on `device`, the scales rounded once to `dtype`."""
+    gu, dn = [], []
+    for e in range(len(experts)):
+        parts = []
+        for p in INT4_EXPERT_PROJECTIONS:
+            r = I8.linear_int8(getattr(experts[e], p, None), f"{name}.{e}.{p}", config=config)
+            if r is None:
+                raise SamdError(f"{name}.{e}.{p}: not an 8-bit GPTQ module beside 8-bit experts: the experts of a layer come in one format")
+            parts.append(r)
+        g, u, d = parts
+        gu.append(I8.fuse_int8([g, u], device, dtype))
+        dn.append(I8.fuse_int8([d], device, dtype))
+    out = {}
+    for key, parts in (("experts_gu", gu), ("experts_down", dn)):
+        for sfx, j in (("", 0), ("_z8", 1), ("_s8", 2)):
+            out[key + sfx] = torch.stack([p[j] for p in parts]).contiguous()
+    return out
+
+
 def _f8_view(t):
     return t.view(torch.float8_e4m3fn) if t.dtype == torch.uint8 else t
 
@@ -477,10 +600,21 @@ class MoeBuffers:
 
     def experts(self, h, wgu_packed, wdown_packed, d_n, expert_format=None):
         """the two expert launches over buffers of pack_experts (expert_format None), pack_experts_mxfp4 ("mxfp4"), pack_experts_int4
-        ("int4g128"; packed for this runner's dtype) or pack_experts_fp8 ("fp8b128")"""
-        L, st = lib(), current_stream()
-        if expert_format not in EXPERT_FORMATS_KNOWN:
+        ("int4g128"; packed for this runner's dtype), pack_experts_fp8 ("fp8b128") or pack_experts_int8 ("int8g128"; packed for this
+        runner's dtype)"""
+        if expert_format not in EXPERT_FORMATS_SERVED:
             raise _format_error(expert_format)
+        if expert_format != "int8g128" and "int8g128" in (getattr(wgu_packed, "expert_format", None), getattr(wdown_packed, "expert_format", None)):
+            raise SamdError(f"an INT8 expert buffer (pack_experts_int8) under expert_format {expert_format!r}: pass expert_format='int8g128'")
+        if expert_format == "int8g128":                          # (the guards come before any device work)
+            _check_expert_buffers(self, wgu_packed, wdown_packed, expert_format)
+        L, st = lib(), current_stream()
+        if expert_format == "int8g128":
+            check(L.samd_moe_gate_up_silu_i8(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts,
+                                             self.top_k, _ptr(self.act), self.dt, st))
+            check(L.samd_moe_down_combine_i8(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws),
+                                             self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k, _ptr(self.out), self.dt, st))
+            return self.out
         if expert_format == "fp8b128":
             # the byte count tells this buffer from every other one of the shape (gate|up and down differ too: swapped buffers raise)
             for what, t, want in (("gate|up", wgu_packed, self.n_experts * F8.packed_block_bytes(2 * self.moe_inter, self.hidden)),
@@ -539,6 +673,9 @@ WIDE_TILE = 64
 PREFILL_ROWS_ENV = "SAMD_MOE_PREFILL_ROWS"
 # the C ABI's expert_format codes
 WIDE_FORMAT_CODES = {None: 0, "mxfp4": 1, "int4g128": 2, "fp8b128": 3}
+# (pinned, as EXPERT_FORMATS_KNOWN is; the calls take the codes of this one.  "int8g128" is 5: callers also pin 4 as a code the library
+# refuses as unknown, so 4 stays unassigned)
+WIDE_FORMAT_CODES_SERVED = dict(WIDE_FORMAT_CODES, int8g128=5)
 
 
 def prefill_rows(value=None):
@@ -622,10 +759,10 @@ class MoeWideBuffers:
 
     def experts(self, h, wgu_packed, wdown_packed, d_n, expert_format=None, rows=None):
         """the two expert launches over the buffers MoeBuffers.experts takes for `expert_format`; returns out [RP, hidden]"""
-        if expert_format not in EXPERT_FORMATS_KNOWN:
+        if expert_format not in EXPERT_FORMATS_SERVED:
             raise _format_error(expert_format)
         _check_expert_buffers(self, wgu_packed, wdown_packed, expert_format)
-        L, st, code, rows = lib(), current_stream(), WIDE_FORMAT_CODES[expert_format], self._rows(rows)
+        L, st, code, rows = lib(), current_stream(), WIDE_FORMAT_CODES_SERVED[expert_format], self._rows(rows)
         check(L.samd_moe_wide_gate_up_silu(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), rows, self.hidden, self.moe_inter, self.n_experts, self.top_k,
                                            code, _ptr(self.act), self.dt, st))
         check(L.samd_moe_wide_down_combine(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws), rows,
@@ -649,15 +786,20 @@ class MoeWideBuffers:
 
 
 def _check_expert_buffers(b, wgu_packed, wdown_packed, expert_format):
-    """the byte counts and marks MoeBuffers.experts asks of packed expert buffers, for the wide calls"""
+    """the byte counts and marks MoeBuffers.experts asks of packed expert buffers, for the wide calls (and its own INT8 launch)"""
+    if expert_format != "int8g128" and "int8g128" in (getattr(wgu_packed, "expert_format", None), getattr(wdown_packed, "expert_format", None)):
+        raise SamdError(f"an INT8 expert buffer (pack_experts_int8) under expert_format {expert_format!r}: pass expert_format='int8g128'")
     if expert_format is None:
         if wgu_packed.dtype == torch.uint8 or wdown_packed.dtype == torch.uint8:
             raise SamdError("uint8 expert buffers are MXFP4 ones: pass expert_format='mxfp4'")
         return
-    nbytes = {"fp8b128": F8.packed_block_bytes, "int4g128": I4.packed_bytes, "mxfp4": MX.packed_bytes}[expert_format]
+    nbytes = {"fp8b128": F8.packed_block_bytes, "int4g128": I4.packed_bytes, "mxfp4": MX.packed_bytes, "int8g128": I8.packed_bytes}[expert_format]
     for what, t, want in (("gate|up", wgu_packed, b.n_experts * nbytes(2 * b.moe_inter, b.hidden)), ("down", wdown_packed, b.n_experts * nbytes(b.hidden, b.moe_inter))):
         if t.dtype != torch.uint8 or t.numel() != want:
             raise SamdError(f"{expert_format} {what} expert buffer of {t.numel()} {t.dtype} elements; the packer gives {want} bytes for this shape")
         if expert_format == "int4g128" and getattr(t, "expert_format", None) != "int4g128":
             raise SamdError("expert_format 'int4g128' over a buffer that pack_experts_int4 did not return (an MXFP4 buffer of this shape "
                             "has the same byte count and other contents; a copy or a view of an INT4 buffer loses the packer's mark)")
+        if expert_format == "int8g128" and getattr(t, "expert_format", None) != "int8g128":
+            raise SamdError("expert_format 'int8g128' over a buffer that pack_experts_int8 did not return (the byte count alone does not "
+                            "tell a packed INT8 buffer from other bytes; a copy or a view of an INT8 buffer loses the packer's mark)")

@@ -16,10 +16,12 @@ random-init weights, per row bucket 1 / 8 / 16 / 64.
            same alternation: model dtype and MXFP4, both untouched by the INT4 kernels, are its yardsticks in the same run.  --dtype picks
            the model dtype (bf16 or fp16) of this step.  --expert-format fp8b128 does the same for the block-scaled FP8 expert launches
            (e4m3fn codes, one fp32 scale per 128 x 128 block): model dtype and MXFP4 are the yardsticks, never the new code against itself.
+           --expert-format int8g128 times the INT8 (GPTQ) expert launches beside the model-dtype and the block-scaled FP8 ones (the other
+           8-bit format), in the same alternation.
 
 Without --step every step runs as a child process of its own under its own time limit, and nothing more is started after a step that failed.
 --buckets 1 keeps a profiler's per-kernel statistics to one bucket: rocprofv3 --kernel-trace --stats -- python scripts/moe_step_bench.py --step experts --buckets 1
-usage: python scripts/moe_step_bench.py [--step experts|step] [--reps 30] [--layers 4] [--depth 12] [--buckets 1,8,16,64] [--expert-format none|mxfp4|int4g128|fp8b128] [--dtype bf16|fp16]"""
+usage: python scripts/moe_step_bench.py [--step experts|step] [--reps 30] [--layers 4] [--depth 12] [--buckets 1,8,16,64] [--expert-format none|mxfp4|int4g128|fp8b128|int8g128] [--dtype bf16|fp16]"""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "sam-decoding_amd")]
@@ -114,13 +116,18 @@ def step_formats(a):
     H, I, E, k = A3B["hidden_size"], A3B["moe_intermediate_size"], A3B["num_experts"], A3B["num_experts_per_tok"]
     dt, BF = (torch.float16, samd_hip.F16) if a.dtype == "fp16" else (torch.bfloat16, samd_hip.BF16)
     L = lib()
-    fmts = ("model", "mxfp4") + ((a.expert_format,) if a.expert_format in ("int4g128", "fp8b128") else ())
+    fmts = ("model", "fp8b128", "int8g128") if a.expert_format == "int8g128" else \
+        ("model", "mxfp4") + ((a.expert_format,) if a.expert_format in ("int4g128", "fp8b128") else ())
     g = torch.Generator(device="cuda").manual_seed(0)
     rnd = lambda *s: (torch.randn(s, generator=g, device="cuda") * 0.02).to(dt)
     sets = []
     for _ in range(a.layers):
         router, gu, dn = rnd(E, H) * 50, rnd(E, 2 * I, H), rnd(E, H, I)
-        packed = {"model": MOE.pack_experts(gu, dn), "mxfp4": MOE.pack_experts_mxfp4(*MOE.quantize_experts(gu, dn, dt))}
+        packed = {"model": MOE.pack_experts(gu, dn)}
+        if "mxfp4" in fmts:
+            packed["mxfp4"] = MOE.pack_experts_mxfp4(*MOE.quantize_experts(gu, dn, dt))
+        if "int8g128" in fmts:
+            packed["int8g128"] = MOE.pack_experts_int8(*MOE.quantize_experts_int8(gu, dn, dt), dt)
         if "int4g128" in fmts:
             packed["int4g128"] = MOE.pack_experts_int4(*MOE.quantize_experts_int4(gu, dn, dt), dt)
         if "fp8b128" in fmts:
@@ -128,11 +135,12 @@ def step_formats(a):
         sets.append((router, packed))
         del gu, dn
     per_expert = {"model": 3 * H * I * 2, "mxfp4": 3 * H * I // 2 + 3 * H * I // 32, "int4g128": 3 * H * I // 2 + 3 * H * I // 32,
-                  "fp8b128": 3 * H * I + 3 * (H // 64) * (I // 128) * 4}     # codes + the packed table: one fp32 per (64 rows, 128 k)
+                  "fp8b128": 3 * H * I + 3 * (H // 64) * (I // 128) * 4,     # codes + the packed table: one fp32 per (64 rows, 128 k)
+                  "int8g128": 3 * H * I + 3 * H * I // 32}
     gate_up_fn = {"model": L.samd_moe_gate_up_silu, "mxfp4": L.samd_moe_gate_up_silu_f4, "int4g128": L.samd_moe_gate_up_silu_i4,
-                  "fp8b128": L.samd_moe_gate_up_silu_f8}
+                  "fp8b128": L.samd_moe_gate_up_silu_f8, "int8g128": L.samd_moe_gate_up_silu_i8}
     down_fn = {"model": L.samd_moe_down_combine, "mxfp4": L.samd_moe_down_combine_f4, "int4g128": L.samd_moe_down_combine_i4,
-               "fp8b128": L.samd_moe_down_combine_f8}
+               "fp8b128": L.samd_moe_down_combine_f8, "int8g128": L.samd_moe_down_combine_i8}
 
     def graph(fn):
         fn(); torch.cuda.synchronize()
@@ -228,8 +236,9 @@ def main():
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--buckets", default=",".join(map(str, BUCKETS)), help="row counts, comma separated")
-    ap.add_argument("--expert-format", default="none", choices=("none", "mxfp4", "int4g128", "fp8b128"),
-                    help="mxfp4: the MXFP4 expert kernels against the model-dtype ones; int4g128 / fp8b128: the INT4 / block-scaled FP8 ones against both")
+    ap.add_argument("--expert-format", default="none", choices=("none", "mxfp4", "int4g128", "fp8b128", "int8g128"),
+                    help="mxfp4: the MXFP4 expert kernels against the model-dtype ones; int4g128 / fp8b128: the INT4 / block-scaled FP8 ones against both; "
+                         "int8g128: the INT8 ones against the model-dtype and FP8 ones")
     ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp16"), help="model dtype of the formats and step measurements")
     a = ap.parse_args()
     a.buckets = tuple(int(b) for b in a.buckets.split(","))
