@@ -53,6 +53,8 @@ EXPONENT_RANGE = {torch.float16: (-23, 13), torch.bfloat16: (-125, 125)}
 GATE4 = {torch.float16: (8.0, 2), torch.bfloat16: (1.5, 0)}          # (weight, block exponent)
 GATE_RANGE4 = {torch.float16: (24, 512), torch.bfloat16: (24, 128)}
 DEPTH4 = {16: 8, 32: 3, 48: 2, 64: 3}                                # pipeline depths of the MXFP4 form (2 everywhere in the model-dtype form)
+# ... and of the other quantised forms (restated from csrc/gemm_kernels.hip: MoeW4Depth, MoeI8Depth, Moe8Depth), rows_pad -> depth
+DEPTHS = {"mxfp4": DEPTH4, "int4g128": DEPTH4, "int8g128": {16: 4, 32: 3, 48: 2, 64: 1}, "fp8b128": {16: 4, 32: 4, 48: 4, 64: 3}}
 
 
 def seed_of(*xs):
@@ -64,10 +66,19 @@ def seed_of(*xs):
 
 def chunk_sweep(form, rows_pad):
     """streams shorter than, at and above every depth; odd counts through the per-block refill of the 48 / 64-row kernels"""
-    depth = 2 if form is None else DEPTH4[rows_pad]
-    sweep = tuple(range(1, 8)) if form is None else tuple(range(1, depth + 3)) if rows_pad == 16 else (1, 2, 3, 4, 5, 7)
+    depth = 2 if form is None else DEPTHS[form][rows_pad]
+    if form in (None, "mxfp4"):
+        sweep = tuple(range(1, 8)) if form is None else tuple(range(1, depth + 3)) if rows_pad == 16 else (1, 2, 3, 4, 5, 7)
+    else:                                                        # (one of depth + 1, depth + 2 is the odd count above the depth)
+        sweep = tuple(range(1, depth + 3))
     assert {max(1, depth - 1), depth, depth + 1, depth + 2} <= set(sweep) and any(c % 2 and c > depth for c in sweep)
     return sweep
+
+
+def exact_sweep(form):
+    """[(K, rows_pad)] of the exact-integer tests of a quantised form's expert kernels: chunk_sweep and the stream lengths 1, 3, 9 that
+    those tests ran before the sweep (K = 256 / 768 / 2304), at every row tile"""
+    return [(KC * c, r) for r in ROWS for c in sorted(set(chunk_sweep(form, r)) | {1, 3, 9})]
 
 
 # ---- routings -------------------------------------------------------------------------------------------------------------------------------

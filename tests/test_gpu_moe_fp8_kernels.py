@@ -9,7 +9,8 @@ gross.
 Exact layout probe: one-hot activations make the down kernel copy weight columns: y[p] == dequantize_blocks(...)[e][:, k_p].to(dtype) with
 torch.equal for arbitrary (non power-of-two) scales, which pins fl32(q * s) followed by one rounding.
 Exact integers: codes integers |q| <= 8 (exact e4m3 values), scales 2^e with different e in the two blocks of every chunk, in neighbouring
-row blocks and for gate vs up, activations integers |a| <= 8, K = 256 / 768 / 2304 (1 chunk: shorter than every ring depth; 3; 9: longer
+row blocks and for gate vs up, activations integers |a| <= 8, K = 256 x every stream length of moe_planting.exact_sweep (depth - 1 .. depth + 2 of every row
+tile's pipeline, and 1 chunk: shorter than every ring depth; 3; 9: longer
 than the deepest), all four row tiles, expert counts from moe_planting.COUNTS.  Every exact sum is a multiple of 2^emin below 2^24 * 2^emin,
 so fp32 holds it -- and every block sum, scaled block sum and partial sum -- in any order, and what the launch must store is
 rne_dtype(exact sum), bit for bit.  Gate|up: the first 128 columns of h are 1 and the gate rows' first block is 4 at scale 2^-2, a bias of
@@ -145,6 +146,11 @@ def test_down_kernel_copies_weight_columns_exactly(dtype, I):
 
 
 # ------------------------------------------------------------------------------------------------ exact integers
+# every stream length around the pipeline depth of each row tile (moe_planting.chunk_sweep) and the lengths 1, 3, 9 (K = 256 / 768 / 2304)
+EXACT = MP.exact_sweep("fp8b128")
+EXACT_IDS = [f"{K}-{rows_pad}" for K, rows_pad in EXACT]
+
+
 def rne(x, dtype):
     """float64 -> dtype, one rounding: every x here is exact in fp32 (asserted), so the step through fp32 rounds nothing"""
     assert torch.equal(x.float().double(), x)
@@ -184,8 +190,7 @@ DOWN_EXPS = (-7, -3)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("rows_pad", MP.ROWS)
-@pytest.mark.parametrize("K", [256, 768, 2304])
+@pytest.mark.parametrize("K,rows_pad", EXACT, ids=EXACT_IDS)
 def test_down_stores_the_rounded_exact_sum_of_every_list_entry(K, rows_pad, dtype):
     R = MP.routing("counts", rows_pad)
     N = 256
@@ -223,8 +228,7 @@ GATE_EXPS, UP_EXPS = (-7, -8), (-6, -5)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("rows_pad", MP.ROWS)
-@pytest.mark.parametrize("K", [256, 768, 2304])
+@pytest.mark.parametrize("K,rows_pad", EXACT, ids=EXACT_IDS)
 def test_gate_up_stores_the_rounded_product_of_every_list_entry(K, rows_pad, dtype):
     R = MP.routing("counts", rows_pad)
     inter = 256                                                  # 4 tiles of 64 gate | 64 up columns

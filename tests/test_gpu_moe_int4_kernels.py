@@ -8,7 +8,8 @@ dequantised weights + 0.02 x max|out|.  Every group of 128 is multiplied by 2^s 
 groups' scales differ by up to 2^8 and the zero points span at least 8 codes: a swapped group word or zero point is gross.
 Exact layout probe: one-hot activations make the down kernel copy weight columns, compared with torch.equal.
 Exact integers: codes and zero points arbitrary in 0..15, scales 2^e with two different e in the two groups of every chunk, alternating
-along the rows, activations integers |a| <= 8, K = 256 / 768 / 2304 (1 chunk: shorter than every depth; 3; 9: longer than the deepest ring),
+along the rows, activations integers |a| <= 8, K = 256 x every stream length of moe_planting.exact_sweep (depth - 1 .. depth + 2 of
+every row tile's pipeline, and 1 chunk: shorter than every depth; 3; 9: longer than the deepest ring),
 all four row tiles, expert counts from moe_planting.COUNTS.  Every exact sum is a multiple of 2^emin below 2^24 * 2^emin, so fp32 holds it
 in any order and what the launch must store is rne_dtype(exact sum), bit for bit.  Gate|up: the first 128 columns of h are 1 and the gate
 rows' first group is (q - z) = 4 at scale 2^-2, a bias of 128 that keeps every gate sum above 20; there 1 + __expf(-g) is 1.0f whatever
@@ -135,6 +136,11 @@ def test_down_kernel_copies_weight_columns_exactly(dtype, I):
 
 
 # ------------------------------------------------------------------------------------------------ exact integers
+# every stream length around the pipeline depth of each row tile (moe_planting.chunk_sweep) and the lengths 1, 3, 9 (K = 256 / 768 / 2304)
+EXACT = MP.exact_sweep("int4g128")
+EXACT_IDS = [f"{K}-{rows_pad}" for K, rows_pad in EXACT]
+
+
 def rne(x, dtype):
     """float64 -> dtype, one rounding: every x here is exact in fp32 (asserted), so the step through fp32 rounds nothing"""
     assert torch.equal(x.float().double(), x)
@@ -175,8 +181,7 @@ DOWN_EXPS = (-4, -2)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("rows_pad", MP.ROWS)
-@pytest.mark.parametrize("K", [256, 768, 2304])
+@pytest.mark.parametrize("K,rows_pad", EXACT, ids=EXACT_IDS)
 def test_down_stores_the_rounded_exact_sum_of_every_list_entry(K, rows_pad, dtype):
     R = MP.routing("counts", rows_pad)
     N = 256
@@ -214,8 +219,7 @@ GATE_EXPS, UP_EXPS = (-7, -8), (-6, -7)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("rows_pad", MP.ROWS)
-@pytest.mark.parametrize("K", [256, 768, 2304])
+@pytest.mark.parametrize("K,rows_pad", EXACT, ids=EXACT_IDS)
 def test_gate_up_stores_the_rounded_product_of_every_list_entry(K, rows_pad, dtype):
     R = MP.routing("counts", rows_pad)
     inter = 256                                                  # 4 tiles of 64 gate | 64 up columns
