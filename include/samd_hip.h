@@ -707,6 +707,23 @@ int samd_gemm_skinny_i4(const void *d_A, const void *d_W4p, int32_t rows_pad, in
 int samd_gemm_pack_i8(const void *d_q, const void *d_z, const void *d_s, void *d_out, int32_t N, int32_t K, int32_t dtype, void *stream);
 int samd_gemm_skinny_i8(const void *d_A, const void *d_W8p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
                         int32_t dtype, void *stream);
+/* Unpack: a quantised projection back to row-major d_out [N][K] in the model dtype (dtype: f16 / bf16), read from the very buffer the matching
+ * samd_gemm_skinny_* call streams (nothing is repacked, no second copy) -- the inverses of samd_gemm_pack_*.  The one-pass prompt prefill of a
+ * quantised runner forms each projection this way in a scratch matrix, as the operand of the library product, and never keeps it.  The
+ * widening is the streaming kernels' own device code, so the result is the weight those launches multiply by:
+ *   _i4, _i8   rne_dtype((q - z) * s), bit for bit int4.dequantize_groups / int8.dequantize_groups (fp16: with subnormals); the buffer must
+ *              have been packed for `dtype`.
+ *   _f4        fp4(q) * 2^(e8 - 127): exact in dtype inside the exponent range samd_hip/mxfp4.py admits.
+ *   _f8        rne_dtype(fl32(float(q) * d_scale[n])), d_scale the fp32 [N] of samd_gemm_skinny_f8: fp8.dequantize_rows, then one rounding.
+ *   _f8b       rne_dtype(fl32(float(q) * d_sinv[n / 128][k / 128])), d_sinv the fp32 table of samd_gemm_skinny_f8b (8-byte aligned):
+ *              fp8.dequantize_blocks, then one rounding.  The FP8 launches never form a weight, so this rounding is the unpacked form's own.
+ * N % 128 == 0, K % 256 == 0, non-null 16-byte aligned buffers, d_out distinct from the inputs; anything else is SAMD_E_INVALID with the error
+ * text, before any device work.  One launch each, vector stores only, capturable. */
+int samd_gemm_unpack_f8(const void *d_W8p, const float *d_scale, int32_t N, int32_t K, void *d_out, int32_t dtype, void *stream);
+int samd_gemm_unpack_f8b(const void *d_W8p, const float *d_sinv, int32_t N, int32_t K, void *d_out, int32_t dtype, void *stream);
+int samd_gemm_unpack_f4(const void *d_W4p, int32_t N, int32_t K, void *d_out, int32_t dtype, void *stream);
+int samd_gemm_unpack_i4(const void *d_W4p, int32_t N, int32_t K, void *d_out, int32_t dtype, void *stream);
+int samd_gemm_unpack_i8(const void *d_W8p, int32_t N, int32_t K, void *d_out, int32_t dtype, void *stream);
 /* Mixture-of-experts MLP (Qwen3-MoE; HF Qwen3MoeSparseMoeBlock) at rows_pad in {16, 32, 48, 64}, hidden % 256 == 0, moe_inter % 256 == 0,
  * n_experts <= 256, top_k <= min(8, n_experts), f16 / bf16.  Every launch has a fixed grid and reads its counts from device memory, so the
  * three calls of a sparse layer can be captured.  norm_topk is a flag (Qwen3-MoE's norm_topk_prob), not a model name.

@@ -24,6 +24,7 @@
 // separate launches of 33-180 MB can stream (4.1-5.9 TB/s incl. ramp-up and tail).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <type_traits>
 #include "samd_common.h"
 
 #define LAUNCHCHK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { samd_set_error("kernel launch: %s", hipGetErrorString(e_)); return SAMD_E_HIP; } } while (0)
@@ -3514,6 +3515,154 @@ int samd_gemm_skinny_f8b(const void *d_A, const void *d_W8p, const float *d_sinv
     if (e != hipSuccess) { samd_set_error("samd_gemm_skinny_f8b: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
     LAUNCHCHK();
     return SAMD_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================
+// Unpack: a quantised projection back to row-major [N][K] in the model dtype, straight from the buffer its streaming launch reads -- the
+// inverses of samd_gemm_pack_f8 / _f4 / _i4 / _i8.  The one-pass prompt prefill of a quantised runner forms one projection at a time in a
+// scratch matrix and hands it to the library product (samd_hip/llama.py: _prefill_wide); nothing is kept.
+//   THE WEIGHTS are the ones the streaming launches multiply by, by construction: the widening is their device code -- W4Mx / W4Int's
+//   group + cvt (F4Widen's v_cvt_scalef32_pk_*_fp4 with the block scale; I4Widen), I8Widen, F8Widen -- called on the same registers' worth
+//   of a lane's unit, so MXFP4 is exact, INT4 / INT8 are rne_dtype((q - z) * s) with fp16 subnormals as v_pk_mul_f16 delivers them.  The
+//   FP8 launches never form a weight (the scale goes on fp32 sums), so here the exact widened code goes to fp32, times the fp32 scale, and
+//   is rounded ONCE to the model dtype: fp8.dequantize_rows / dequantize_blocks, then .to(dtype) -- one rounding per weight that the
+//   decode step does not carry.
+//   SHAPE: one 512-thread workgroup per packed block (tile t, chunk c), lane = the streaming kernels' lane (tid = 64 w + 16 g + n owns
+//   row 128 t + 16 w + n).  Temporal 16-byte loads of the lane's units and one load of its side data; the widened units (a 16-code unit is
+//   two, a 32-code unit four 16-byte pieces of its row) are staged in 64 KiB of LDS and leave as whole rows: every store instruction of a
+//   wave writes the 512 contiguous bytes that two rows have in this chunk.  Measured against storing each lane's pieces directly (16
+//   bytes per lane at a 32- or 64-byte stride, the line completed by the next one or three instructions): 22016 x 4096, fp16, 8-bit
+//   51 - 56 -> 45 - 46 us, 4-bit 63 - 65 -> 38 - 40 us (profiles/quant_prefill.md), so the staging stays.  64 KiB of static LDS: two
+//   workgroups per CU.  Plain vector loads and stores: capturable.
+// ================================================================================================
+enum { UNPACK_F8 = 0, UNPACK_F8B = 1, UNPACK_F4 = 2, UNPACK_I4 = 3, UNPACK_I8 = 4 };
+
+// rne_dtype(float(v) * s) of 8 exactly widened FP8 codes
+template <typename TT> struct UnpackScale;
+template <> struct UnpackScale<GF16> {
+    static __device__ __forceinline__ half8 mul(half8 v, float s) {
+        half8 r;
+#pragma unroll
+        for (int i = 0; i < 8; i++) r[i] = (_Float16)((float)v[i] * s);
+        return r;
+    }
+};
+template <> struct UnpackScale<GBF16> {
+    static __device__ __forceinline__ bf16x8 mul(bf16x8 v, float s) {
+        u32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float a = (float)v[2 * i] * s, b = (float)v[2 * i + 1] * s;
+            unsigned p;
+            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p) : "v"(a), "v"(b));
+            r[i] = p;
+        }
+        return __builtin_bit_cast(bf16x8, r);
+    }
+};
+
+template <int F, typename TT>
+__global__ __launch_bounds__(64 * GEMM_WAVES) void k_gemm_unpack(const unsigned char *__restrict__ Wp, const float *__restrict__ scale,
+                                                                 typename TT::elem *__restrict__ out, int K, int n_chunks) {
+    typedef typename TT::vec8 V;
+    constexpr bool W4 = F == UNPACK_F4 || F == UNPACK_I4;
+    constexpr size_t WCH = W4 ? 17408 : F == UNPACK_I8 ? 33792 : 32768, WU = 8192, WS = W4 ? 16384 : 32768;
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
+    const int t = (int)(blockIdx.x / (unsigned)n_chunks), c = (int)(blockIdx.x - (unsigned)t * (unsigned)n_chunks);
+    const unsigned char *blk = Wp + (size_t)blockIdx.x * WCH;
+    const int row = GEMM_COLS * t + 16 * w + n;
+    // the block's 64 KiB of output, [128 rows][32 units of 16 bytes]; unit u of row r sits at u ^ (r & 31), so the 16 rows of a wave's
+    // ds_write_b128 and the 32 units of a row's read spread over all banks
+    __shared__ __attribute__((aligned(16))) u32x4 stage[GEMM_COLS * 32];
+    const int rl = 16 * w + n;
+    auto put = [&](int kl, V v) { stage[rl * 32 + (((kl >> 3) ^ rl) & 31)] = __builtin_bit_cast(u32x4, v); };      // 8 weights at k = kl of this lane's row
+    if constexpr (W4) {
+        typedef typename std::conditional<F == UNPACK_F4, W4Mx, W4Int>::type Fmt;
+        typename Fmt::side_t side;
+        if constexpr (F == UNPACK_F4) side = *reinterpret_cast<const unsigned short *>(blk + WS + Fmt::slane(tid, w, n));
+        else side = *reinterpret_cast<const u32x2 *>(blk + WS + Fmt::slane(tid, w, n));
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const u32x4 u = *reinterpret_cast<const u32x4 *>(blk + WU * j + (size_t)tid * 16);
+            const auto grp = Fmt::template group<TT>(side, j);
+#pragma unroll
+            for (int i = 0; i < 4; i++) put(128 * j + 32 * g + 8 * i, Fmt::template cvt<TT>(u[i], grp));      // the unit's 32 codes: k + 8 i .. + 7 in dword i
+        }
+    } else {
+        u32x2 gd = {0u, 0u};
+        float srow = 0.f;
+        if constexpr (F == UNPACK_I8) gd = *reinterpret_cast<const u32x2 *>(blk + WS + (size_t)(16 * w + n) * 8);
+        if constexpr (F == UNPACK_F8) srow = scale[row];
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const u32x4 u = *reinterpret_cast<const u32x4 *>(blk + WU * b + (size_t)tid * 16);
+            const int kl = 64 * b + 16 * g;                                   // the unit's 16 codes in k order
+            if constexpr (F == UNPACK_I8) {
+                const auto grp = I8Widen<TT>::group(gd, b >> 1);
+                put(kl, I8Widen<TT>::cvt(u[0], u[1], grp));
+                put(kl + 8, I8Widen<TT>::cvt(u[2], u[3], grp));
+            } else {
+                // block-scaled: the checkpoint's own table [N / 128][K / 128]; tile t is its row t, k block 2 c + (b >> 1)
+                const float s = F == UNPACK_F8 ? srow : scale[(size_t)t * 2 * n_chunks + 2 * c + (b >> 1)];
+                put(kl, UnpackScale<TT>::mul(F8Widen<TT>::cvt(u[0], u[1]), s));
+                put(kl + 8, UnpackScale<TT>::mul(F8Widen<TT>::cvt(u[2], u[3]), s));
+            }
+        }
+    }
+    __syncthreads();
+    // 32 consecutive lanes write the 512 contiguous bytes one row has in this chunk: every store instruction of a wave is two whole row pieces
+    typename TT::elem *oblk = out + (size_t)GEMM_COLS * t * K + (size_t)c * GEMM_KC;
+#pragma unroll
+    for (int it = 0; it < 8; it++) {
+        const int u = it * 512 + tid, r = u >> 5, col = u & 31;
+        *reinterpret_cast<u32x4 *>(oblk + (size_t)r * K + 8 * col) = stage[r * 32 + ((col ^ r) & 31)];
+    }
+}
+
+// the checks and the launch of samd_gemm_unpack_*: everything is decided before any device work
+template <int F>
+static int gemm_unpack_call(const char *fn, const void *d_Wp, const float *d_scale, int N, int K, void *d_out, int dtype, void *stream) {
+    constexpr bool scaled = F == UNPACK_F8 || F == UNPACK_F8B;
+    if (!d_Wp || !d_out || d_Wp == d_out || (scaled && (!d_scale || (const void *)d_scale == d_out)) || (F == UNPACK_F8B && ((uintptr_t)d_scale & 7) != 0) ||
+        (((uintptr_t)d_Wp | (uintptr_t)d_out) & 15) != 0 || N < GEMM_COLS || N % GEMM_COLS != 0 || K < GEMM_KC || K % GEMM_KC != 0 ||
+        (long long)(N / GEMM_COLS) * (K / GEMM_KC) > 0x7fffffffLL || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("%s: needs N %% 128 == 0, K %% 256 == 0, dtype fp16 or bf16, 16-byte aligned distinct buffers%s", fn,
+                       F == UNPACK_F8 ? " and a scale per row" : F == UNPACK_F8B ? " and an 8-byte aligned block-scale table" : "");
+        return SAMD_E_INVALID;
+    }
+    const dim3 grid((unsigned)((N / GEMM_COLS) * (K / GEMM_KC)));
+    if (dtype == SAMD_F16)
+        hipLaunchKernelGGL((k_gemm_unpack<F, GF16>), grid, dim3(64 * GEMM_WAVES), 0, (hipStream_t)stream, (const unsigned char *)d_Wp, d_scale, (_Float16 *)d_out, K,
+                           K / GEMM_KC);
+    else
+        hipLaunchKernelGGL((k_gemm_unpack<F, GBF16>), grid, dim3(64 * GEMM_WAVES), 0, (hipStream_t)stream, (const unsigned char *)d_Wp, d_scale, (__bf16 *)d_out, K,
+                           K / GEMM_KC);
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+extern "C" {
+
+int samd_gemm_unpack_f8(const void *d_W8p, const float *d_scale, int32_t N, int32_t K, void *d_out, int32_t dtype, void *stream) {
+    return gemm_unpack_call<UNPACK_F8>("samd_gemm_unpack_f8", d_W8p, d_scale, N, K, d_out, dtype, stream);
+}
+
+int samd_gemm_unpack_f8b(const void *d_W8p, const float *d_sinv, int32_t N, int32_t K, void *d_out, int32_t dtype, void *stream) {
+    return gemm_unpack_call<UNPACK_F8B>("samd_gemm_unpack_f8b", d_W8p, d_sinv, N, K, d_out, dtype, stream);
+}
+
+int samd_gemm_unpack_f4(const void *d_W4p, int32_t N, int32_t K, void *d_out, int32_t dtype, void *stream) {
+    return gemm_unpack_call<UNPACK_F4>("samd_gemm_unpack_f4", d_W4p, nullptr, N, K, d_out, dtype, stream);
+}
+
+int samd_gemm_unpack_i4(const void *d_W4p, int32_t N, int32_t K, void *d_out, int32_t dtype, void *stream) {
+    return gemm_unpack_call<UNPACK_I4>("samd_gemm_unpack_i4", d_W4p, nullptr, N, K, d_out, dtype, stream);
+}
+
+int samd_gemm_unpack_i8(const void *d_W8p, int32_t N, int32_t K, void *d_out, int32_t dtype, void *stream) {
+    return gemm_unpack_call<UNPACK_I8>("samd_gemm_unpack_i8", d_W8p, nullptr, N, K, d_out, dtype, stream);
 }
 
 }  // extern "C"

@@ -187,6 +187,11 @@ _PROTOS = {
     "samd_gemm_skinny_i4": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "samd_gemm_pack_i8": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),
     "samd_gemm_skinny_i8": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
+    "samd_gemm_unpack_f8": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _I32, _VP]),
+    "samd_gemm_unpack_f8b": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _I32, _VP]),
+    "samd_gemm_unpack_f4": (C.c_int, [_VP, _I32, _I32, _VP, _I32, _VP]),
+    "samd_gemm_unpack_i4": (C.c_int, [_VP, _I32, _I32, _VP, _I32, _VP]),
+    "samd_gemm_unpack_i8": (C.c_int, [_VP, _I32, _I32, _VP, _I32, _VP]),
     "samd_moe_workspace_layout": (_I32, [_I32]),
     "samd_moe_workspace": (_I64, [_I32, _I32, _I32, _I32, _I32]),
     "samd_moe_pack_experts": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _VP]),

@@ -64,6 +64,25 @@ def _weight_format(weight_format, weights, dtype):
     return fmt
 
 
+QUANT_FORMATS = ("fp8", "fp8b128", "mxfp4", "int4g128", "int8g128")
+
+
+def quant_prefill_min_rows(default):
+    """the prompt length from which a quantised dense runner takes the one-pass prefill: SAMD_QUANT_PREFILL_MIN_ROWS if set, else `default`
+    (LlamaRunner.QUANT_PF_MIN_ROWS).  A multiple of 64 and >= 128 -- the one-pass form starts where the 64-row chunks stop being one or two
+    launches' worth; anything else raises SamdError.  Pure Python: no device, no library."""
+    raw = os.environ.get("SAMD_QUANT_PREFILL_MIN_ROWS")
+    if raw is None or raw.strip() == "":
+        return int(default)
+    try:
+        rows = int(raw.strip())
+    except ValueError:
+        raise SamdError(f"SAMD_QUANT_PREFILL_MIN_ROWS={raw!r}: expected an integer number of prompt rows (a multiple of 64, >= 128)") from None
+    if rows < 2 * TILE_ROWS or rows % TILE_ROWS != 0:
+        raise SamdError(f"SAMD_QUANT_PREFILL_MIN_ROWS={rows}: must be a multiple of 64 and >= 128")
+    return rows
+
+
 def _is_f4_tensor(t):
     return t.dtype == torch.uint8 or MX.is_fp4_dtype(t.dtype)
 
@@ -573,7 +592,7 @@ class LlamaRunner:
                         raise SamdError(f"{k} must be a contiguous {dtype} tensor on the GPU")
             self.epi = [epi(l, True) for l in weights["layers"]]
             self.epi_nobias = [epi(l, False) for l in weights["layers"]]
-        self.row_major_released = quant or moe                   # (FP8 / MXFP4 / experts: no row-major projections; prefill runs in 64-row chunks)
+        self.row_major_released = quant or moe                   # (quantised / experts: no row-major projections; short prompts run in 64-row chunks, long ones unpack per projection)
         if moe and self.wp:
             # no launch of an MoE runner reads a row-major projection that has a packed form (every bucket streams): only their shapes stay
             for l, lp in zip(self.w["layers"], self.wp["layers"]):
@@ -627,6 +646,8 @@ class LlamaRunner:
         rep["total"] = sum(rep.values())
         if self.weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128", "int8g128"):
             rep["weight_format"] = self.weight_format
+        if getattr(self, "_qpf_scratch", None) is not None:      # one unpacked projection of the one-pass prefill: no weights of its own, so
+            rep["quant_prefill_scratch"] = nbytes(self._qpf_scratch)          # outside "total"; there from the first such prefill on
         rep["expert_format"] = self.expert_format                # None: experts (if any) in the model dtype; packed_moe_* are the bytes held
         return rep
 
@@ -1484,7 +1505,8 @@ class LlamaRunner:
         the last prompt position in session.start_token.  on_chunk(tokens int32[64], logits [64,V], n, hidden [64,H]) is
         called per chunk (Token Recycle learns from the prompt logits, EAGLE-2 from the last hidden states:
         S/samd_model.py:117-122).  Prompts of 128 tokens or more take a one-pass form unless SAMD_PREFILL=chunked: _prefill_wide on a
-        runner that holds its row-major matrices, _prefill_moe (same bits as the chunks) on a mixture-of-experts runner."""
+        runner that holds its row-major matrices, _prefill_moe (same bits as the chunks) on a mixture-of-experts runner; a quantised dense
+        runner takes _prefill_wide from QUANT_PF_MIN_ROWS tokens on (SAMD_QUANT_PREFILL_MIN_ROWS), unpacking one projection at a time."""
         ids = input_ids.reshape(-1).to(device=self.device, dtype=torch.int32)
         N = ids.numel()
         if N < 1 or N > self.max_len:
@@ -1493,6 +1515,9 @@ class LlamaRunner:
             return self._prefill_wide(session, ids, on_chunk)
         if N >= self.MOE_PF_MIN_ROWS and os.environ.get("SAMD_PREFILL", "wide") != "chunked" and self.shape.moe:
             return self._prefill_moe(session, ids, on_chunk)
+        if (self.weight_format in QUANT_FORMATS and not self.shape.moe and os.environ.get("SAMD_PREFILL", "wide") != "chunked"
+                and N >= quant_prefill_min_rows(self.QUANT_PF_MIN_ROWS)):
+            return self._prefill_wide(session, ids, on_chunk)        # (each projection unpacked into a scratch matrix: _pf_weight)
         v = session.device_views()
         b = None
         for c0 in range(0, N, TILE_ROWS):
@@ -1655,6 +1680,37 @@ class LlamaRunner:
         rest = -(-(M - R) // 64) * 64
         return R if self._pf_plan.get(key, {}).get(R, {}).get(rest, False) else 0
 
+    # ---- quantised dense runners: the one-pass prefill's operand, formed on the device (profiles/quant_prefill.md) ----
+    QUANT_PF_MIN_ROWS = 256           # the switch-over: shorter prompts keep the 64-row chunks (measured: profiles/quant_prefill.md)
+
+    def _pf_weight(self, li, key):
+        """projection `key` of layer li as the library product's row-major operand: the runner's own matrix, or -- a quantised runner holds
+        none -- its packed buffer unpacked (samd_gemm_unpack_*: the weights the streaming launch multiplies by) into the scratch matrix,
+        which the next projection overwrites.  The scratch ([max N x K over the four projections], model dtype) is allocated at the first
+        one-pass prefill and kept; memory_report() shows it, weight_bytes() does not count it."""
+        w = self.w["layers"][li][key]
+        if self.weight_format not in QUANT_FORMATS:
+            return w
+        N, K = w.shape
+        if getattr(self, "_qpf_scratch", None) is None:
+            elems = max(self.w["layers"][0][k].shape[0] * self.w["layers"][0][k].shape[1] for k in F8.PROJECTIONS)
+            self._qpf_scratch = torch.empty(elems, dtype=self.dtype, device=self.device)
+        if N * K > self._qpf_scratch.numel():
+            raise SamdError(f"projection {key} of layer {li}, shape ({N}, {K}), exceeds the prefill scratch of {self._qpf_scratch.numel()} elements")
+        out = self._qpf_scratch[:N * K].view(N, K)
+        L, lp, st = lib(), self.wp["layers"][li], current_stream()
+        if self.weight_format == "fp8":
+            check(L.samd_gemm_unpack_f8(_ptr(lp[key + "_f8"][0]), _ptr(lp[key + "_f8"][1]), N, K, _ptr(out), self.dt, st))
+        elif self.weight_format == "fp8b128":
+            check(L.samd_gemm_unpack_f8b(_ptr(lp[key + "_f8b"][0]), _ptr(lp[key + "_f8b"][1]), N, K, _ptr(out), self.dt, st))
+        elif self.weight_format == "mxfp4":
+            check(L.samd_gemm_unpack_f4(_ptr(lp[key + "_f4"]), N, K, _ptr(out), self.dt, st))
+        elif self.weight_format == "int4g128":
+            check(L.samd_gemm_unpack_i4(_ptr(lp[key + "_i4"]), N, K, _ptr(out), self.dt, st))
+        else:
+            check(L.samd_gemm_unpack_i8(_ptr(lp[key + "_i8"]), N, K, _ptr(out), self.dt, st))
+        return out
+
     def _pf_mm(self, x, w, out, key, bias=None):
         """out = x @ w.T (+ bias: HF's own nn.Linear arithmetic, torch.addmm -- the q|k|v of Qwen2, whose V may go to the cache or to SDPA
         without passing the RoPE kernel's per-element path)"""
@@ -1703,7 +1759,7 @@ class LlamaRunner:
         delta = None
         for li, w in enumerate(self.w["layers"]):
             check(L.samd_rmsnorm(_ptr(x), _ptr(delta), _ptr(w["ln1"]), _ptr(h), N, s.hidden, s.eps, dt, 0, 0, st))
-            self._pf_mm(h, w["wqkv"], qkv, "wqkv", bias=w.get("bqkv"))
+            self._pf_mm(h, self._pf_weight(li, "wqkv"), qkv, "wqkv", bias=w.get("bqkv"))
             if self.epi is not None:
                 # Qwen2 / Qwen3: the bias is already in the product; q / k norm (if any) in front of the RoPE
                 check(L.samd_rope_kv_write_epi(_ptr(qkv), _ptr(relpos), _ptr(d_L), _ptr(d_n), _ptr(self.cos), _ptr(self.sin), None, _ptr(q),
@@ -1727,17 +1783,17 @@ class LlamaRunner:
                 check((L.samd_prefill_attention_vt if self.v_transposed else L.samd_prefill_attention)(
                     _ptr(q), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(ao), dt, N, 0, s.heads, s.kv_heads,
                     s.head_dim, self.max_len, self.scale, st))
-                self._pf_mm(ao, w["wo"], o, "wo")
+                self._pf_mm(ao, self._pf_weight(li, "wo"), o, "wo")
             else:
                 kk = self.kv[li, 0][:, :Np]
                 if s.kv_heads != s.heads:
                     kk, vv = kk.repeat_interleave(s.heads // s.kv_heads, dim=0), vv.repeat_interleave(s.heads // s.kv_heads, dim=0)
                 att = torch.nn.functional.scaled_dot_product_attention(qp.transpose(0, 1)[None], kk[None], vv[None], is_causal=True, scale=self.scale)
-                self._pf_mm(att[0, :, :N].transpose(0, 1).reshape(N, -1), w["wo"], o, "wo")
+                self._pf_mm(att[0, :, :N].transpose(0, 1).reshape(N, -1), self._pf_weight(li, "wo"), o, "wo")
             check(L.samd_rmsnorm(_ptr(x), _ptr(o), _ptr(w["ln2"]), _ptr(h), N, s.hidden, s.eps, dt, 0, 0, st))
-            self._pf_mm(h, w["wgu"], gu, "wgu")
+            self._pf_mm(h, self._pf_weight(li, "wgu"), gu, "wgu")
             check(L.samd_silu_mul(_ptr(gu), _ptr(act), N, s.inter, dt, 0, 0, st))
-            self._pf_mm(act, w["wdown"], d, "wdown")
+            self._pf_mm(act, self._pf_weight(li, "wdown"), d, "wdown")
             delta = d
         check(L.samd_rmsnorm(_ptr(x), _ptr(delta), _ptr(self.w["norm"]), _ptr(h), N, s.hidden, s.eps, dt, 0, 0, st))
         b = self._buffers(1)
