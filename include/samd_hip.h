@@ -229,6 +229,13 @@ int samd_session_static_walk(samd_session_t *s, const samd_static_t *sam, const 
  * Pass NULL arrays to query sizes only.  Edges state-major in dict (insertion) order.  Synchronises. */
 int samd_session_export(samd_session_t *s, int64_t out_info[10], int32_t *h_link, int32_t *h_length, int32_t *h_minend,
                         int32_t *h_deg, int32_t *h_edge_tok, int32_t *h_edge_dst, int32_t *h_text, void *stream);
+/* host read-back of the dynamic automaton's TRANSITION TABLE as it lies in the arena (tests): out_info: [0]=H (slots, a power of
+ * two) [1]=n_states.  h_key/h_dst/h_next: [H], slot by slot -- key = state << 32 | token, all-ones = empty; dst and next (the next
+ * slot of the same state's dict order, -1 = last) mean something for occupied slots only.  h_head/h_tail: [n_states], first / last
+ * slot of each state's chain, -1 = no edge.  samd_session_export walks head -> next only; this call also shows a duplicated key, an
+ * orphaned slot or a key that survived a reset.  Pass NULL arrays to query sizes only.  Synchronises. */
+int samd_session_export_table(samd_session_t *s, int64_t out_info[2], uint64_t *h_key, int32_t *h_dst, int32_t *h_next,
+                              int32_t *h_head, int32_t *h_tail, void *stream);
 /* set the cursors explicitly (tests; mirrors assigning cur_index/cur_length in the reference objects) */
 int samd_session_set_cursors(samd_session_t *s, int32_t dyn_index, int32_t dyn_length, int32_t st_index,
                              int32_t st_length, void *stream);

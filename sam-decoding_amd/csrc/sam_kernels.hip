@@ -1210,6 +1210,26 @@ int samd_session_export(samd_session_t *s, int64_t out_info[10], int32_t *h_link
     return SAMD_OK;
 }
 
+int samd_session_export_table(samd_session_t *s, int64_t out_info[2], uint64_t *h_key, int32_t *h_dst, int32_t *h_next,
+                              int32_t *h_head, int32_t *h_tail, void *stream) {
+    if (!s || !out_info) return SAMD_E_INVALID;
+    const SessionDev &D = s->dev;
+    int32_t ns = 0;
+    D2H(&ns, D.meta + M_NSTATES, sizeof(ns));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    const size_t H = (size_t)D.hmask + 1;
+    out_info[0] = (int64_t)H; out_info[1] = ns;
+    if (ns < 0 || ns > D.cap_states) { samd_set_error("samd_session_export_table: n_states %d outside the arena", ns); return SAMD_E_INVALID; }
+    // the arrays as they lie in the arena: every slot, occupied or not -- what samd_session_export's chain walk cannot see
+    if (h_key) D2H(h_key, D.hkey, 8 * H);
+    if (h_dst) D2H(h_dst, D.hdst, 4 * H);
+    if (h_next) D2H(h_next, D.hnext, 4 * H);
+    if (h_head) D2H(h_head, D.head, 4ull * ns);
+    if (h_tail) D2H(h_tail, D.tail, 4ull * ns);
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return SAMD_OK;
+}
+
 int samd_session_set_cache_length(samd_session_t *s, int32_t length, void *stream) {
     if (!s || length < 0) return SAMD_E_INVALID;
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)s->dev.cache_length, length, 1, (hipStream_t)stream));

@@ -103,6 +103,7 @@ _PROTOS = {
     "samd_dyn_walk": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP]),
     "samd_session_static_walk": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     "samd_session_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "samd_session_export_table": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "samd_session_set_cursors": (C.c_int, [_VP, _I32, _I32, _I32, _I32, _VP]),
     "samd_session_draft": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "samd_session_draft_seq": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP]),
@@ -613,6 +614,18 @@ class Session:
         out = dict(zip(keys, list(info)))
         out.update(link=link, length=length, aux=minend, deg=deg, edge_tok=et, edge_dst=ed, text=text)
         return out
+
+    def export_table(self):
+        """the transition table as it lies in the arena (samd_session_export_table): key / dst / next of every slot, head / tail of
+        every state.  Tests compare it slot by slot with a model of the hash and the probe."""
+        info = (C.c_int64 * 2)()
+        check(lib().samd_session_export_table(self._h, info, None, None, None, None, None, current_stream()))
+        H, ns = info[0], info[1]
+        key = np.empty(H, np.uint64)
+        dst, nxt = np.empty(H, np.int32), np.empty(H, np.int32)
+        head, tail = np.empty(ns, np.int32), np.empty(ns, np.int32)
+        check(lib().samd_session_export_table(self._h, info, _ptr(key), _ptr(dst), _ptr(nxt), _ptr(head), _ptr(tail), current_stream()))
+        return dict(H=int(H), n_states=int(ns), key=key, dst=dst, next=nxt, head=head, tail=tail)
 
 
 class TokenRecycleTable:
