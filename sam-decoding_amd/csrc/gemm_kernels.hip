@@ -1348,17 +1348,18 @@ __global__ __launch_bounds__(256) void k_gemm_pack_f8(const uint4 *__restrict__ 
     out[u] = W8[(row * K + col) / 16];
 }
 
-template <typename TT, int RT, int DEPTH>
-static hipError_t gemm_f8_launch(dim3 grid, hipStream_t st, const void *A, const void *W8, const float *scale, float *partial, void *out, int K, int N,
-                                 int splits) {
-    constexpr int lds = (DEPTH + 1) * 16 * RT * GEMM_KC * 2;
-    if constexpr (lds > 65536) {
+// the dynamic LDS of a streaming kernel with `depth` chunks in flight: depth + 1 A buffers of 16 rt rows
+static constexpr int stream_lds(int depth, int rt) { return (depth + 1) * 16 * rt * GEMM_KC * 2; }
+
+// one launch of a weight-only streaming kernel, dense or expert: dynamic LDS above 64 KiB is reserved once per kernel instantiation and device
+template <auto KERN, int LDS, typename... A>
+static hipError_t stream_launch(dim3 grid, hipStream_t st, A... args) {
+    if constexpr (LDS > 65536) {
         static unsigned long long done = 0ull;                     // per-device (samd_common.h)
-        const hipError_t attr = samd_reserve_lds((const void *)k_gemm_skinny_f8<TT, RT, DEPTH>, lds, &done);
+        const hipError_t attr = samd_reserve_lds((const void *)KERN, LDS, &done);
         if (attr != hipSuccess) return attr;
     }
-    hipLaunchKernelGGL((k_gemm_skinny_f8<TT, RT, DEPTH>), grid, dim3(64 * GEMM_WAVES), lds, st, (const typename TT::elem *)A, (const unsigned char *)W8, scale,
-                       partial, (typename TT::elem *)out, K, N, K / GEMM_KC, splits);
+    hipLaunchKernelGGL(KERN, grid, dim3(64 * GEMM_WAVES), LDS, st, args...);
     return hipSuccess;
 }
 
@@ -1384,7 +1385,8 @@ int samd_gemm_skinny_f8(const void *d_A, const void *d_W8p, const float *d_scale
     const hipStream_t st = (hipStream_t)stream;
     float *part = splits == 1 ? nullptr : d_partial;
     void *out = splits == 1 ? d_out : nullptr;
-#define GO(TT, RT, D) e = gemm_f8_launch<TT, RT, D>(grid, st, d_A, d_W8p, d_scale, part, out, K, N, splits)
+#define GO(TT, RT, D) e = stream_launch<k_gemm_skinny_f8<TT, RT, D>, stream_lds(D, RT)>(grid, st, (const typename TT::elem *)d_A, (const unsigned char *)d_W8p, \
+        d_scale, part, (typename TT::elem *)out, K, N, K / GEMM_KC, splits)
 #define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1, 4); else if (rows_pad == 32) GO(TT, 2, 4); else if (rows_pad == 48) GO(TT, 3, 4); else GO(TT, 4, 3); } while (0)
     hipError_t e;
     if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
@@ -1433,7 +1435,7 @@ template <> struct F4Widen<GBF16> {
 // INT4 (AWQ / GPTQ: unsigned 4-bit codes, one scale and one 4-bit zero point per 128 elements along k) weight-only projection:
 // out[m][n] = sum_k A[m][k] * W[n][k], W[n][k] = rne_dtype((q[n][k] - z[n][k/128]) * s[n][k/128]), A and s in the model dtype
 // (samd_hip/int4.py has the numeric contract).  Grid, A staging by LDS-DMA, A-side swizzle, counted waits, in-out load destinations and
-// MFMA sequence are MXFP4's (one body, gemm_skinny_w4 below); the weight block and the widening differ: integer arithmetic with a zero point and a scale that
+// MFMA sequence are MXFP4's (one body, gemm_stream_w4 below); the weight block and the widening differ: integer arithmetic with a zero point and a scale that
 // is no power of two, which v_cvt_scalef32_pk_*_fp4 cannot do.
 //   PACKED LAYOUT (samd_gemm_pack_i4): block (tile t = 128 columns, chunk c = 256 k) is 17 KiB contiguous at (t * K/256 + c) * 17408 bytes:
 //   16 KiB of elements, then 1 KiB of group data.  Element unit j * 512 + tid (16 bytes, j = 0, 1) holds the 32 codes
@@ -1493,6 +1495,136 @@ template <> struct I4Widen<GBF16> {
 };
 
 // ================================================================================================
+// THE SIDE of a weight-only streaming kernel: whose rows and whose weight tile a workgroup works on, and where its sums go.  A kernel is a
+// weight stream (one body per format: gemm_stream_w4, gemm_stream_i8) times a side, chosen by `if constexpr` inside the body.
+//   SIDE_DENSE   rows 0 .. R - 1 of A, weight tile blockIdx.x, the chunk range [c0, c1) of split blockIdx.y, and stream_store_dense: the
+//                rounded sum (splits == 1) or the split's fp32 partial.
+//   SIDE_EXPERT  one active expert's share of a gathered projection (the mixture-of-experts sections below have the calls and the routing
+//                workspace).  The grid's y dimension is the shape's upper bound of active experts, min(E, rows * k); a workgroup whose
+//                slot is >= ws[0], the count the router left on the device, exits at once (moe_side_idle: uniform, before any barrier).  moe_side_open
+//                reads the slot's expert and entry count (clamped to the row tile) and copies its list of entries p = row * k + slot into
+//                static LDS; tile rows past the count repeat entry 0, so every staged row is a valid one.  The caller's __syncthreads()
+//                follows -- left to the caller so that a body can stage more static LDS under the same barrier, as moe8_expert_gemm does
+//                with its scales.  moe_side_row gives a thread the XV source rows of its A staging units (srow: p / k of h for gate|up, p
+//                itself of act for down): the gather is an indirection on the LDS-DMA's source address, no copy.  The chunk range is the
+//                whole of K: no split-K, no atomics.  moe_side_store is the epilogue; rows >= cnt are not stored.  GU: waves 4-7 hold the
+//                up columns that waves 0-3's gate columns meet; they pass through LDS (the A tiles are dead by then) and act[p][I] gets
+//                HF's act_fn(gate) * up with its roundings in the model dtype: gate, up, silu(gate) and the product each rounded once (as
+//                k_gemm_skinny EPI 1 / k_silu_mul).  Otherwise y[p][N] gets the sum rounded once.
+//   SIDE_WIDE    the expert side over the wide workspace (one-pass prefill): the slot is a TILE of 64 entries, ws[0] the tile count, and
+//                the tile's record {expert, first entry, entries} names the expert and its part of the entry array.
+// ================================================================================================
+enum { SIDE_DENSE, SIDE_EXPERT, SIDE_WIDE };
+
+#define MOE_MAX_E 256
+#define MOE_MAX_K 8
+#define MOE_MAX_ROWS 64
+#define MOE_WS_ACTIVE 16
+#define MOE_WS_COUNT (MOE_WS_ACTIVE + MOE_MAX_E)
+#define MOE_WS_LIST (MOE_WS_COUNT + MOE_MAX_E)
+#define MOE_WS_INTS (MOE_WS_LIST + MOE_MAX_E * MOE_MAX_ROWS)
+#define MOE_WS_Y_OFF (((MOE_WS_INTS * 4 + 255) / 256) * 256)
+// the wide calls' routing workspace (samd_moe_wide_*, at the end of the mixture-of-experts sections): fixed word offsets, so that the
+// expert side reads a tile record without knowing the shape
+#define MOEW_MAX_ROWS 4096
+#define MOEW_TILE_INTS 3
+#define MOEW_MAX_TILES (MOE_MAX_E + MOEW_MAX_ROWS * MOE_MAX_K / MOE_MAX_ROWS)
+#define MOEW_WS_ACTIVE 16
+#define MOEW_WS_COUNT (MOEW_WS_ACTIVE + MOE_MAX_E)
+#define MOEW_WS_OFFSET (MOEW_WS_COUNT + MOE_MAX_E)
+#define MOEW_WS_TILE (MOEW_WS_OFFSET + MOE_MAX_E)
+#define MOEW_WS_ENTRY (MOEW_WS_TILE + MOEW_TILE_INTS * MOEW_MAX_TILES)
+
+// the workgroup's list of entries, in static LDS
+__device__ __forceinline__ int *moe_side_list() {
+    __shared__ int lst[MOE_MAX_ROWS];
+    return lst;
+}
+
+// no work for this slot (uniform): the caller returns at once.  (Kept apart from moe_side_open so that the exit is a plain branch of the kernel.)
+__device__ __forceinline__ bool moe_side_idle(const int *ws) { return (int)blockIdx.y >= ws[0]; }
+
+// the slot's expert, its entry count (<= R) and the list fill; the caller's barrier follows.  (The helpers return values, not references:
+// what they compute then folds into the kernel as if written there, and the code objects stay those of the hand-written copies.)
+struct MoeSlot { int expert, cnt; };
+template <int R, bool WIDE>
+__device__ __forceinline__ MoeSlot moe_side_open(const int *ws) {
+    int *lst = moe_side_list();
+    const int tid = threadIdx.x, slot_a = blockIdx.y;
+    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
+    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
+    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
+    cnt = cnt > R ? R : cnt;
+    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
+    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
+    return {expert, cnt};
+}
+
+// source row i of this thread's A staging units: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
+template <bool GU>
+__device__ __forceinline__ int moe_side_row(int i, int top_k) {
+    const int tid = threadIdx.x;
+    const int p = moe_side_list()[(tid >> 5) + 16 * i];
+    return GU ? p / top_k : p;
+}
+
+// C layout of mfma_16x16: lane (w, n, g -- the caller's own values, so that its expressions stay shared) holds rows 4g + r of column n.
+// ex: the dynamic LDS, [R][64] up values
+template <typename TT, int RT, bool GU>
+__device__ __forceinline__ void moe_side_store(const floatx4 (&acc)[RT], int cnt, typename TT::elem *out, int N, float *ex, int w, int n, int g) {
+    typedef typename TT::elem E;
+    const int *lst = moe_side_list();
+    if constexpr (GU) {
+        __syncthreads();
+        if (w >= 4) {
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) ex[(16 * mt + 4 * g + r) * 64 + 16 * (w - 4) + n] = acc[mt][r];
+        }
+        __syncthreads();
+        if (w < 4) {
+#pragma unroll
+            for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int m = 16 * mt + 4 * g + r;
+                    if (m >= cnt) continue;
+                    const float gf = (float)(E)acc[mt][r], uf = (float)(E)ex[m * 64 + 16 * w + n];
+                    const E sv = (E)(gf / (1.f + __expf(-gf)));
+                    out[(size_t)lst[m] * (N / 2) + blockIdx.x * 64 + 16 * w + n] = (E)((float)sv * uf);
+                }
+        }
+    } else {
+        const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+#pragma unroll
+        for (int mt = 0; mt < RT; mt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int m = 16 * mt + 4 * g + r;
+                if (m < cnt) out[(size_t)lst[m] * N + n0 + n] = (E)acc[mt][r];
+            }
+    }
+}
+
+// the dense side's store: the scales went in with the widening, so ONE rounding and nothing else; a split stores its fp32 partial
+template <typename TT, int RT>
+__device__ __forceinline__ void stream_store_dense(const floatx4 (&acc)[RT], float *partial, typename TT::elem *out, int N, int w, int n, int g) {
+    typedef typename TT::elem E;
+    const int n0 = blockIdx.x * GEMM_COLS + 16 * w, split = blockIdx.y;
+#pragma unroll
+    for (int mt = 0; mt < RT; mt++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int m = 16 * mt + 4 * g + r;
+            const float v = acc[mt][r];
+            if (out) out[(size_t)m * N + n0 + n] = (E)v;
+            else __hip_atomic_store(&partial[((size_t)split * (16 * RT) + m) * N + n0 + n], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// ================================================================================================
 // The 4-bit streaming body shared by MXFP4 and INT4.  Both formats stream 17 KiB (tile, chunk) blocks -- 16 KiB of elements, then 1 KiB of
 // per-chunk side data -- over the grid, the LDS-DMA A staging, the A-side swizzle and the MFMA order of k_gemm_skinny_f8.  A format is a
 // small policy: the type of a lane's side data (side_t), its byte offset behind the elements (slane), the ONE nt load that fetches it
@@ -1531,7 +1663,8 @@ __device__ __forceinline__ void gemm_wait_younger_deep(int younger) {
     asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
 }
 
-// THE PIPELINE (this block speaks for moe_w4_expert_gemm too, which differs only in where A rows and the weight tile come from).
+// THE PIPELINE (explained here for every weight-only stream with in-out destinations: gemm_stream_i8, moe_expert_gemm, moe8_expert_gemm
+// and k_gemm_skinny_f8b point here).
 //   Hand-issued nt element and side-data loads, counted waits and bare barriers: see k_gemm_skinny.  3 + XV memory operations per lane and
 //   chunk: 2 element loads, 1 side-data load, the A staging.
 //   In-out destinations: the destination registers are defined once, up front, and every load is an in-out ("+v") of that value.  A load
@@ -1540,11 +1673,15 @@ __device__ __forceinline__ void gemm_wait_younger_deep(int younger) {
 //   whatever lives there by then.  This fault was met once, with a split whose prologue skipped a load.
 //   Re-definition behind the wait: the widening is ordinary VALU code on the loaded registers, so they are re-defined behind the counted
 //   wait (volatile asm keeps its order) and no conversion can be scheduled above the wait while the load is still in flight.
-template <typename F, typename TT, int RT, int DEPTH>
-__device__ __forceinline__ void gemm_skinny_w4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4, float *__restrict__ partial,
-                                               typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int n_splits) {
+//   Per-unit refill at 48 / 64 rows: a unit's registers are loaded again as soon as its MFMAs have read them, with that unit's share of
+//   the A staging, instead of all at the end of the phase (see k_gemm_skinny); the side data follows its last use.
+// F: the weight policy.  SIDE, GU: see THE SIDE; ws and `aux` = top_k belong to the expert sides, partial and `aux` = n_splits to the dense one.
+template <typename F, typename TT, int RT, int DEPTH, int SIDE, bool GU = false>
+__device__ __forceinline__ void gemm_stream_w4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
+                                               float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int aux) {
     typedef typename TT::elem E;
     typedef typename F::side_t side_t;
+    constexpr bool MOE = SIDE != SIDE_DENSE;
     constexpr int R = 16 * RT;
     constexpr int NT = 64 * GEMM_WAVES;
     constexpr int XV = (R * 32) / NT;              // 16-byte units per thread to stage one A chunk (as k_gemm_skinny)
@@ -1555,10 +1692,19 @@ __device__ __forceinline__ void gemm_skinny_w4(const typename TT::elem *__restri
     E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
 
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    // the side: the weight tile, the chunk range [c0, c1) and the source row of tile row r (expert sides: srow)
+    MoeSlot slot = {0, 0};
+    int srow[XV];
+    if constexpr (MOE) {
+        if (moe_side_idle(ws)) return;
+        slot = moe_side_open<R, SIDE == SIDE_WIDE>(ws);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < XV; i++) srow[i] = moe_side_row<GU>(i, aux);
+    }
     const int split = blockIdx.y;
-    const int c0 = (int)((long long)split * n_chunks / n_splits), c1 = (int)((long long)(split + 1) * n_chunks / n_splits);
-    const char *wtile = reinterpret_cast<const char *>(W4) + (size_t)blockIdx.x * n_chunks * WCH;
+    const int c0 = MOE ? 0 : (int)((long long)split * n_chunks / aux), c1 = MOE ? n_chunks : (int)((long long)(split + 1) * n_chunks / aux);
+    const char *wtile = reinterpret_cast<const char *>(W4) + (MOE ? (size_t)slot.expert * (N / GEMM_COLS) + blockIdx.x : (size_t)blockIdx.x) * n_chunks * WCH;
     const uint32_t wlane = (uint32_t)tid * 16, slane = F::slane(tid, w, n);
     const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
 
@@ -1567,9 +1713,9 @@ __device__ __forceinline__ void gemm_skinny_w4(const typename TT::elem *__restri
     for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
 
     u32x4 wr[DEPTH][2];
-    side_t ws[DEPTH];
+    side_t sd[DEPTH];
 #pragma unroll
-    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(ws[d]));
+    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(sd[d]));
     auto load_wj = [&](u32x4 (&dst)[2], int c, int j) {
         const char *p = wtile + (size_t)c * WCH;
         asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[j]) : "v"(wlane), "s"(p + WU * j) : "memory");
@@ -1577,7 +1723,7 @@ __device__ __forceinline__ void gemm_skinny_w4(const typename TT::elem *__restri
     auto load_s = [&](side_t &dst, int c) { F::load_side(dst, slane, wtile + (size_t)c * WCH + WS); };
     auto stage_xi = [&](int c, int buf, int i) {
         const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
-        const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
+        const E *src = A + (size_t)(MOE ? srow[i] : row) * K + (size_t)c * GEMM_KC + 8 * unit;
         E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
         asm volatile("" ::: "memory");
@@ -1623,43 +1769,34 @@ __device__ __forceinline__ void gemm_skinny_w4(const typename TT::elem *__restri
         }
         if (RT < 3 && c + DEPTH < c1) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
     };
-    if (c0 < c1) {
+    if (MOE || c0 < c1) {                          // (a dense split may be empty; an expert's stream is not)
 #pragma unroll
         for (int d = 0; d < DEPTH; d++)
-            if (c0 + d < c1) { load_w(wr[d], ws[d], c0 + d); stage_x(c0 + d, d); }
+            if (c0 + d < c1) { load_w(wr[d], sd[d], c0 + d); stage_x(c0 + d, d); }
         int buf = 0;
         for (int c = c0; c < c1; c += DEPTH) {
 #pragma unroll
             for (int d = 0; d < DEPTH; d++)
-                if (c + d < c1) { phase(wr[d], ws[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+                if (c + d < c1) { phase(wr[d], sd[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
         }
     }
-    // C layout of mfma_16x16: lane holds rows 4g + r of column n; block scales / scale and zero point went in with the widening, so ONE
-    // rounding and nothing else
-#pragma unroll
-    for (int mt = 0; mt < RT; mt++) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int m = 16 * mt + 4 * g + r;
-            const float v = acc[mt][r];
-            if (out) out[(size_t)m * N + n0 + n] = (E)v;
-            else __hip_atomic_store(&partial[((size_t)split * R + m) * N + n0 + n], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    // block scales / scale and zero point went in with the widening: the sums are final
+    if constexpr (MOE) moe_side_store<TT, RT, GU>(acc, slot.cnt, out, N, reinterpret_cast<float *>(gemm_lds), w, n, g);
+    else stream_store_dense<TT, RT>(acc, partial, out, N, w, n, g);
 }
 
 template <typename TT, int RT, int DEPTH>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_f4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4,
                                                                      float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
                                                                      int n_chunks, int n_splits) {
-    gemm_skinny_w4<W4Mx, TT, RT, DEPTH>(A, W4, partial, out, K, N, n_chunks, n_splits);
+    gemm_stream_w4<W4Mx, TT, RT, DEPTH, SIDE_DENSE>(A, W4, nullptr, partial, out, K, N, n_chunks, n_splits);
 }
 
 template <typename TT, int RT, int DEPTH>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i4(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4,
                                                                      float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
                                                                      int n_chunks, int n_splits) {
-    gemm_skinny_w4<W4Int, TT, RT, DEPTH>(A, W4, partial, out, K, N, n_chunks, n_splits);
+    gemm_stream_w4<W4Int, TT, RT, DEPTH, SIDE_DENSE>(A, W4, nullptr, partial, out, K, N, n_chunks, n_splits);
 }
 
 // row-major q [N][K/2] bytes + e8 [N][K/32] codes -> the packed blocks of k_gemm_skinny_f4; one thread moves one 16-byte unit and its scale
@@ -1710,23 +1847,17 @@ __global__ __launch_bounds__(256) void k_gemm_pack_i4(const uint4 *__restrict__ 
     }
 }
 
-// one launch of a 4-bit streaming kernel: dynamic LDS above 64 KiB is reserved once per kernel instantiation and device
-template <auto KERN, int LDS, typename... A>
-static hipError_t w4_launch(dim3 grid, hipStream_t st, A... args) {
-    if constexpr (LDS > 65536) {
-        static unsigned long long done = 0ull;                     // per-device (samd_common.h)
-        const hipError_t attr = samd_reserve_lds((const void *)KERN, LDS, &done);
-        if (attr != hipSuccess) return attr;
-    }
-    hipLaunchKernelGGL(KERN, grid, dim3(64 * GEMM_WAVES), LDS, st, args...);
-    return hipSuccess;
-}
+// the dense 4-bit kernels and their DEPTH row (16 / 32 / 48 / 64 rows), one for both formats
+template <typename F> struct SkinnyW4 {
+    static constexpr int depth(int rt) { return rt == 1 ? 8 : rt == 2 ? 4 : rt == 3 ? 5 : 3; }
+    template <typename TT, int RT> static constexpr auto kern() { return F::mx ? k_gemm_skinny_f4<TT, RT, depth(RT)> : k_gemm_skinny_i4<TT, RT, depth(RT)>; }
+};
 
-// samd_gemm_skinny_f4 / _i4: the checks, the grid and the row-tile / dtype dispatch with the DEPTH table of both formats
-template <typename F>
-static int gemm_skinny_w4_call(const char *fn, const void *d_A, const void *d_W4p, int rows_pad, int N, int K, int splits, float *d_partial, void *d_out, int dtype,
-                               void *stream) {
-    if (!d_A || !d_W4p || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS || N % GEMM_COLS != 0 ||
+// samd_gemm_skinny_f4 / _i4 / _i8: the checks, the grid and the row-tile / dtype dispatch; D names the format's kernels and its DEPTH row
+template <typename D>
+static int gemm_skinny_q_call(const char *fn, const void *d_A, const void *d_Wp, int rows_pad, int N, int K, int splits, float *d_partial, void *d_out, int dtype,
+                              void *stream) {
+    if (!d_A || !d_Wp || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS || N % GEMM_COLS != 0 ||
         K < GEMM_KC || K % GEMM_KC != 0 || splits < 1 || splits > K / GEMM_KC || (splits == 1 ? !d_out : !d_partial) || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
         samd_set_error("%s: unsupported shape (rows 16/32/48/64, N %% 128 == 0, K %% 256 == 0) or null pointer", fn); return SAMD_E_INVALID;
     }
@@ -1734,9 +1865,9 @@ static int gemm_skinny_w4_call(const char *fn, const void *d_A, const void *d_W4
     const hipStream_t st = (hipStream_t)stream;
     float *part = splits == 1 ? nullptr : d_partial;
     void *out = splits == 1 ? d_out : nullptr;
-#define GO(TT, RT, D) e = w4_launch<(F::mx ? k_gemm_skinny_f4<TT, RT, D> : k_gemm_skinny_i4<TT, RT, D>), (D + 1) * 16 * RT * GEMM_KC * 2>( \
-        grid, st, (const typename TT::elem *)d_A, (const unsigned char *)d_W4p, part, (typename TT::elem *)out, K, N, K / GEMM_KC, splits)
-#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1, 8); else if (rows_pad == 32) GO(TT, 2, 4); else if (rows_pad == 48) GO(TT, 3, 5); else GO(TT, 4, 3); } while (0)
+#define GO(TT, RT) e = stream_launch<D::template kern<TT, RT>(), stream_lds(D::depth(RT), RT)>( \
+        grid, st, (const typename TT::elem *)d_A, (const unsigned char *)d_Wp, part, (typename TT::elem *)out, K, N, K / GEMM_KC, splits)
+#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
     hipError_t e;
     if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
 #undef ROWS
@@ -1773,12 +1904,12 @@ int samd_gemm_pack_i4(const void *d_q, const void *d_z, const void *d_s, void *d
 
 int samd_gemm_skinny_f4(const void *d_A, const void *d_W4p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
                         int32_t dtype, void *stream) {
-    return gemm_skinny_w4_call<W4Mx>("samd_gemm_skinny_f4", d_A, d_W4p, rows_pad, N, K, splits, d_partial, d_out, dtype, stream);
+    return gemm_skinny_q_call<SkinnyW4<W4Mx>>("samd_gemm_skinny_f4", d_A, d_W4p, rows_pad, N, K, splits, d_partial, d_out, dtype, stream);
 }
 
 int samd_gemm_skinny_i4(const void *d_A, const void *d_W4p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
                         int32_t dtype, void *stream) {
-    return gemm_skinny_w4_call<W4Int>("samd_gemm_skinny_i4", d_A, d_W4p, rows_pad, N, K, splits, d_partial, d_out, dtype, stream);
+    return gemm_skinny_q_call<SkinnyW4<W4Int>>("samd_gemm_skinny_i4", d_A, d_W4p, rows_pad, N, K, splits, d_partial, d_out, dtype, stream);
 }
 
 }  // extern "C"
@@ -1846,11 +1977,15 @@ template <> struct I8Widen<GBF16> {
     }
 };
 
-template <typename TT, int RT, int DEPTH>
-__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i8(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8,
-                                                                     float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
-                                                                     int n_chunks, int n_splits) {
+// The INT8 streaming body, dense and expert: THE PIPELINE of gemm_stream_w4 (in-out destinations defined once, re-definition behind the
+// counted wait, per-k-block refill at 48 / 64 rows) over four code loads and one group-data load per chunk, and the same sides (THE SIDE).
+// A body of its own beside the 4-bit one because the PHASE differs, not the side: four code loads per chunk where the 4-bit stream has
+// two, one A unit pair per load where that one has two, another A-side unit order and another refill cadence.
+template <typename TT, int RT, int DEPTH, int SIDE, bool GU = false>
+__device__ __forceinline__ void gemm_stream_i8(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8, const int *__restrict__ ws,
+                                               float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int aux) {
     typedef typename TT::elem E;
+    constexpr bool MOE = SIDE != SIDE_DENSE;
     constexpr int R = 16 * RT;
     constexpr int NT = 64 * GEMM_WAVES;
     constexpr int XV = (R * 32) / NT;              // 16-byte units per thread to stage one A chunk (as k_gemm_skinny)
@@ -1861,10 +1996,19 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i8(const typ
     E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
 
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
+    // the side, as in gemm_stream_w4
+    MoeSlot slot = {0, 0};
+    int srow[XV];
+    if constexpr (MOE) {
+        if (moe_side_idle(ws)) return;
+        slot = moe_side_open<R, SIDE == SIDE_WIDE>(ws);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < XV; i++) srow[i] = moe_side_row<GU>(i, aux);
+    }
     const int split = blockIdx.y;
-    const int c0 = (int)((long long)split * n_chunks / n_splits), c1 = (int)((long long)(split + 1) * n_chunks / n_splits);
-    const char *wtile = reinterpret_cast<const char *>(W8) + (size_t)blockIdx.x * n_chunks * WCH;
+    const int c0 = MOE ? 0 : (int)((long long)split * n_chunks / aux), c1 = MOE ? n_chunks : (int)((long long)(split + 1) * n_chunks / aux);
+    const char *wtile = reinterpret_cast<const char *>(W8) + (MOE ? (size_t)slot.expert * (N / GEMM_COLS) + blockIdx.x : (size_t)blockIdx.x) * n_chunks * WCH;
     const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)(16 * w + n) * 8;
     const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
 
@@ -1872,11 +2016,10 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i8(const typ
 #pragma unroll
     for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
 
-    // the load destinations: one value each, defined once; every load is an in-out operand of it (see gemm_skinny_w4)
     u32x4 wr[DEPTH][4];
-    u32x2 ws[DEPTH];                               // the chunk's group data of this lane's row: {s0 | s1 << 16, zb0 | zb1 << 16}
+    u32x2 gs[DEPTH];                               // the chunk's group data of this lane's row: {s0 | s1 << 16, zb0 | zb1 << 16}
 #pragma unroll
-    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(wr[d][2]), "=v"(wr[d][3]), "=v"(ws[d]));
+    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(wr[d][2]), "=v"(wr[d][3]), "=v"(gs[d]));
     auto load_wb = [&](u32x4 (&dst)[4], int c, int b) {
         const char *p = wtile + (size_t)c * WCH;
         asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[b]) : "v"(wlane), "s"(p + WU * b) : "memory");
@@ -1887,7 +2030,7 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i8(const typ
     };
     auto stage_xi = [&](int c, int buf, int i) {
         const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
-        const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
+        const E *src = A + (size_t)(MOE ? srow[i] : row) * K + (size_t)c * GEMM_KC + 8 * unit;
         E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
         asm volatile("" ::: "memory");
@@ -1906,8 +2049,6 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i8(const typ
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
-        // the widening is ordinary VALU code on the loaded registers: re-define them here, behind the counted wait (volatile asm keeps its
-        // order), so that no conversion can be scheduled above the wait while the load is still in flight
         asm volatile("" : "+v"(cs) : : "memory");
         const u32x2 gd = cs;
 #pragma unroll
@@ -1931,28 +2072,27 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i8(const typ
         }
         if (RT < 3 && c + DEPTH < c1) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
     };
-    if (c0 < c1) {
+    if (MOE || c0 < c1) {
 #pragma unroll
         for (int d = 0; d < DEPTH; d++)
-            if (c0 + d < c1) { load_w(wr[d], ws[d], c0 + d); stage_x(c0 + d, d); }
+            if (c0 + d < c1) { load_w(wr[d], gs[d], c0 + d); stage_x(c0 + d, d); }
         int buf = 0;
         for (int c = c0; c < c1; c += DEPTH) {
 #pragma unroll
             for (int d = 0; d < DEPTH; d++)
-                if (c + d < c1) { phase(wr[d], ws[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
+                if (c + d < c1) { phase(wr[d], gs[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
         }
     }
-    // C layout of mfma_16x16: lane holds rows 4g + r of column n; scale and zero point went in with the widening, so ONE rounding and nothing else
-#pragma unroll
-    for (int mt = 0; mt < RT; mt++) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int m = 16 * mt + 4 * g + r;
-            const float v = acc[mt][r];
-            if (out) out[(size_t)m * N + n0 + n] = (E)v;
-            else __hip_atomic_store(&partial[((size_t)split * R + m) * N + n0 + n], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    // scale and zero point went in with the widening: the sums are final
+    if constexpr (MOE) moe_side_store<TT, RT, GU>(acc, slot.cnt, out, N, reinterpret_cast<float *>(gemm_lds), w, n, g);
+    else stream_store_dense<TT, RT>(acc, partial, out, N, w, n, g);
+}
+
+template <typename TT, int RT, int DEPTH>
+__global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_skinny_i8(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8,
+                                                                     float *__restrict__ partial, typename TT::elem *__restrict__ out, int K, int N,
+                                                                     int n_chunks, int n_splits) {
+    gemm_stream_i8<TT, RT, DEPTH, SIDE_DENSE>(A, W8, nullptr, partial, out, K, N, n_chunks, n_splits);
 }
 
 // row-major q [N][K] bytes, z [N][K/128] bytes, s [N][K/128] 16-bit words -> the packed blocks of k_gemm_skinny_i8; one thread moves one
@@ -1979,18 +2119,10 @@ __global__ __launch_bounds__(256) void k_gemm_pack_i8(const uint4 *__restrict__ 
     }
 }
 
-template <typename TT, int RT, int DEPTH>
-static hipError_t gemm_i8_launch(dim3 grid, hipStream_t st, const void *A, const void *W8, float *partial, void *out, int K, int N, int splits) {
-    constexpr int lds = (DEPTH + 1) * 16 * RT * GEMM_KC * 2;
-    if constexpr (lds > 65536) {
-        static unsigned long long done = 0ull;                     // per-device (samd_common.h)
-        const hipError_t attr = samd_reserve_lds((const void *)k_gemm_skinny_i8<TT, RT, DEPTH>, lds, &done);
-        if (attr != hipSuccess) return attr;
-    }
-    hipLaunchKernelGGL((k_gemm_skinny_i8<TT, RT, DEPTH>), grid, dim3(64 * GEMM_WAVES), lds, st, (const typename TT::elem *)A, (const unsigned char *)W8,
-                       partial, (typename TT::elem *)out, K, N, K / GEMM_KC, splits);
-    return hipSuccess;
-}
+struct SkinnyI8 {                                  // the dense INT8 kernel and its DEPTH row, for gemm_skinny_q_call
+    static constexpr int depth(int rt) { return rt == 4 ? 3 : 4; }
+    template <typename TT, int RT> static constexpr auto kern() { return k_gemm_skinny_i8<TT, RT, depth(RT)>; }
+};
 
 extern "C" {
 
@@ -2008,23 +2140,7 @@ int samd_gemm_pack_i8(const void *d_q, const void *d_z, const void *d_s, void *d
 
 int samd_gemm_skinny_i8(const void *d_A, const void *d_W8p, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial, void *d_out,
                         int32_t dtype, void *stream) {
-    if (!d_A || !d_W8p || (rows_pad != 16 && rows_pad != 32 && rows_pad != 48 && rows_pad != 64) || N < GEMM_COLS || N % GEMM_COLS != 0 ||
-        K < GEMM_KC || K % GEMM_KC != 0 || splits < 1 || splits > K / GEMM_KC || (splits == 1 ? !d_out : !d_partial) || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
-        samd_set_error("samd_gemm_skinny_i8: unsupported shape (rows 16/32/48/64, N %% 128 == 0, K %% 256 == 0) or null pointer"); return SAMD_E_INVALID;
-    }
-    const dim3 grid(N / GEMM_COLS, splits);
-    const hipStream_t st = (hipStream_t)stream;
-    float *part = splits == 1 ? nullptr : d_partial;
-    void *out = splits == 1 ? d_out : nullptr;
-#define GO(TT, RT, D) e = gemm_i8_launch<TT, RT, D>(grid, st, d_A, d_W8p, part, out, K, N, splits)
-#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1, 4); else if (rows_pad == 32) GO(TT, 2, 4); else if (rows_pad == 48) GO(TT, 3, 4); else GO(TT, 4, 3); } while (0)
-    hipError_t e;
-    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
-#undef ROWS
-#undef GO
-    if (e != hipSuccess) { samd_set_error("samd_gemm_skinny_i8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
-    LAUNCHCHK();
-    return SAMD_OK;
+    return gemm_skinny_q_call<SkinnyI8>("samd_gemm_skinny_i8", d_A, d_W8p, rows_pad, N, K, splits, d_partial, d_out, dtype, stream);
 }
 
 }  // extern "C"
@@ -2049,25 +2165,8 @@ int samd_gemm_skinny_i8(const void *d_A, const void *d_W8p, int32_t rows_pad, in
 //   ROUTING WORKSPACE (int32 words at the head of d_ws): [0] n_active; [16 + a] expert of active slot a; [272 + a] its entry count;
 //   [528 + 64 a + q] its q-th entry p = row * k + slot.  The down products y [rows * k][hidden] (model dtype) follow at MOE_WS_Y_OFF bytes.
 // Tile rows past an expert's count read its first entry's row again (their sums are not written); entries are < rows * k by construction.
+// (The MOE_WS_* / MOEW_WS_* word offsets sit with the expert side that reads them: THE SIDE, above the 4-bit streaming body.)
 // ================================================================================================
-#define MOE_MAX_E 256
-#define MOE_MAX_K 8
-#define MOE_MAX_ROWS 64
-#define MOE_WS_ACTIVE 16
-#define MOE_WS_COUNT (MOE_WS_ACTIVE + MOE_MAX_E)
-#define MOE_WS_LIST (MOE_WS_COUNT + MOE_MAX_E)
-#define MOE_WS_INTS (MOE_WS_LIST + MOE_MAX_E * MOE_MAX_ROWS)
-#define MOE_WS_Y_OFF (((MOE_WS_INTS * 4 + 255) / 256) * 256)
-// the wide calls' routing workspace (samd_moe_wide_*, at the end of the mixture-of-experts sections): fixed word offsets, so that the
-// expert GEMMs above read a tile record without knowing the shape
-#define MOEW_MAX_ROWS 4096
-#define MOEW_TILE_INTS 3
-#define MOEW_MAX_TILES (MOE_MAX_E + MOEW_MAX_ROWS * MOE_MAX_K / MOE_MAX_ROWS)
-#define MOEW_WS_ACTIVE 16
-#define MOEW_WS_COUNT (MOEW_WS_ACTIVE + MOE_MAX_E)
-#define MOEW_WS_OFFSET (MOEW_WS_COUNT + MOE_MAX_E)
-#define MOEW_WS_TILE (MOEW_WS_OFFSET + MOE_MAX_E)
-#define MOEW_WS_ENTRY (MOEW_WS_TILE + MOEW_TILE_INTS * MOEW_MAX_TILES)
 
 // Router logits stay in fp32 (HF's low-precision F.linear rounds them to the model dtype, which manufactures exact ties: a documented
 // difference).  Rows >= *d_n get index -1 and weight 0: they route nowhere.
@@ -2201,11 +2300,10 @@ __global__ __launch_bounds__(MOE_MAX_E) void k_moe_lists(const int *__restrict__
 }
 
 // One expert's share of a projection: k_gemm_skinny's stream (GEMM_KC chunks, 8 waves x 16 columns, hand-issued nt weight loads with counted
-// vmcnt, LDS-DMA'd A tiles with the XOR swizzle on the source address, two chunks in flight) with a gathered A tile.  The load destinations
-// are single values defined once and every load is an in-out operand of that value, as in k_gemm_skinny_f4.
-// GU: W = gate|up tiles (64 gate | 64 up columns), A = h, epilogue silu(gate) * up -> out[p][N / 2]; otherwise W = down tiles, A = act,
-// out[p][N] = the product rounded to the model dtype.
-template <typename TT, int RT, bool GU, bool WIDE = false>          // WIDE: a tile record of the wide workspace names the expert and its list
+// vmcnt, LDS-DMA'd A tiles with the XOR swizzle on the source address, two chunks in flight) behind the expert side (THE SIDE, above the
+// 4-bit streaming body), with in-out load destinations (THE PIPELINE, there).
+// GU: W = gate|up tiles (64 gate | 64 up columns), A = h, out = act; otherwise W = down tiles, A = act, out = y.
+template <typename TT, int RT, bool GU, bool WIDE = false>
 __device__ __forceinline__ void moe_expert_gemm(const typename TT::elem *__restrict__ A, const typename TT::elem *__restrict__ W, const int *__restrict__ ws,
                                                 typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
     typedef typename TT::elem E;
@@ -2218,25 +2316,16 @@ __device__ __forceinline__ void moe_expert_gemm(const typename TT::elem *__restr
     constexpr int PC = 8 + XV;                     // memory operations per thread and chunk
     extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
     E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
-    __shared__ int lst[MOE_MAX_ROWS];
 
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    const int slot_a = blockIdx.y;
-    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts (WIDE: of tiles; ws[0] = the tile count)
-    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
-    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
-    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
-    cnt = cnt > R ? R : cnt;
-    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
-    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
-    __syncthreads();
-    // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
+    if (moe_side_idle(ws)) return;
+    const MoeSlot slot = moe_side_open<R, WIDE>(ws);
     int srow[XV];
+    __syncthreads();
 #pragma unroll
-    for (int i = 0; i < XV; i++) { const int p = lst[(tid >> 5) + 16 * i]; srow[i] = GU ? p / top_k : p; }
+    for (int i = 0; i < XV; i++) srow[i] = moe_side_row<GU>(i, top_k);
 
-    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
-    const char *wtile = reinterpret_cast<const char *>(W) + ((size_t)expert * (N / GEMM_COLS) + blockIdx.x) * n_chunks * 65536;
+    const char *wtile = reinterpret_cast<const char *>(W) + ((size_t)slot.expert * (N / GEMM_COLS) + blockIdx.x) * n_chunks * 65536;
     const uint32_t wlane = (uint32_t)tid * 16;
     const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
 
@@ -2302,39 +2391,7 @@ __device__ __forceinline__ void moe_expert_gemm(const typename TT::elem *__restr
         for (int d = 0; d < DEPTH; d++)
             if (c + d < n_chunks) { phase(wr[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
     }
-    // C layout of mfma_16x16: lane holds rows 4g + r of column n
-    if constexpr (GU) {
-        float *ex = reinterpret_cast<float *>(gemm_lds);            // [R][64] up values; the A tiles are dead by now
-        __syncthreads();
-        if (w >= 4) {
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) ex[(16 * mt + 4 * g + r) * 64 + 16 * (w - 4) + n] = acc[mt][r];
-        }
-        __syncthreads();
-        if (w < 4) {
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int m = 16 * mt + 4 * g + r;
-                    if (m >= cnt) continue;
-                    // the roundings of HF's act_fn(gate) * up in the model dtype (same as k_gemm_skinny EPI 1 / k_silu_mul)
-                    const float gf = (float)(E)acc[mt][r], uf = (float)(E)ex[m * 64 + 16 * w + n];
-                    const E sv = (E)(gf / (1.f + __expf(-gf)));
-                    out[(size_t)lst[m] * (N / 2) + blockIdx.x * 64 + 16 * w + n] = (E)((float)sv * uf);
-                }
-        }
-    } else {
-#pragma unroll
-        for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int m = 16 * mt + 4 * g + r;
-                if (m < cnt) out[(size_t)lst[m] * N + n0 + n] = (E)acc[mt][r];
-            }
-    }
+    moe_side_store<TT, RT, GU>(acc, slot.cnt, out, N, reinterpret_cast<float *>(gemm_lds), w, n, g);
 }
 
 template <typename TT, int RT>
@@ -2396,31 +2453,10 @@ __global__ __launch_bounds__(256) void k_moe_pack(const uint4 *__restrict__ W, u
     out[ug] = W[e * per + (row * K + col) / 8];
 }
 
-template <typename TT, int RT, bool GU>
-static hipError_t moe_gemm_launch(dim3 grid, hipStream_t st, const void *A, const void *W, const int *ws, void *out, int K, int N, int top_k) {
-    typedef typename TT::elem E;
-    constexpr int lds = 3 * 16 * RT * GEMM_KC * 2;
-    if constexpr (GU) {
-        if constexpr (lds > 65536) {
-            static unsigned long long done = 0ull;
-            const hipError_t attr = samd_reserve_lds((const void *)k_moe_gate_up_silu<TT, RT>, lds, &done);
-            if (attr != hipSuccess) return attr;
-        }
-        hipLaunchKernelGGL((k_moe_gate_up_silu<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, K / GEMM_KC, top_k);
-    } else {
-        if constexpr (lds > 65536) {
-            static unsigned long long done = 0ull;
-            const hipError_t attr = samd_reserve_lds((const void *)k_moe_down<TT, RT>, lds, &done);
-            if (attr != hipSuccess) return attr;
-        }
-        hipLaunchKernelGGL((k_moe_down<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, K / GEMM_KC, top_k);
-    }
-    return hipSuccess;
-}
-
 template <bool GU>
 static hipError_t moe_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W, const int *ws, void *out, int K, int N, int top_k) {
-#define GO(TT, RT) return moe_gemm_launch<TT, RT, GU>(grid, st, A, W, ws, out, K, N, top_k)
+#define GO(TT, RT) return stream_launch<(GU ? k_moe_gate_up_silu<TT, RT> : k_moe_down<TT, RT>), stream_lds(2, RT)>( \
+        grid, st, (const typename TT::elem *)A, (const typename TT::elem *)W, ws, (typename TT::elem *)out, K, N, K / GEMM_KC, top_k)
 #define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
     if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
 #undef ROWS
@@ -2433,6 +2469,19 @@ static bool moe_shape_ok(int rows_pad, int hidden, int moe_inter, int n_experts,
            top_k <= n_experts && (dtype == SAMD_F16 || dtype == SAMD_BF16);
 }
 #define MOE_SHAPE_MSG "unsupported shape (rows 16/32/48/64, hidden %% 256 == 0, moe_intermediate %% 256 == 0, experts <= 256, top-k <= 8, f16/bf16) or null pointer"
+
+// the slot dimension of an expert launch's grid: the shape's upper bound of active experts
+static inline int moe_slot_bound(int rows_pad, int n_experts, int top_k) { return n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k; }
+
+// k_moe_combine over `rows` rows of the down products y, behind every format's down launch
+static void moe_combine_launch(int dtype, hipStream_t st, const void *y, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_out, int rows, int hidden,
+                               int top_k, int n_experts) {
+    const dim3 cgrid((hidden / 8 + 255) / 256, rows);
+    if (dtype == SAMD_F16)
+        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
+    else
+        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
+}
 
 extern "C" {
 
@@ -2493,7 +2542,7 @@ int samd_moe_gate_up_silu(const void *d_h, const void *d_Wgu, const void *d_ws, 
     if (!d_h || !d_Wgu || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
         samd_set_error("samd_moe_gate_up_silu: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
     }
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const int bound = moe_slot_bound(rows_pad, n_experts, top_k);
     const hipError_t e = moe_gemm_dispatch<true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu, (const int *)d_ws, d_act, hidden,
                                                  2 * moe_inter, top_k);
     if (e != hipSuccess) { samd_set_error("samd_moe_gate_up_silu: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
@@ -2508,15 +2557,11 @@ int samd_moe_down_combine(const void *d_act, const void *d_Wdown, const int32_t 
     }
     hipStream_t st = (hipStream_t)stream;
     void *y = (char *)d_ws + MOE_WS_Y_OFF;
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const int bound = moe_slot_bound(rows_pad, n_experts, top_k);
     const hipError_t e = moe_gemm_dispatch<false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown, (const int *)d_ws, y, moe_inter, hidden, top_k);
     if (e != hipSuccess) { samd_set_error("samd_moe_down_combine: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
     LAUNCHCHK();
-    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
-    if (dtype == SAMD_F16)
-        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
-    else
-        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
+    moe_combine_launch(dtype, st, y, d_topk_idx, d_topk_w, d_n, d_out, rows_pad, hidden, top_k, n_experts);
     LAUNCHCHK();
     return SAMD_OK;
 }
@@ -2524,14 +2569,13 @@ int samd_moe_down_combine(const void *d_act, const void *d_Wdown, const int32_t 
 }  // extern "C"
 
 // ================================================================================================
-// Mixture-of-experts MLP with 4-bit experts: the gathered expert GEMMs of moe_expert_gemm over gemm_skinny_w4's 4.25-bit weight stream,
-// ONE body (moe_w4_expert_gemm) for both formats with the weight-side policies W4Mx / W4Int.
+// Mixture-of-experts MLP with 4-bit experts: gemm_stream_w4, the dense calls' body with their weight policies W4Mx / W4Int, on the expert
+// side (THE SIDE, above that body) -- the kernels below are its SIDE_EXPERT instantiations at MoeW4Depth.
 //   samd_moe_gate_up_silu_f4 / _i4, samd_moe_down_combine_f4 / _i4: the fixed grid (N / 128, min(E, rows_pad * top_k)), the routing
-//   workspace, the early exit of slots >= ws[0], the list in static LDS, the gathered LDS-DMA A tile (srow), both epilogues (HF's roundings;
-//   rows >= cnt not stored) and k_moe_combine are those of the model-dtype calls; the weight side is gemm_skinny_w4's: 17 KiB (tile, chunk)
-//   blocks, two 16-byte nt element loads and one nt side-data load per lane and chunk, the widening behind the counted wait, the A-side unit
-//   order (16 j + 4 g + i) ^ n, fp32 accumulation in chunk order.  No split-K, no atomics: a row's output has the same bits whatever shares
-//   the launch.
+//   workspace and k_moe_combine are those of the model-dtype calls; the weight side is the dense one: 17 KiB (tile, chunk) blocks, two
+//   16-byte nt element loads and one nt side-data load per lane and chunk, the widening behind the counted wait, the A-side unit order
+//   (16 j + 4 g + i) ^ n, fp32 accumulation in chunk order.  No split-K, no atomics: a row's output has the same bits whatever shares the
+//   launch.
 //   PACKED LAYOUT, MXFP4: the experts laid end to end are ONE matrix of E * N rows in samd_gemm_pack_f4's layout; expert e's tile t is global
 //   tile e * N / 128 + t, at ((e * N / 128 + t) * K / 256 + c) * 17408 bytes for chunk c.  gate|up: packed row 128 t + r of an expert is its
 //   gate row 64 t + r for r < 64 and its up row I + 64 t + r - 64 otherwise (samd_hip/moe.py permutes q and e8 before packing; MX blocks run
@@ -2549,227 +2593,87 @@ int samd_moe_down_combine(const void *d_act, const void *d_Wdown, const int32_t 
 //   never fit).  INT4's group data costs one VGPR per chunk in flight more than MXFP4's scales (8 more at 16 rows) and every instantiation
 //   still compiles without scratch (tests/test_moe_int4_cpu.py reads it from the code object's metadata).  An expert's stream is often
 //   SHORTER than the depth (3 chunks for down at moe_inter 768, 1 at 256): the skipped prologue loads leave their in-out destination
-//   registers as they are (see gemm_skinny_w4).  Not swept on a GPU; profiles/moe_experts_mxfp4.md and profiles/moe_experts_int4.md have
+//   registers as they are (THE PIPELINE, at gemm_stream_w4).  Not swept on a GPU; profiles/moe_experts_mxfp4.md and profiles/moe_experts_int4.md have
 //   the timings.
 // ================================================================================================
 template <int RT> struct MoeW4Depth { static constexpr int value = RT == 1 ? 8 : RT == 3 ? 2 : 3; };
-
-template <typename F, typename TT, int RT, bool GU, bool WIDE>      // WIDE: a tile record of the wide workspace names the expert and its list
-__device__ __forceinline__ void moe_w4_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
-                                                   typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
-    typedef typename TT::elem E;
-    typedef typename F::side_t side_t;
-    constexpr int DEPTH = MoeW4Depth<RT>::value;
-    constexpr int R = 16 * RT;
-    constexpr int NT = 64 * GEMM_WAVES;
-    constexpr int XV = (R * 32) / NT;
-    constexpr int NB = DEPTH + 1;
-    constexpr int PC = 3 + XV;                     // memory operations per thread and chunk: 2 element loads + 1 side-data load + the A staging
-    constexpr size_t WCH = 17408, WU = 8192, WS = 16384;   // bytes of one (tile, chunk) block; of one j row inside it; offset of its side data
-    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
-    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
-    __shared__ int lst[MOE_MAX_ROWS];
-
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    const int slot_a = blockIdx.y;
-    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts (WIDE: of tiles; ws[0] = the tile count)
-    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
-    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
-    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
-    cnt = cnt > R ? R : cnt;
-    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
-    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
-    __syncthreads();
-    // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
-    int srow[XV];
-#pragma unroll
-    for (int i = 0; i < XV; i++) { const int p = lst[(tid >> 5) + 16 * i]; srow[i] = GU ? p / top_k : p; }
-
-    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
-    const char *wtile = reinterpret_cast<const char *>(W4) + ((size_t)expert * (N / GEMM_COLS) + blockIdx.x) * n_chunks * WCH;
-    const uint32_t wlane = (uint32_t)tid * 16, slane = F::slane(tid, w, n);
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
-
-    floatx4 acc[RT];
-#pragma unroll
-    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    // the pipeline of gemm_skinny_w4, statement for statement: in-out load destinations defined once, re-defined behind the counted wait
-    u32x4 wr[DEPTH][2];
-    side_t sd[DEPTH];
-#pragma unroll
-    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(sd[d]));
-    auto load_wj = [&](u32x4 (&dst)[2], int c, int j) {
-        const char *p = wtile + (size_t)c * WCH;
-        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[j]) : "v"(wlane), "s"(p + WU * j) : "memory");
-    };
-    auto load_s = [&](side_t &dst, int c) { F::load_side(dst, slane, wtile + (size_t)c * WCH + WS); };
-    auto stage_xi = [&](int c, int buf, int i) {
-        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
-        const E *src = A + (size_t)srow[i] * K + (size_t)c * GEMM_KC + 8 * unit;
-        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
-        asm volatile("" ::: "memory");
-    };
-    auto load_w = [&](u32x4 (&dst)[2], side_t &sdst, int c) {
-        load_wj(dst, c, 0); load_wj(dst, c, 1); load_s(sdst, c);
-    };
-    auto stage_x = [&](int c, int buf) {
-#pragma unroll
-        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
-    };
-    auto phase = [&](u32x4 (&cur)[2], side_t &cs, int c, int buf) {
-        gemm_wait_younger_deep<DEPTH, PC>(n_chunks - 1 - c);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
-        asm volatile("" : "+v"(cs) : : "memory");
-        const side_t side = cs;
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            asm volatile("" : "+v"(cur[j]) : : "memory");
-            const auto grp = F::template group<TT>(side, j);
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int u = 16 * j + 4 * g + 2 * h;
-                const uint32_t a0 = xbase + (uint32_t)(u ^ n) * 16, a1 = xbase + (uint32_t)((u + 1) ^ n) * 16;
-                u32x4 r[RT][2];
-                gemm_read_a2<RT>(r, a0, a1);
-                const auto lo = F::template cvt<TT>(cur[j][2 * h], grp), hi = F::template cvt<TT>(cur[j][2 * h + 1], grp);
-#pragma unroll
-                for (int mt = 0; mt < RT; mt++) {
-                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
-                    acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, acc[mt]);
-                }
-            }
-            if (RT >= 3 && c + DEPTH < n_chunks) {             // 48 / 64 rows: refill per unit (see k_gemm_skinny)
-                load_wj(cur, c + DEPTH, j);
-                if (j == 1) load_s(cs, c + DEPTH);
-#pragma unroll
-                for (int i = 2 * j; i < 2 * j + 2; i++)
-                    if (i < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, i);
-            }
-        }
-        if (RT < 3 && c + DEPTH < n_chunks) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
-    };
-#pragma unroll
-    for (int d = 0; d < DEPTH; d++)
-        if (d < n_chunks) { load_w(wr[d], sd[d], d); stage_x(d, d); }
-    int buf = 0;
-    for (int c = 0; c < n_chunks; c += DEPTH) {
-#pragma unroll
-        for (int d = 0; d < DEPTH; d++)
-            if (c + d < n_chunks) { phase(wr[d], sd[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
-    }
-    // C layout of mfma_16x16: lane holds rows 4g + r of column n; block scales / scale and zero point went in with the widening
-    if constexpr (GU) {
-        float *ex = reinterpret_cast<float *>(gemm_lds);            // [R][64] up values; the A tiles are dead by now
-        __syncthreads();
-        if (w >= 4) {
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) ex[(16 * mt + 4 * g + r) * 64 + 16 * (w - 4) + n] = acc[mt][r];
-        }
-        __syncthreads();
-        if (w < 4) {
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int m = 16 * mt + 4 * g + r;
-                    if (m >= cnt) continue;
-                    // the roundings of HF's act_fn(gate) * up in the model dtype (same as moe_expert_gemm)
-                    const float gf = (float)(E)acc[mt][r], uf = (float)(E)ex[m * 64 + 16 * w + n];
-                    const E sv = (E)(gf / (1.f + __expf(-gf)));
-                    out[(size_t)lst[m] * (N / 2) + blockIdx.x * 64 + 16 * w + n] = (E)((float)sv * uf);
-                }
-        }
-    } else {
-#pragma unroll
-        for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int m = 16 * mt + 4 * g + r;
-                if (m < cnt) out[(size_t)lst[m] * N + n0 + n] = (E)acc[mt][r];
-            }
-    }
-}
 
 template <typename TT, int RT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe4_gate_up_silu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4,
                                                                          const int *__restrict__ ws, typename TT::elem *__restrict__ act,
                                                                          int K, int N, int n_chunks, int top_k) {
-    moe_w4_expert_gemm<W4Mx, TT, RT, true, false>(h, W4, ws, act, K, N, n_chunks, top_k);
+    gemm_stream_w4<W4Mx, TT, RT, MoeW4Depth<RT>::value, SIDE_EXPERT, true>(h, W4, ws, nullptr, act, K, N, n_chunks, top_k);
 }
 
 template <typename TT, int RT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe4_down(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4,
                                                                  const int *__restrict__ ws, typename TT::elem *__restrict__ y,
                                                                  int K, int N, int n_chunks, int top_k) {
-    moe_w4_expert_gemm<W4Mx, TT, RT, false, false>(act, W4, ws, y, K, N, n_chunks, top_k);
+    gemm_stream_w4<W4Mx, TT, RT, MoeW4Depth<RT>::value, SIDE_EXPERT, false>(act, W4, ws, nullptr, y, K, N, n_chunks, top_k);
 }
 
 template <typename TT, int RT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i4_gate_up_silu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4,
                                                                            const int *__restrict__ ws, typename TT::elem *__restrict__ act,
                                                                            int K, int N, int n_chunks, int top_k) {
-    moe_w4_expert_gemm<W4Int, TT, RT, true, false>(h, W4, ws, act, K, N, n_chunks, top_k);
+    gemm_stream_w4<W4Int, TT, RT, MoeW4Depth<RT>::value, SIDE_EXPERT, true>(h, W4, ws, nullptr, act, K, N, n_chunks, top_k);
 }
 
 template <typename TT, int RT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i4_down(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4,
                                                                    const int *__restrict__ ws, typename TT::elem *__restrict__ y,
                                                                    int K, int N, int n_chunks, int top_k) {
-    moe_w4_expert_gemm<W4Int, TT, RT, false, false>(act, W4, ws, y, K, N, n_chunks, top_k);
+    gemm_stream_w4<W4Int, TT, RT, MoeW4Depth<RT>::value, SIDE_EXPERT, false>(act, W4, ws, nullptr, y, K, N, n_chunks, top_k);
 }
 
-template <typename F, typename TT, int RT, bool GU>
-static hipError_t moe_w4_gemm_launch(dim3 grid, hipStream_t st, const void *A, const void *W4, const int *ws, void *out, int K, int N, int top_k) {
-    typedef typename TT::elem E;
-    constexpr auto kern = F::mx ? (GU ? k_moe4_gate_up_silu<TT, RT> : k_moe4_down<TT, RT>) : (GU ? k_moe_i4_gate_up_silu<TT, RT> : k_moe_i4_down<TT, RT>);
-    return w4_launch<kern, (MoeW4Depth<RT>::value + 1) * 16 * RT * GEMM_KC * 2>(grid, st, (const E *)A, (const unsigned char *)W4, ws, (E *)out, K, N, K / GEMM_KC, top_k);
-}
+// the 4-bit expert kernels and their DEPTH table, for the host-side templates below (MoeI8 is the INT8 one)
+template <typename F> struct MoeW4 {
+    template <int RT> static constexpr int depth = MoeW4Depth<RT>::value;
+    template <typename TT, int RT, bool GU> static constexpr auto kern() {
+        return F::mx ? (GU ? k_moe4_gate_up_silu<TT, RT> : k_moe4_down<TT, RT>) : (GU ? k_moe_i4_gate_up_silu<TT, RT> : k_moe_i4_down<TT, RT>);
+    }
+};
 
-template <typename F, bool GU>
-static hipError_t moe_w4_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W4, const int *ws, void *out, int K, int N, int top_k) {
-#define GO(TT, RT) return moe_w4_gemm_launch<F, TT, RT, GU>(grid, st, A, W4, ws, out, K, N, top_k)
+// X: a quantised expert format whose kernels take (A, packed W, ws, out, K, N, chunks, top_k) -- MoeW4<W4Mx>, MoeW4<W4Int>, MoeI8.  The
+// model-dtype and block-scaled FP8 calls stay apart: the first casts W to the model dtype, the second adds a scale table, a bound on K
+// and a message of its own.
+template <typename X, bool GU>
+static hipError_t moe_q_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W, const int *ws, void *out, int K, int N, int top_k) {
+#define GO(TT, RT) return stream_launch<X::template kern<TT, RT, GU>(), stream_lds(X::template depth<RT>, RT)>( \
+        grid, st, (const typename TT::elem *)A, (const unsigned char *)W, ws, (typename TT::elem *)out, K, N, K / GEMM_KC, top_k)
 #define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
     if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
 #undef ROWS
 #undef GO
 }
 
-template <typename F>
-static int moe_w4_gate_up_silu(const char *fn, const void *d_h, const void *d_Wgu4, const void *d_ws, int rows_pad, int hidden, int moe_inter, int n_experts, int top_k,
-                               void *d_act, int dtype, void *stream) {
-    if (!d_h || !d_Wgu4 || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
+template <typename X>
+static int moe_q_gate_up_silu(const char *fn, const void *d_h, const void *d_Wgu, const void *d_ws, int rows_pad, int hidden, int moe_inter, int n_experts, int top_k,
+                              void *d_act, int dtype, void *stream) {
+    if (!d_h || !d_Wgu || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
         samd_set_error("%s: " MOE_SHAPE_MSG, fn); return SAMD_E_INVALID;
     }
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
-    const hipError_t e = moe_w4_gemm_dispatch<F, true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu4, (const int *)d_ws, d_act,
-                                                       hidden, 2 * moe_inter, top_k);
+    const int bound = moe_slot_bound(rows_pad, n_experts, top_k);
+    const hipError_t e = moe_q_gemm_dispatch<X, true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu, (const int *)d_ws, d_act,
+                                                      hidden, 2 * moe_inter, top_k);
     if (e != hipSuccess) { samd_set_error("%s: %s", fn, hipGetErrorString(e)); return SAMD_E_HIP; }
     LAUNCHCHK();
     return SAMD_OK;
 }
 
-template <typename F>
-static int moe_w4_down_combine(const char *fn, const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
-                               int rows_pad, int hidden, int moe_inter, int n_experts, int top_k, void *d_out, int dtype, void *stream) {
-    if (!d_act || !d_Wdown4 || !d_topk_idx || !d_topk_w || !d_n || !d_ws || !d_out || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
+template <typename X>
+static int moe_q_down_combine(const char *fn, const void *d_act, const void *d_Wdown, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
+                              int rows_pad, int hidden, int moe_inter, int n_experts, int top_k, void *d_out, int dtype, void *stream) {
+    if (!d_act || !d_Wdown || !d_topk_idx || !d_topk_w || !d_n || !d_ws || !d_out || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
         samd_set_error("%s: " MOE_SHAPE_MSG, fn); return SAMD_E_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
     void *y = (char *)d_ws + MOE_WS_Y_OFF;
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
-    const hipError_t e = moe_w4_gemm_dispatch<F, false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown4, (const int *)d_ws, y, moe_inter, hidden, top_k);
+    const int bound = moe_slot_bound(rows_pad, n_experts, top_k);
+    const hipError_t e = moe_q_gemm_dispatch<X, false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown, (const int *)d_ws, y, moe_inter, hidden, top_k);
     if (e != hipSuccess) { samd_set_error("%s: %s", fn, hipGetErrorString(e)); return SAMD_E_HIP; }
     LAUNCHCHK();
-    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
-    if (dtype == SAMD_F16)
-        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
-    else
-        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
+    moe_combine_launch(dtype, st, y, d_topk_idx, d_topk_w, d_n, d_out, rows_pad, hidden, top_k, n_experts);
     LAUNCHCHK();
     return SAMD_OK;
 }
@@ -2778,40 +2682,39 @@ extern "C" {
 
 int samd_moe_gate_up_silu_f4(const void *d_h, const void *d_Wgu4, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
                              int32_t top_k, void *d_act, int32_t dtype, void *stream) {
-    return moe_w4_gate_up_silu<W4Mx>("samd_moe_gate_up_silu_f4", d_h, d_Wgu4, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_act, dtype, stream);
+    return moe_q_gate_up_silu<MoeW4<W4Mx>>("samd_moe_gate_up_silu_f4", d_h, d_Wgu4, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_act, dtype, stream);
 }
 
 int samd_moe_down_combine_f4(const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
                              int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream) {
-    return moe_w4_down_combine<W4Mx>("samd_moe_down_combine_f4", d_act, d_Wdown4, d_topk_idx, d_topk_w, d_n, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_out, dtype,
+    return moe_q_down_combine<MoeW4<W4Mx>>("samd_moe_down_combine_f4", d_act, d_Wdown4, d_topk_idx, d_topk_w, d_n, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_out, dtype,
                                      stream);
 }
 
 int samd_moe_gate_up_silu_i4(const void *d_h, const void *d_Wgu4, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
                              int32_t top_k, void *d_act, int32_t dtype, void *stream) {
-    return moe_w4_gate_up_silu<W4Int>("samd_moe_gate_up_silu_i4", d_h, d_Wgu4, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_act, dtype, stream);
+    return moe_q_gate_up_silu<MoeW4<W4Int>>("samd_moe_gate_up_silu_i4", d_h, d_Wgu4, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_act, dtype, stream);
 }
 
 int samd_moe_down_combine_i4(const void *d_act, const void *d_Wdown4, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
                              int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream) {
-    return moe_w4_down_combine<W4Int>("samd_moe_down_combine_i4", d_act, d_Wdown4, d_topk_idx, d_topk_w, d_n, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_out, dtype,
+    return moe_q_down_combine<MoeW4<W4Int>>("samd_moe_down_combine_i4", d_act, d_Wdown4, d_topk_idx, d_topk_w, d_n, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_out, dtype,
                                       stream);
 }
 
 }  // extern "C"
 
 // ================================================================================================
-// Mixture-of-experts MLP with INT8 experts (GPTQ: unsigned 8-bit codes, one scale and one 8-bit zero point per 128 elements along k): the
-// gathered expert GEMMs of moe_expert_gemm over k_gemm_skinny_i8's 8.25-bit weight stream.
-//   samd_moe_gate_up_silu_i8 / samd_moe_down_combine_i8: the expert side is moe_w4_expert_gemm's, statement for statement -- the fixed grid
-//   (N / 128, min(E, rows_pad * top_k)), the routing workspace, the early exit of slots >= ws[0], the list in static LDS, the gathered
-//   LDS-DMA A tile (srow), both epilogues (HF's roundings; rows >= cnt not stored) and k_moe_combine.  The weight side is k_gemm_skinny_i8's:
+// Mixture-of-experts MLP with INT8 experts (GPTQ: unsigned 8-bit codes, one scale and one 8-bit zero point per 128 elements along k):
+// gemm_stream_i8, k_gemm_skinny_i8's body, on the expert side (THE SIDE, above the 4-bit streaming body) -- the kernels below are its
+// SIDE_EXPERT / SIDE_WIDE instantiations at MoeI8Depth.
+//   samd_moe_gate_up_silu_i8 / samd_moe_down_combine_i8: the fixed grid (N / 128, min(E, rows_pad * top_k)), the routing workspace and
+//   k_moe_combine are those of the model-dtype calls, through the host templates of the 4-bit calls.  The weight side is the dense one:
 //   33 KiB (tile, chunk) blocks, four 16-byte nt code loads and one 8-byte nt group-data load per lane and chunk with in-out destinations,
 //   I8Widen behind the counted wait (W = rne_dtype((q - z) * s), ONE rounding), the A-side unit order (8 b + 2 g) ^ n, fp32 accumulation in
 //   chunk order.  No split-K, no atomics: a row's output has the same bits whatever shares the launch.
-//   A body of its own, not a policy of moe_w4_expert_gemm: the 8-bit stream has four code loads per chunk where the 4-bit one has two, one
-//   A unit pair per load where that one has two, another A-side unit order and another refill cadence at 48 / 64 rows; a policy would have
-//   to carry the whole phase.
+//   What the 4-bit and the 8-bit kernels share is the side, and that is written once; the phase stays with the format (gemm_stream_i8 says
+//   how the two differ), so there are two stream bodies and no 4-bit / 8-bit policy.
 //   PACKED LAYOUT: the experts laid end to end are ONE matrix of E * N rows in samd_gemm_pack_i8's layout (the pack call with N := E * N);
 //   expert e's tile t is global tile e * N / 128 + t, at ((e * N / 128 + t) * K / 256 + c) * 33792 bytes for chunk c.  gate|up: the rows are
 //   permuted before packing as for INT4 (samd_hip/moe.py: gate_up_tile_order; groups run along k, so whole rows move with their zero points
@@ -2826,220 +2729,54 @@ int samd_moe_down_combine_i4(const void *d_act, const void *d_Wdown4, const int3
 //   MI355X against 3 at one workgroup per CU (4 x 32 = 128 KiB, 146 VGPRs), the 4-bit and FP8 tables' choice: 170 against 207 us (bf16)
 //   and 164 against 189 us (fp16) for the three-call layer at A3B geometry (profiles/moe_experts_int8.md); the other entries were not
 //   swept.  An expert's stream is often SHORTER than the depth (3 chunks for down at moe_inter 768, 1 at 256): the skipped prologue loads
-//   leave their in-out destination registers as they are (see gemm_skinny_w4).
+//   leave their in-out destination registers as they are (THE PIPELINE, at gemm_stream_w4).
 //   The one-pass-prefill forms are the WIDE instantiations at the 64-row tile (k_moew_i8_gu / k_moew_i8_dn, expert_format code 5: 4 stays
 //   unassigned, callers pin it as an unknown code).
 // ================================================================================================
 template <int RT> struct MoeI8Depth { static constexpr int value = RT == 1 ? 4 : RT == 3 ? 2 : RT == 4 ? 1 : 3; };
 
-template <typename TT, int RT, bool GU, bool WIDE>      // WIDE: a tile record of the wide workspace names the expert and its list
-__device__ __forceinline__ void moe_i8_expert_gemm(const typename TT::elem *__restrict__ A, const unsigned char *__restrict__ W8, const int *__restrict__ ws,
-                                                   typename TT::elem *__restrict__ out, int K, int N, int n_chunks, int top_k) {
-    typedef typename TT::elem E;
-    constexpr int DEPTH = MoeI8Depth<RT>::value;
-    constexpr int R = 16 * RT;
-    constexpr int NT = 64 * GEMM_WAVES;
-    constexpr int XV = (R * 32) / NT;
-    constexpr int NB = DEPTH + 1;
-    constexpr int PC = 5 + XV;                     // memory operations per thread and chunk: 4 code loads + 1 group-data load + the A staging
-    constexpr size_t WCH = 33792, WU = 8192, WS = 32768;   // bytes of one (tile, chunk) block; of one b row inside it; offset of its group data
-    extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
-    E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
-    __shared__ int lst[MOE_MAX_ROWS];
-
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    const int slot_a = blockIdx.y;
-    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts (WIDE: of tiles; ws[0] = the tile count)
-    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
-    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
-    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
-    cnt = cnt > R ? R : cnt;
-    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
-    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
-    __syncthreads();
-    // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
-    int srow[XV];
-#pragma unroll
-    for (int i = 0; i < XV; i++) { const int p = lst[(tid >> 5) + 16 * i]; srow[i] = GU ? p / top_k : p; }
-
-    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
-    const char *wtile = reinterpret_cast<const char *>(W8) + ((size_t)expert * (N / GEMM_COLS) + blockIdx.x) * n_chunks * WCH;
-    const uint32_t wlane = (uint32_t)tid * 16, slane = (uint32_t)(16 * w + n) * 8;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
-
-    floatx4 acc[RT];
-#pragma unroll
-    for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    // the pipeline of k_gemm_skinny_i8, statement for statement: in-out load destinations defined once, re-defined behind the counted wait
-    u32x4 wr[DEPTH][4];
-    u32x2 gs[DEPTH];                               // the chunk's group data of this lane's row: {s0 | s1 << 16, zb0 | zb1 << 16}
-#pragma unroll
-    for (int d = 0; d < DEPTH; d++) asm volatile("" : "=v"(wr[d][0]), "=v"(wr[d][1]), "=v"(wr[d][2]), "=v"(wr[d][3]), "=v"(gs[d]));
-    auto load_wb = [&](u32x4 (&dst)[4], int c, int b) {
-        const char *p = wtile + (size_t)c * WCH;
-        asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst[b]) : "v"(wlane), "s"(p + WU * b) : "memory");
-    };
-    auto load_s = [&](u32x2 &dst, int c) {
-        const char *p = wtile + (size_t)c * WCH + WS;
-        asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "+v"(dst) : "v"(slane), "s"(p) : "memory");
-    };
-    auto stage_xi = [&](int c, int buf, int i) {
-        const int slot = tid + NT * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
-        const E *src = A + (size_t)srow[i] * K + (size_t)c * GEMM_KC + 8 * unit;
-        E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
-        asm volatile("" ::: "memory");
-    };
-    auto load_w = [&](u32x4 (&dst)[4], u32x2 &sdst, int c) {
-#pragma unroll
-        for (int b = 0; b < 4; b++) load_wb(dst, c, b);
-        load_s(sdst, c);
-    };
-    auto stage_x = [&](int c, int buf) {
-#pragma unroll
-        for (int i = 0; i < XV; i++) stage_xi(c, buf, i);
-    };
-    auto phase = [&](u32x4 (&cur)[4], u32x2 &cs, int c, int buf) {
-        gemm_wait_younger_deep<DEPTH, PC>(n_chunks - 1 - c);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const uint32_t xbase = lds_base + (uint32_t)buf * (R * GEMM_KC * 2) + (uint32_t)n * (GEMM_KC * 2);
-        asm volatile("" : "+v"(cs) : : "memory");
-        const u32x2 gd = cs;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const uint32_t a0 = xbase + (uint32_t)((8 * b + 2 * g) ^ n) * 16, a1 = xbase + (uint32_t)((8 * b + 2 * g + 1) ^ n) * 16;
-            u32x4 r[RT][2];
-            gemm_read_a2<RT>(r, a0, a1);
-            asm volatile("" : "+v"(cur[b]) : : "memory");
-            const auto grp = I8Widen<TT>::group(gd, b >> 1);
-            const auto lo = I8Widen<TT>::cvt(cur[b][0], cur[b][1], grp), hi = I8Widen<TT>::cvt(cur[b][2], cur[b][3], grp);
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++) {
-                acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][0]), lo, acc[mt]);
-                acc[mt] = TT::mfma(__builtin_bit_cast(typename TT::vec8, r[mt][1]), hi, acc[mt]);
-            }
-            if (RT >= 3 && c + DEPTH < n_chunks) {             // 48 / 64 rows: refill per k block (see k_gemm_skinny)
-                load_wb(cur, c + DEPTH, b);
-                if (b < XV) stage_xi(c + DEPTH, buf == 0 ? NB - 1 : buf - 1, b);
-                if (b == 3) load_s(cs, c + DEPTH);             // (after the group data's last use)
-            }
-        }
-        if (RT < 3 && c + DEPTH < n_chunks) { load_w(cur, cs, c + DEPTH); stage_x(c + DEPTH, buf == 0 ? NB - 1 : buf - 1); }
-    };
-#pragma unroll
-    for (int d = 0; d < DEPTH; d++)
-        if (d < n_chunks) { load_w(wr[d], gs[d], d); stage_x(d, d); }
-    int buf = 0;
-    for (int c = 0; c < n_chunks; c += DEPTH) {
-#pragma unroll
-        for (int d = 0; d < DEPTH; d++)
-            if (c + d < n_chunks) { phase(wr[d], gs[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
-    }
-    // C layout of mfma_16x16: lane holds rows 4g + r of column n; scale and zero point went in with the widening
-    if constexpr (GU) {
-        float *ex = reinterpret_cast<float *>(gemm_lds);            // [R][64] up values; the A tiles are dead by now
-        __syncthreads();
-        if (w >= 4) {
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) ex[(16 * mt + 4 * g + r) * 64 + 16 * (w - 4) + n] = acc[mt][r];
-        }
-        __syncthreads();
-        if (w < 4) {
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int m = 16 * mt + 4 * g + r;
-                    if (m >= cnt) continue;
-                    // the roundings of HF's act_fn(gate) * up in the model dtype (same as moe_expert_gemm)
-                    const float gf = (float)(E)acc[mt][r], uf = (float)(E)ex[m * 64 + 16 * w + n];
-                    const E sv = (E)(gf / (1.f + __expf(-gf)));
-                    out[(size_t)lst[m] * (N / 2) + blockIdx.x * 64 + 16 * w + n] = (E)((float)sv * uf);
-                }
-        }
-    } else {
-#pragma unroll
-        for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int m = 16 * mt + 4 * g + r;
-                if (m < cnt) out[(size_t)lst[m] * N + n0 + n] = (E)acc[mt][r];
-            }
-    }
-}
-
 template <typename TT, int RT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i8_gate_up_silu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W8,
                                                                            const int *__restrict__ ws, typename TT::elem *__restrict__ act,
                                                                            int K, int N, int n_chunks, int top_k) {
-    moe_i8_expert_gemm<TT, RT, true, false>(h, W8, ws, act, K, N, n_chunks, top_k);
+    gemm_stream_i8<TT, RT, MoeI8Depth<RT>::value, SIDE_EXPERT, true>(h, W8, ws, nullptr, act, K, N, n_chunks, top_k);
 }
 
 template <typename TT, int RT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moe_i8_down(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W8,
                                                                    const int *__restrict__ ws, typename TT::elem *__restrict__ y,
                                                                    int K, int N, int n_chunks, int top_k) {
-    moe_i8_expert_gemm<TT, RT, false, false>(act, W8, ws, y, K, N, n_chunks, top_k);
+    gemm_stream_i8<TT, RT, MoeI8Depth<RT>::value, SIDE_EXPERT, false>(act, W8, ws, nullptr, y, K, N, n_chunks, top_k);
 }
 
 // the one-pass-prefill forms (samd_moe_wide_*, expert_format 5): the 64-row tile over the wide workspace's tile records
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moew_i8_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W8, const int *__restrict__ ws,
                                                                   typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
-    moe_i8_expert_gemm<TT, 4, true, true>(h, W8, ws, act, K, N, n_chunks, top_k);
+    gemm_stream_i8<TT, 4, MoeI8Depth<4>::value, SIDE_WIDE, true>(h, W8, ws, nullptr, act, K, N, n_chunks, top_k);
 }
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_moew_i8_dn(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W8, const int *__restrict__ ws,
                                                                   typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
-    moe_i8_expert_gemm<TT, 4, false, true>(act, W8, ws, y, K, N, n_chunks, top_k);
+    gemm_stream_i8<TT, 4, MoeI8Depth<4>::value, SIDE_WIDE, false>(act, W8, ws, nullptr, y, K, N, n_chunks, top_k);
 }
 
-template <bool GU>
-static hipError_t moe_i8_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W8, const int *ws, void *out, int K, int N, int top_k) {
-#define GO(TT, RT) return w4_launch<(GU ? k_moe_i8_gate_up_silu<TT, RT> : k_moe_i8_down<TT, RT>), (MoeI8Depth<RT>::value + 1) * 16 * RT * GEMM_KC * 2>( \
-        grid, st, (const typename TT::elem *)A, (const unsigned char *)W8, ws, (typename TT::elem *)out, K, N, K / GEMM_KC, top_k)
-#define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
-    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
-#undef ROWS
-#undef GO
-}
+struct MoeI8 {                                     // the INT8 expert kernels and their DEPTH table, for moe_q_gate_up_silu / moe_q_down_combine
+    template <int RT> static constexpr int depth = MoeI8Depth<RT>::value;
+    template <typename TT, int RT, bool GU> static constexpr auto kern() { return GU ? k_moe_i8_gate_up_silu<TT, RT> : k_moe_i8_down<TT, RT>; }
+};
 
 extern "C" {
 
 int samd_moe_gate_up_silu_i8(const void *d_h, const void *d_Wgu8, const void *d_ws, int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts,
                              int32_t top_k, void *d_act, int32_t dtype, void *stream) {
-    if (!d_h || !d_Wgu8 || !d_ws || !d_act || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
-        samd_set_error("samd_moe_gate_up_silu_i8: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
-    }
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
-    const hipError_t e = moe_i8_gemm_dispatch<true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu8, (const int *)d_ws, d_act,
-                                                    hidden, 2 * moe_inter, top_k);
-    if (e != hipSuccess) { samd_set_error("samd_moe_gate_up_silu_i8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
-    LAUNCHCHK();
-    return SAMD_OK;
+    return moe_q_gate_up_silu<MoeI8>("samd_moe_gate_up_silu_i8", d_h, d_Wgu8, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_act, dtype, stream);
 }
 
 int samd_moe_down_combine_i8(const void *d_act, const void *d_Wdown8, const int32_t *d_topk_idx, const void *d_topk_w, const int32_t *d_n, void *d_ws,
                              int32_t rows_pad, int32_t hidden, int32_t moe_inter, int32_t n_experts, int32_t top_k, void *d_out, int32_t dtype, void *stream) {
-    if (!d_act || !d_Wdown8 || !d_topk_idx || !d_topk_w || !d_n || !d_ws || !d_out || !moe_shape_ok(rows_pad, hidden, moe_inter, n_experts, top_k, dtype)) {
-        samd_set_error("samd_moe_down_combine_i8: " MOE_SHAPE_MSG); return SAMD_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    void *y = (char *)d_ws + MOE_WS_Y_OFF;
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
-    const hipError_t e = moe_i8_gemm_dispatch<false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown8, (const int *)d_ws, y, moe_inter, hidden, top_k);
-    if (e != hipSuccess) { samd_set_error("samd_moe_down_combine_i8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
-    LAUNCHCHK();
-    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
-    if (dtype == SAMD_F16)
-        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
-    else
-        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
-    LAUNCHCHK();
-    return SAMD_OK;
+    return moe_q_down_combine<MoeI8>("samd_moe_down_combine_i8", d_act, d_Wdown8, d_topk_idx, d_topk_w, d_n, d_ws, rows_pad, hidden, moe_inter, n_experts, top_k, d_out, dtype,
+                                     stream);
 }
 
 }  // extern "C"
@@ -3051,11 +2788,11 @@ int samd_moe_down_combine_i8(const void *d_act, const void *d_Wdown8, const int3
 //   out = sum_b s_b * (sum_{k in block b} A[m][k] * q[n][k]) -- the inner sum an fp32 MFMA accumulation over the block's 128 k with q widened
 //   exactly (F8Widen, scale 1), the outer step ONE fp32 FMA per accumulator and block (acc = fma(acc_blk, s_b, acc)), blocks in ascending
 //   order: 4 * RT FMAs per lane and block.  Nothing can overflow the model dtype on the way; the epilogues' roundings are unchanged.
-//   samd_moe_gate_up_silu_f8 / samd_moe_down_combine_f8: the fixed grid (N / 128, min(E, rows_pad * top_k)), the early exit of slots
-//   >= ws[0], the list in static LDS, the gathered LDS-DMA A tile (srow), the counted waits with in-out load destinations, both epilogues
-//   (HF's roundings; rows >= cnt not stored) and k_moe_combine are moe_expert_gemm's; the weight side is k_gemm_skinny_f8's: 32 KiB per
-//   (128-column tile, 256-k chunk), four hand-issued nt 16-byte loads per thread and chunk.  No split-K, no atomics: a row's output has the
-//   same bits whatever shares the launch.  A function of its own: the other expert kernels are left textually alone.
+//   samd_moe_gate_up_silu_f8 / samd_moe_down_combine_f8: the fixed grid (N / 128, min(E, rows_pad * top_k)) and k_moe_combine are the
+//   model-dtype calls'; the expert side is the shared one (THE SIDE, above the 4-bit streaming body), with the scale staging under the
+//   list's barrier; the counted waits have in-out load destinations (THE PIPELINE, there); the weight side is k_gemm_skinny_f8's: 32 KiB
+//   per (128-column tile, 256-k chunk), four hand-issued nt 16-byte loads per thread and chunk.  No split-K, no atomics: a row's output
+//   has the same bits whatever shares the launch.  The weight pipeline is a function of its own (the per-block FMA sits inside the phase).
 //   PACKED BUFFER (samd_hip/moe.py: pack_experts_fp8), one per fused tensor: the codes of the E experts laid end to end as ONE matrix of
 //   E * N rows in samd_gemm_pack_f8's layout (expert e's tile t is global tile T = e * N / 128 + t, chunk c at (T * K / 256 + c) * 32768
 //   bytes; gate|up rows permuted before packing by gate_up_tile_order), then, at the next multiple of 256 bytes, an fp32 table
@@ -3090,28 +2827,19 @@ __device__ __forceinline__ void moe8_expert_gemm(const typename TT::elem *__rest
     constexpr size_t WCH = 32768, WU = 8192;       // bytes of one (tile, chunk) block; of one b row inside it
     extern __shared__ __attribute__((aligned(1024))) char gemm_lds[];
     E (*xs)[R][GEMM_KC] = reinterpret_cast<E (*)[R][GEMM_KC]>(gemm_lds);
-    __shared__ int lst[MOE_MAX_ROWS];
     __shared__ __attribute__((aligned(8))) float scl[2][MOE8_MAX_KB];
 
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    const int slot_a = blockIdx.y;
-    if (slot_a >= ws[0]) return;                   // (uniform) grid = the shape's upper bound of active experts (WIDE: of tiles; ws[0] = the tile count)
-    const int *rec = ws + MOEW_WS_TILE + MOEW_TILE_INTS * slot_a;     // WIDE: the tile's record {expert, first entry, entries}
-    const int expert = WIDE ? rec[0] : ws[MOE_WS_ACTIVE + slot_a];
-    int cnt = WIDE ? rec[2] : ws[MOE_WS_COUNT + slot_a];
-    cnt = cnt > R ? R : cnt;
-    const size_t tile = (size_t)expert * (N / GEMM_COLS) + blockIdx.x;
-    const int *ent = WIDE ? ws + MOEW_WS_ENTRY + rec[1] : ws + MOE_WS_LIST + MOE_MAX_ROWS * slot_a;
-    if (tid < MOE_MAX_ROWS) lst[tid] = ent[tid < cnt ? tid : 0];
-    // the tile's scales: rows 2 tile (waves 0-3) and 2 tile + 1 (waves 4-7) of the table are contiguous, 2 * K / 128 floats
+    if (moe_side_idle(ws)) return;
+    const MoeSlot slot = moe_side_open<R, WIDE>(ws);
+    int srow[XV];
+    const size_t tile = (size_t)slot.expert * (N / GEMM_COLS) + blockIdx.x;
+    // the tile's scales, under the list's barrier: rows 2 tile (waves 0-3) and 2 tile + 1 (waves 4-7) of the table are contiguous, 2 * K / 128 floats
     if (tid < 4 * n_chunks) scl[tid >= 2 * n_chunks][tid >= 2 * n_chunks ? tid - 2 * n_chunks : tid] = stab[tile * 4 * n_chunks + tid];
     __syncthreads();
-    // this thread's source rows of the A tile: tile row r = entry r of the expert's list (rows past the count: entry 0 again)
-    int srow[XV];
 #pragma unroll
-    for (int i = 0; i < XV; i++) { const int p = lst[(tid >> 5) + 16 * i]; srow[i] = GU ? p / top_k : p; }
+    for (int i = 0; i < XV; i++) srow[i] = moe_side_row<GU>(i, top_k);
 
-    const int n0 = blockIdx.x * GEMM_COLS + 16 * w;
     const char *wtile = reinterpret_cast<const char *>(W8) + tile * n_chunks * WCH;
     const uint32_t wlane = (uint32_t)tid * 16;
     const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t)&xs[0][0][0];
@@ -3120,7 +2848,7 @@ __device__ __forceinline__ void moe8_expert_gemm(const typename TT::elem *__rest
     floatx4 acc[RT];
 #pragma unroll
     for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    // the load destinations: one value each, defined once; every load is an in-out operand of it (see gemm_skinny_w4)
+    // the load destinations: one value each, defined once; every load is an in-out operand of it (THE PIPELINE, at gemm_stream_w4)
     u32x4 wr[DEPTH][4];
 #pragma unroll
     for (int d = 0; d < DEPTH; d++)
@@ -3192,39 +2920,8 @@ __device__ __forceinline__ void moe8_expert_gemm(const typename TT::elem *__rest
         for (int d = 0; d < DEPTH; d++)
             if (c + d < n_chunks) { phase(wr[d], c + d, buf); buf = buf == NB - 1 ? 0 : buf + 1; }
     }
-    // C layout of mfma_16x16: lane holds rows 4g + r of column n; the block scales went in with the FMAs
-    if constexpr (GU) {
-        float *ex = reinterpret_cast<float *>(gemm_lds);            // [R][64] up values; the A tiles are dead by now
-        __syncthreads();
-        if (w >= 4) {
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) ex[(16 * mt + 4 * g + r) * 64 + 16 * (w - 4) + n] = acc[mt][r];
-        }
-        __syncthreads();
-        if (w < 4) {
-#pragma unroll
-            for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int m = 16 * mt + 4 * g + r;
-                    if (m >= cnt) continue;
-                    // the roundings of HF's act_fn(gate) * up in the model dtype (same as moe_expert_gemm)
-                    const float gf = (float)(E)acc[mt][r], uf = (float)(E)ex[m * 64 + 16 * w + n];
-                    const E sv = (E)(gf / (1.f + __expf(-gf)));
-                    out[(size_t)lst[m] * (N / 2) + blockIdx.x * 64 + 16 * w + n] = (E)((float)sv * uf);
-                }
-        }
-    } else {
-#pragma unroll
-        for (int mt = 0; mt < RT; mt++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int m = 16 * mt + 4 * g + r;
-                if (m < cnt) out[(size_t)lst[m] * N + n0 + n] = (E)acc[mt][r];
-            }
-    }
+    // the block scales went in with the FMAs: the sums are final
+    moe_side_store<TT, RT, GU>(acc, slot.cnt, out, N, reinterpret_cast<float *>(gemm_lds), w, n, g);
 }
 
 template <typename TT, int RT>
@@ -3245,34 +2942,11 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT == 1 ? 2 : 1) void k_moe8_down(
 // block_scale_offset is the same formula)
 static inline size_t moe8_scale_offset(size_t rows, size_t K) { return (rows * K + 255) / 256 * 256; }
 
-template <typename TT, int RT, bool GU>
-static hipError_t moe8_gemm_launch(dim3 grid, hipStream_t st, const void *A, const void *W8, const float *stab, const int *ws, void *out, int K, int N, int top_k) {
-    typedef typename TT::elem E;
-    constexpr int lds = (Moe8Depth<RT>::value + 1) * 16 * RT * GEMM_KC * 2;
-    if constexpr (GU) {
-        if constexpr (lds > 65536) {
-            static unsigned long long done = 0ull;                 // per-device (samd_common.h)
-            const hipError_t attr = samd_reserve_lds((const void *)k_moe8_gate_up_silu<TT, RT>, lds, &done);
-            if (attr != hipSuccess) return attr;
-        }
-        hipLaunchKernelGGL((k_moe8_gate_up_silu<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const unsigned char *)W8, stab, ws, (E *)out, K, N,
-                           K / GEMM_KC, top_k);
-    } else {
-        if constexpr (lds > 65536) {
-            static unsigned long long done = 0ull;
-            const hipError_t attr = samd_reserve_lds((const void *)k_moe8_down<TT, RT>, lds, &done);
-            if (attr != hipSuccess) return attr;
-        }
-        hipLaunchKernelGGL((k_moe8_down<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const E *)A, (const unsigned char *)W8, stab, ws, (E *)out, K, N,
-                           K / GEMM_KC, top_k);
-    }
-    return hipSuccess;
-}
-
 template <bool GU>
 static hipError_t moe8_gemm_dispatch(int dtype, int rows_pad, dim3 grid, hipStream_t st, const void *A, const void *W8, size_t rows, const int *ws, void *out, int K, int N, int top_k) {
     const float *stab = reinterpret_cast<const float *>(reinterpret_cast<const char *>(W8) + moe8_scale_offset(rows, (size_t)K));
-#define GO(TT, RT) return moe8_gemm_launch<TT, RT, GU>(grid, st, A, W8, stab, ws, out, K, N, top_k)
+#define GO(TT, RT) return stream_launch<(GU ? k_moe8_gate_up_silu<TT, RT> : k_moe8_down<TT, RT>), stream_lds(Moe8Depth<RT>::value, RT)>( \
+        grid, st, (const typename TT::elem *)A, (const unsigned char *)W8, stab, ws, (typename TT::elem *)out, K, N, K / GEMM_KC, top_k)
 #define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
     if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
 #undef ROWS
@@ -3289,7 +2963,7 @@ int samd_moe_gate_up_silu_f8(const void *d_h, const void *d_Wgu8, const void *d_
         moe_inter > 128 * MOE8_MAX_KB) {
         samd_set_error("samd_moe_gate_up_silu_f8: " MOE8_SHAPE_MSG); return SAMD_E_INVALID;
     }
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const int bound = moe_slot_bound(rows_pad, n_experts, top_k);
     const hipError_t e = moe8_gemm_dispatch<true>(dtype, rows_pad, dim3(2 * moe_inter / GEMM_COLS, bound), (hipStream_t)stream, d_h, d_Wgu8,
                                                   (size_t)n_experts * 2 * moe_inter, (const int *)d_ws, d_act, hidden, 2 * moe_inter, top_k);
     if (e != hipSuccess) { samd_set_error("samd_moe_gate_up_silu_f8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
@@ -3305,16 +2979,12 @@ int samd_moe_down_combine_f8(const void *d_act, const void *d_Wdown8, const int3
     }
     hipStream_t st = (hipStream_t)stream;
     void *y = (char *)d_ws + MOE_WS_Y_OFF;
-    const int bound = n_experts < rows_pad * top_k ? n_experts : rows_pad * top_k;
+    const int bound = moe_slot_bound(rows_pad, n_experts, top_k);
     const hipError_t e = moe8_gemm_dispatch<false>(dtype, rows_pad, dim3(hidden / GEMM_COLS, bound), st, d_act, d_Wdown8, (size_t)n_experts * hidden,
                                                    (const int *)d_ws, y, moe_inter, hidden, top_k);
     if (e != hipSuccess) { samd_set_error("samd_moe_down_combine_f8: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
     LAUNCHCHK();
-    const dim3 cgrid((hidden / 8 + 255) / 256, rows_pad);
-    if (dtype == SAMD_F16)
-        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
-    else
-        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
+    moe_combine_launch(dtype, st, y, d_topk_idx, d_topk_w, d_n, d_out, rows_pad, hidden, top_k, n_experts);
     LAUNCHCHK();
     return SAMD_OK;
 }
@@ -3388,7 +3058,7 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT <= 2 ? 4 : 2) void k_gemm_skinn
     floatx4 acc[RT];
 #pragma unroll
     for (int mt = 0; mt < RT; mt++) acc[mt] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    // the load destinations: one value each, defined once; every load is an in-out operand of it (see gemm_skinny_w4)
+    // the load destinations: one value each, defined once; every load is an in-out operand of it (THE PIPELINE, at gemm_stream_w4)
     u32x4 wr[DEPTH][4];
 #pragma unroll
     for (int d = 0; d < DEPTH; d++)
@@ -3478,20 +3148,6 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT <= 2 ? 4 : 2) void k_gemm_skinn
     }
 }
 
-template <typename TT, int RT>
-static hipError_t gemm_f8b_launch(dim3 grid, hipStream_t st, const void *A, const void *W8, const float *sinv, float *partial, void *out, int K, int N,
-                                  int splits) {
-    constexpr int lds = (F8bDepth<RT>::value + 1) * 16 * RT * GEMM_KC * 2;
-    if constexpr (lds > 65536) {
-        static unsigned long long done = 0ull;                     // per-device (samd_common.h)
-        const hipError_t attr = samd_reserve_lds((const void *)k_gemm_skinny_f8b<TT, RT>, lds, &done);
-        if (attr != hipSuccess) return attr;
-    }
-    hipLaunchKernelGGL((k_gemm_skinny_f8b<TT, RT>), grid, dim3(64 * GEMM_WAVES), lds, st, (const typename TT::elem *)A, (const unsigned char *)W8, sinv,
-                       partial, (typename TT::elem *)out, K, N, K / GEMM_KC, splits);
-    return hipSuccess;
-}
-
 extern "C" {
 
 int samd_gemm_skinny_f8b(const void *d_A, const void *d_W8p, const float *d_sinv, int32_t rows_pad, int32_t N, int32_t K, int32_t splits, float *d_partial,
@@ -3506,7 +3162,8 @@ int samd_gemm_skinny_f8b(const void *d_A, const void *d_W8p, const float *d_sinv
     const hipStream_t st = (hipStream_t)stream;
     float *part = splits == 1 ? nullptr : d_partial;
     void *out = splits == 1 ? d_out : nullptr;
-#define GO(TT, RT) e = gemm_f8b_launch<TT, RT>(grid, st, d_A, d_W8p, d_sinv, part, out, K, N, splits)
+#define GO(TT, RT) e = stream_launch<k_gemm_skinny_f8b<TT, RT>, stream_lds(F8bDepth<RT>::value, RT)>(grid, st, (const typename TT::elem *)d_A, \
+        (const unsigned char *)d_W8p, d_sinv, part, (typename TT::elem *)out, K, N, K / GEMM_KC, splits)
 #define ROWS(TT) do { if (rows_pad == 16) GO(TT, 1); else if (rows_pad == 32) GO(TT, 2); else if (rows_pad == 48) GO(TT, 3); else GO(TT, 4); } while (0)
     hipError_t e;
     if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
@@ -3671,9 +3328,9 @@ int samd_gemm_unpack_i8(const void *d_W8p, int32_t N, int32_t K, void *d_out, in
 // Mixture-of-experts MLP over MANY rows (a prompt in one pass): samd_moe_wide_route / _lists / _gate_up_silu / _down_combine serve 1 ..
 // MOEW_MAX_ROWS rows (padded to 64 inside; rows >= *d_n route nowhere) with the kernels above.  An expert's list may now be longer than a
 // 64-row tile, so the lists are followed by a TILE TABLE -- one record {expert, first entry, entries <= 64} per 64 entries of an expert's
-// list, the tiles of one expert adjacent, experts ascending -- and an expert GEMM workgroup is moe_expert_gemm / moe_w4_ /
-// moe8_expert_gemm<TT, 4, GU, WIDE = true>: the 64-row tile's stream, MFMA sequence, epilogues and roundings, with `expert`, `cnt` and the
-// list taken from its tile record instead of an active slot.  A row's sum does not depend on the tile it sits in (chunk order over k, no
+// list, the tiles of one expert adjacent, experts ascending -- and an expert GEMM workgroup is moe_expert_gemm / moe8_expert_gemm<TT, 4,
+// GU, WIDE = true> or gemm_stream_w4 / gemm_stream_i8<..., 4, ..., SIDE_WIDE, GU>: the 64-row tile's stream, MFMA sequence, epilogues and
+// roundings, with `expert`, `cnt` and the list taken from its tile record instead of an active slot (moe_side_open).  A row's sum does not depend on the tile it sits in (chunk order over k, no
 // split-K), so every row gets the bits the <= 64-row calls give it.
 //   GRID (column tile, tile slot); the slot dimension is the shape's bound min(E, rows * k) + rows * k / 64 >= sum_e ceil(c_e / 64)
 //   (each active expert has at most one partly filled tile); workgroups past ws[0] = the tile count exit at once.  Nothing comes back to
@@ -3749,22 +3406,22 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe_dn(const typename T
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe4_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
                                                                 typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
-    moe_w4_expert_gemm<W4Mx, TT, 4, true, true>(h, W4, ws, act, K, N, n_chunks, top_k);
+    gemm_stream_w4<W4Mx, TT, 4, MoeW4Depth<4>::value, SIDE_WIDE, true>(h, W4, ws, nullptr, act, K, N, n_chunks, top_k);
 }
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe4_dn(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
                                                                 typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
-    moe_w4_expert_gemm<W4Mx, TT, 4, false, true>(act, W4, ws, y, K, N, n_chunks, top_k);
+    gemm_stream_w4<W4Mx, TT, 4, MoeW4Depth<4>::value, SIDE_WIDE, false>(act, W4, ws, nullptr, y, K, N, n_chunks, top_k);
 }
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe_i4_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
                                                                   typename TT::elem *__restrict__ act, int K, int N, int n_chunks, int top_k) {
-    moe_w4_expert_gemm<W4Int, TT, 4, true, true>(h, W4, ws, act, K, N, n_chunks, top_k);
+    gemm_stream_w4<W4Int, TT, 4, MoeW4Depth<4>::value, SIDE_WIDE, true>(h, W4, ws, nullptr, act, K, N, n_chunks, top_k);
 }
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_wmoe_i4_dn(const typename TT::elem *__restrict__ act, const unsigned char *__restrict__ W4, const int *__restrict__ ws,
                                                                   typename TT::elem *__restrict__ y, int K, int N, int n_chunks, int top_k) {
-    moe_w4_expert_gemm<W4Int, TT, 4, false, true>(act, W4, ws, y, K, N, n_chunks, top_k);
+    gemm_stream_w4<W4Int, TT, 4, MoeW4Depth<4>::value, SIDE_WIDE, false>(act, W4, ws, nullptr, y, K, N, n_chunks, top_k);
 }
 template <typename TT>
 __global__ __launch_bounds__(64 * GEMM_WAVES, 1) void k_wmoe8_gu(const typename TT::elem *__restrict__ h, const unsigned char *__restrict__ W8, const float *__restrict__ stab,
@@ -3777,41 +3434,18 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 1) void k_wmoe8_dn(const typename 
     moe8_expert_gemm<TT, 4, false, true>(act, W8, stab, ws, y, K, N, n_chunks, top_k);
 }
 
-// one wide expert launch: the 64-row tile's dynamic LDS of the format (reserved once per kernel and device), grid (N / 128, tile slots)
-template <auto KERN, typename... A>
-static hipError_t wmoe_launch(int lds, dim3 grid, hipStream_t st, A... args) {
-    static unsigned long long done = 0ull;                       // per-device (samd_common.h)
-    const hipError_t attr = samd_reserve_lds((const void *)KERN, lds, &done);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(KERN, grid, dim3(64 * GEMM_WAVES), lds, st, args...);
-    return hipSuccess;
-}
-
+// one wide expert launch: the format's kernel at the 64-row tile with that tile's dynamic LDS, grid (N / 128, tile slots)
 template <typename TT, bool GU>
 static hipError_t wmoe_gemm_format(int fmt, dim3 grid, hipStream_t st, const void *A, const void *W, size_t w_rows, const int *ws, void *out, int K, int N, int top_k) {
     typedef typename TT::elem E;
-    constexpr int tile = 16 * 4 * GEMM_KC * 2;                   // one A buffer of the 64-row tile
     const unsigned char *wb = (const unsigned char *)W;
     const int nc = K / GEMM_KC;
-    if (fmt == 0) {
-        if constexpr (GU) return wmoe_launch<k_wmoe_gu<TT>>(3 * tile, grid, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, nc, top_k);
-        else return wmoe_launch<k_wmoe_dn<TT>>(3 * tile, grid, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, nc, top_k);
-    }
-    if (fmt == 1 || fmt == 2) {
-        constexpr int lds = (MoeW4Depth<4>::value + 1) * tile;
-        constexpr auto mx = GU ? k_wmoe4_gu<TT> : k_wmoe4_dn<TT>, i4 = GU ? k_wmoe_i4_gu<TT> : k_wmoe_i4_dn<TT>;
-        return fmt == 1 ? wmoe_launch<mx>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k)
-                        : wmoe_launch<i4>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
-    }
-    if (fmt == 5) {
-        constexpr int lds = (MoeI8Depth<4>::value + 1) * tile;
-        if constexpr (GU) return wmoe_launch<k_moew_i8_gu<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
-        else return wmoe_launch<k_moew_i8_dn<TT>>(lds, grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
-    }
-    constexpr int lds = (Moe8Depth<4>::value + 1) * tile;
+    if (fmt == 0) return stream_launch<(GU ? k_wmoe_gu<TT> : k_wmoe_dn<TT>), stream_lds(2, 4)>(grid, st, (const E *)A, (const E *)W, ws, (E *)out, K, N, nc, top_k);
+    if (fmt == 1) return stream_launch<(GU ? k_wmoe4_gu<TT> : k_wmoe4_dn<TT>), stream_lds(MoeW4Depth<4>::value, 4)>(grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
+    if (fmt == 2) return stream_launch<(GU ? k_wmoe_i4_gu<TT> : k_wmoe_i4_dn<TT>), stream_lds(MoeW4Depth<4>::value, 4)>(grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
+    if (fmt == 5) return stream_launch<(GU ? k_moew_i8_gu<TT> : k_moew_i8_dn<TT>), stream_lds(MoeI8Depth<4>::value, 4)>(grid, st, (const E *)A, wb, ws, (E *)out, K, N, nc, top_k);
     const float *stab = reinterpret_cast<const float *>(reinterpret_cast<const char *>(W) + moe8_scale_offset(w_rows, (size_t)K));
-    if constexpr (GU) return wmoe_launch<k_wmoe8_gu<TT>>(lds, grid, st, (const E *)A, wb, stab, ws, (E *)out, K, N, nc, top_k);
-    else return wmoe_launch<k_wmoe8_dn<TT>>(lds, grid, st, (const E *)A, wb, stab, ws, (E *)out, K, N, nc, top_k);
+    return stream_launch<(GU ? k_wmoe8_gu<TT> : k_wmoe8_dn<TT>), stream_lds(Moe8Depth<4>::value, 4)>(grid, st, (const E *)A, wb, stab, ws, (E *)out, K, N, nc, top_k);
 }
 
 static inline int moew_rows_pad(int rows) { return (rows + MOE_MAX_ROWS - 1) / MOE_MAX_ROWS * MOE_MAX_ROWS; }
@@ -3909,11 +3543,7 @@ int samd_moe_wide_down_combine(const void *d_act, const void *d_Wdown, const int
         : wmoe_gemm_format<GBF16, false>(expert_format, grid, st, d_act, d_Wdown, w_rows, (const int *)d_ws, y, moe_inter, hidden, top_k);
     if (e != hipSuccess) { samd_set_error("samd_moe_wide_down_combine: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
     LAUNCHCHK();
-    const dim3 cgrid((hidden / 8 + 255) / 256, rp);
-    if (dtype == SAMD_F16)
-        hipLaunchKernelGGL(k_moe_combine<_Float16>, cgrid, dim3(256), 0, st, (const _Float16 *)y, d_topk_idx, (const _Float16 *)d_topk_w, d_n, (_Float16 *)d_out, hidden, top_k, n_experts);
-    else
-        hipLaunchKernelGGL(k_moe_combine<__bf16>, cgrid, dim3(256), 0, st, (const __bf16 *)y, d_topk_idx, (const __bf16 *)d_topk_w, d_n, (__bf16 *)d_out, hidden, top_k, n_experts);
+    moe_combine_launch(dtype, st, y, d_topk_idx, d_topk_w, d_n, d_out, rp, hidden, top_k, n_experts);
     LAUNCHCHK();
     return SAMD_OK;
 }
