@@ -283,6 +283,14 @@ __device__ __forceinline__ u32x4 norm_scale8(u32x4 xraw, u32x4 graw, float rs) {
     return out;
 }
 
+// one staged unit of an ODD row count (AR rows of 32 lanes each): the x and g loads under a wave-uniform lane mask.  The wave ISSUES both
+// loads whatever the mask, so the counted waits stay exact; a masked-off lane fetches nothing and keeps stale registers.  One statement
+// with unconditional outputs, not a branch around the loads: the compiler must see no path on which it may copy a register in flight
+__device__ __forceinline__ void norm_load_masked(u32x4 &xd, u32x4 &gd, const void *xsrc, const void *gsrc, unsigned long long mask) {
+    unsigned long long saved;
+    asm volatile("s_and_saveexec_b64 %2, %5\n\tglobal_load_dwordx4 %0, %3, off\n\tglobal_load_dwordx4 %1, %4, off\n\ts_mov_b64 exec, %2"
+                 : "=&v"(xd), "=&v"(gd), "=&s"(saved) : "v"(xsrc), "v"(gsrc), "s"(mask) : "memory", "scc");
+}
 
 // counted wait of the weight stream: memory operations retire in issue order, so chunk c has landed when at most `younger` x PC
 // operations (PC = this wave's memory operations per chunk) may still fly
@@ -311,7 +319,9 @@ __device__ __forceinline__ void gemm_wait_younger(int younger) {
 // (32 KiB chunks: DEPTH 4 = the same 128 KiB per workgroup), counted waits, bare barriers.
 // ================================================================================================
 // AR (NORM only; round 4): activation rows a workgroup fetches -- 16, or 8 for a draft of <= 8 nodes: waves 0-3 stage rows 0-7, waves 4-7
-// stage nothing (rows 8-15 of the LDS tiles are zeroed once), a sixth less of what the CU's memory pipe ingests beside the weights
+// stage nothing (rows 8-15 of the LDS tiles are zeroed once), a sixth less of what the CU's memory pipe ingests beside the weights.
+// Any AR in 1..16 (the draft's own node count, known on the host): threads 0 .. 32 AR - 1 stage, the others zero rows AR..15 once; with an
+// odd AR the upper half of the last staging wave is masked off inside the loads, which the wave still issues (norm_load_masked)
 template <typename TT, int RT, int DEPTH, int CG, bool NORM, int AR = 16>
 __global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 || NORM ? 2 : GEMM_WAVES / 2) void k_gemm_qkv_rope(
         const typename TT::elem *__restrict__ A, const typename TT::elem *__restrict__ W, int K, int n_chunks,
@@ -333,8 +343,10 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 || NORM ? 2 : GEMM_WAVES /
     // waves 0 .. 2 CG - 1 stream and multiply (column group cg, k half kh); with 48-column tiles waves 6, 7 only help staging A
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
     const bool streams = CG == 4 || w < 2 * CG;
-    static_assert(AR == 16 || (AR == 8 && NORM && RT == 1), "8 activation rows: the norm-fold kernels only");
-    const bool stager = AR == 16 || w < GEMM_WAVES / 2;                          // wave-uniform: rows 0..7 belong to threads 0..255
+    static_assert(AR == 16 || (AR >= 1 && AR < 16 && NORM && RT == 1), "fewer than 16 activation rows: the norm-fold kernels only");
+    const bool stager = AR == 16 || w < (AR + 1) / 2;                            // wave-uniform: a wave with a staging lane (rows 0..AR-1 belong to threads 0..32 AR - 1)
+    const bool stages = !(AR & 1) ? stager : tid < 32 * AR;                      // per lane: not the upper half of an odd AR's last staging wave
+    const unsigned long long stage_mask = (AR & 1) && __builtin_amdgcn_readfirstlane(w) == AR / 2 ? 0xffffffffull : ~0ull;
     const int cg = CG == 4 ? (w & 3) : (streams ? w % CG : 0), kh = CG == 4 ? (w >> 2) : (streams ? w / CG : 0);
     const char *wtile = reinterpret_cast<const char *>(W) + (size_t)blockIdx.x * n_chunks * CH;
     const uint32_t wlane = (uint32_t)(64 * (CG * kh + cg) + l) * 16;
@@ -363,8 +375,11 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 || NORM ? 2 : GEMM_WAVES /
         const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
         if constexpr (NORM) {
             const E *gsrc = reinterpret_cast<const E *>(na.g) + (size_t)c * GEMM_KC + 8 * unit;
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(xr[d][i]) : "v"(src) : "memory");
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(gr[d][i]) : "v"(gsrc) : "memory");
+            if constexpr (AR & 1) norm_load_masked(xr[d][i], gr[d][i], src, gsrc, stage_mask);
+            else {
+                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(xr[d][i]) : "v"(src) : "memory");
+                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(gr[d][i]) : "v"(gsrc) : "memory");
+            }
         } else {
             E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
@@ -387,7 +402,7 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 || NORM ? 2 : GEMM_WAVES /
                 // (re-defined here, behind the counted wait: the compiler does not know that the asm loads that produced them were asynchronous)
                 asm volatile("" : "+v"(xr[d][i]), "+v"(gr[d][i]) : : "memory");
                 const u32x4 v = norm_scale8<E>(xr[d][i], gr[d][i], norm_rs[row]);
-                *reinterpret_cast<u32x4 *>(&xs[buf][0][0] + (size_t)slot * 8) = v;
+                if (stages) *reinterpret_cast<u32x4 *>(&xs[buf][0][0] + (size_t)slot * 8) = v;
             }
         }
     };
@@ -435,8 +450,8 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 || NORM ? 2 : GEMM_WAVES /
 #pragma unroll
     for (int d = 0; d < DEPTH; d++)
         if (d < n_chunks) issue(wr[d], d, d, d);
-    if constexpr (AR == 8) {                        // rows 8..15 of every A buffer: zero, once (the waves that stage nothing write them)
-        if (!stager) {
+    if constexpr (AR < 16) {                        // rows AR..15 of every A buffer: zero, once (the lanes that stage nothing write them)
+        if (!stages) {
 #pragma unroll
             for (int bz = 0; bz < NB; bz++) *reinterpret_cast<u32x4 *>(&xs[bz][0][0] + (size_t)tid * 8) = (u32x4){0u, 0u, 0u, 0u};
         }
@@ -558,8 +573,10 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 || DEPTH > 2 ? 2 : GEMM_WA
     // this workgroup's pairs [p0, p1): an even deal of n_pairs over the grid
     const int p0 = (int)((long long)blockIdx.x * n_pairs / gridDim.x), p1 = (int)((long long)(blockIdx.x + 1) * n_pairs / gridDim.x);
     const bool active = w < 2 * (p1 - p0);                                       // wave-uniform
-    static_assert(AR == 16 || (AR == 8 && NORM && RT == 1), "8 activation rows: the norm-fold kernels only");
-    const bool stager = AR == 16 || w < GEMM_WAVES / 2;                          // wave-uniform: rows 0..7 belong to threads 0..255
+    static_assert(AR == 16 || (AR >= 1 && AR < 16 && NORM && RT == 1), "fewer than 16 activation rows: the norm-fold kernels only");
+    const bool stager = AR == 16 || w < (AR + 1) / 2;                            // wave-uniform: a wave with a staging lane (rows 0..AR-1 belong to threads 0..32 AR - 1)
+    const bool stages = !(AR & 1) ? stager : tid < 32 * AR;                      // per lane: not the upper half of an odd AR's last staging wave
+    const unsigned long long stage_mask = (AR & 1) && w == AR / 2 ? 0xffffffffull : ~0ull;
     const int gi = 2 * p0 + w;                                                    // this wave's column group
     const char *wgrp = reinterpret_cast<const char *>(W) + (size_t)(active ? gi : 0) * n_chunks * 8192;
     const uint32_t wlane = (uint32_t)l * 16;
@@ -590,8 +607,11 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 || DEPTH > 2 ? 2 : GEMM_WA
             const E *src = A + (size_t)((abl & 8) ? (row & 15) : row) * K + (size_t)c * GEMM_KC + 8 * unit;
             if constexpr (NORM) {
                 const E *gsrc = reinterpret_cast<const E *>(na.g) + (size_t)c * GEMM_KC + 8 * unit;
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(xr[d][i]) : "v"(src) : "memory");
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(gr[d][i]) : "v"(gsrc) : "memory");
+                if constexpr (AR & 1) norm_load_masked(xr[d][i], gr[d][i], src, gsrc, stage_mask);
+                else {
+                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(xr[d][i]) : "v"(src) : "memory");
+                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(gr[d][i]) : "v"(gsrc) : "memory");
+                }
             } else {
                 E *dst = &xs[buf][0][0] + (size_t)(NT * i + 64 * w) * 8;
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
@@ -612,7 +632,7 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 || DEPTH > 2 ? 2 : GEMM_WA
                     // (re-defined here, behind the counted wait: the compiler does not know that the asm loads that produced them were asynchronous)
                     asm volatile("" : "+v"(xr[d][i]), "+v"(gr[d][i]) : : "memory");
                     const u32x4 v = norm_scale8<E>(xr[d][i], gr[d][i], norm_rs[row]);
-                    *reinterpret_cast<u32x4 *>(&xs[buf][0][0] + (size_t)slot * 8) = v;
+                    if (stages) *reinterpret_cast<u32x4 *>(&xs[buf][0][0] + (size_t)slot * 8) = v;
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -657,8 +677,8 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, RT >= 3 || DEPTH > 2 ? 2 : GEMM_WA
 #pragma unroll
     for (int d = 0; d < DEPTH; d++)
         if (d < n_chunks) { if (active) load_w(wr[d], d); stage_x(d, d, d); }
-    if constexpr (AR == 8) {                        // rows 8..15 of every A buffer: zero, once
-        if (!stager) {
+    if constexpr (AR < 16) {                        // rows AR..15 of every A buffer: zero, once
+        if (!stages) {
 #pragma unroll
             for (int bz = 0; bz < NB; bz++) *reinterpret_cast<u32x4 *>(&xs[bz][0][0] + (size_t)tid * 8) = (u32x4){0u, 0u, 0u, 0u};
         }
@@ -731,16 +751,19 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_cs_residual(const t
     const char *wgrp = reinterpret_cast<const char *>(W) + (size_t)blockIdx.x * n_chunks * 8192;
     const uint32_t wlane = (uint32_t)l * 16;
 
-    // ROWS = 8: a draft of <= 8 rows -- only rows 0..7 of the activation tile are fetched (half of what this ingest-bound launch pulls
-    // from L2 besides its weights); rows 8..15 of the LDS tiles are zeroed once and their outputs are not written
-    static_assert(ROWS == 8 || ROWS == 16, "");
-    constexpr int AL = ROWS / 2;                               // A loads per lane and chunk
-    if constexpr (ROWS == 8) {
+    // ROWS < 16: a draft of ROWS rows -- only rows 0..ROWS-1 of the activation tile are fetched (at 8 rows half of what this ingest-bound
+    // launch pulls from L2 besides its weights); rows ROWS..15 of the LDS tiles are zeroed once and their outputs are not written.  A load
+    // covers two rows (lanes 0-31 | 32-63): with an odd ROWS the upper half of the last one is masked off -- the wave still issues the
+    // instruction, so the counted waits below do not change
+    static_assert(ROWS >= 1 && ROWS <= 16, "");
+    constexpr int AL = (ROWS + 1) / 2;                         // A loads per lane and chunk
+    if constexpr (ROWS < 16) {
 #pragma unroll
         for (int buf = 0; buf < CSD; buf++)
 #pragma unroll
-            for (int i = 4; i < 8; i++)
-                *reinterpret_cast<u32x4 *>(xs + (size_t)buf * 16 * GEMM_KC + (size_t)(64 * i + l) * 8) = (u32x4){0u, 0u, 0u, 0u};
+            for (int i = ROWS / 2; i < 8; i++)
+                if (!(ROWS & 1) || i > ROWS / 2 || l >= 32)
+                    *reinterpret_cast<u32x4 *>(xs + (size_t)buf * 16 * GEMM_KC + (size_t)(64 * i + l) * 8) = (u32x4){0u, 0u, 0u, 0u};
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     floatx4 acc = (floatx4){0.f, 0.f, 0.f, 0.f};
@@ -759,7 +782,8 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, 2) void k_gemm_cs_residual(const t
             const int slot = l + 64 * i, row = slot >> 5, pos = slot & 31, unit = pos ^ (row & 15);
             const E *src = A + (size_t)row * K + (size_t)c * GEMM_KC + 8 * unit;
             E *dst_l = xs + (size_t)buf * 16 * GEMM_KC + (size_t)(64 * i) * 8;
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst_l, 16, 0, 0);
+            if ((ROWS & 1) && i == AL - 1) { if (l < 32) __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst_l, 16, 0, 0); }   // (row ROWS is not fetched)
+            else __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst_l, 16, 0, 0);
             asm volatile("" ::: "memory");
         }
     };
@@ -912,6 +936,10 @@ static hipError_t pairs_silu_launch(hipStream_t st, int grid, const void *A, con
     return hipSuccess;
 }
 
+// activation rows the norm-fold projections can fetch: the two tile forms (8, 16) and the headline workload's two commonest draft
+// sizes (5 and 9 nodes: 75 % and 16 % of its steps, profiles/rows_exact.md)
+static bool samd_rows_fetch_ok(int rows) { return rows == 5 || rows == 8 || rows == 9 || rows == 16; }
+
 extern "C" {
 
 // choose the split-K factor.  Measured (scripts/gemm_bench.py, profiles/): the stream is fastest when the launch is ONE
@@ -970,9 +998,9 @@ int samd_gemm_pack_groups(const void *d_W, void *d_packed, int32_t N, int32_t K,
 
 int samd_gemm_pairs_silu_norm(const void *d_x, const float *d_ssq, const void *d_norm_weight, float eps, const void *d_Wg, int32_t rows_pad, int32_t inter, int32_t K,
                               void *d_out, int32_t dtype, void *stream) {
-    if (!d_x || !d_ssq || !d_norm_weight || !d_Wg || !d_out || (rows_pad != 16 && rows_pad != 8) || inter < 16 || inter % 16 != 0 || K < GEMM_KC || K % GEMM_KC != 0 ||
+    if (!d_x || !d_ssq || !d_norm_weight || !d_Wg || !d_out || !samd_rows_fetch_ok(rows_pad) || inter < 16 || inter % 16 != 0 || K < GEMM_KC || K % GEMM_KC != 0 ||
         K / 16 > 32 * NORM_NS || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
-        samd_set_error("samd_gemm_pairs_silu_norm: unsupported shape (8 or 16 rows, inter %% 16 == 0, K %% 256 == 0, K <= 8192, f16/bf16) or null pointer"); return SAMD_E_INVALID;
+        samd_set_error("samd_gemm_pairs_silu_norm: unsupported shape (5, 8, 9 or 16 rows, inter %% 16 == 0, K %% 256 == 0, K <= 8192, f16/bf16) or null pointer"); return SAMD_E_INVALID;
     }
     const int n_cu = samd_cu_count();
     const int n_pairs = inter / 16;
@@ -980,20 +1008,21 @@ int samd_gemm_pairs_silu_norm(const void *d_x, const float *d_ssq, const void *d
     while ((n_pairs + grid - 1) / grid > 4) grid += n_cu;
     const NormArgs na{d_ssq, d_norm_weight, K / 16, 1.f / (float)K, eps};
     hipStream_t st = (hipStream_t)stream;
-    // rows_pad 8: a draft of <= 8 nodes -- only rows 0..7 of x are fetched (the tile stays 16 rows; outputs of rows 8..15 are zero)
-    const hipError_t e = rows_pad == 8
-        ? (dtype == SAMD_F16 ? pairs_silu_launch<GF16, 1, 3, true, 8>(st, grid, d_x, d_Wg, d_out, K, inter, n_pairs, na)
-                             : pairs_silu_launch<GBF16, 1, 3, true, 8>(st, grid, d_x, d_Wg, d_out, K, inter, n_pairs, na))
-        : (dtype == SAMD_F16 ? pairs_silu_launch<GF16, 1, 3, true>(st, grid, d_x, d_Wg, d_out, K, inter, n_pairs, na)
-                             : pairs_silu_launch<GBF16, 1, 3, true>(st, grid, d_x, d_Wg, d_out, K, inter, n_pairs, na));
+    // rows_pad < 16: a draft of that many nodes -- only rows 0..rows_pad-1 of x are fetched (the tile stays 16 rows; outputs of the others are zero)
+    hipError_t e = hipSuccess;
+#define GO(TT, AR) e = pairs_silu_launch<TT, 1, 3, true, AR>(st, grid, d_x, d_Wg, d_out, K, inter, n_pairs, na)
+#define ROWS(TT) do { if (rows_pad == 5) GO(TT, 5); else if (rows_pad == 8) GO(TT, 8); else if (rows_pad == 9) GO(TT, 9); else GO(TT, 16); } while (0)
+    if (dtype == SAMD_F16) ROWS(GF16); else ROWS(GBF16);
+#undef ROWS
+#undef GO
     if (e != hipSuccess) { samd_set_error("samd_gemm_pairs_silu_norm: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
     LAUNCHCHK();
     return SAMD_OK;
 }
 
 int samd_gemm_cs_residual(const void *d_A, const void *d_Wg, int32_t rows_pad, int32_t N, int32_t K, void *d_x, float *d_ssq, int32_t dtype, void *stream) {
-    if (!d_A || !d_Wg || !d_x || !d_ssq || (rows_pad != 16 && rows_pad != 8) || N < 16 || N % 16 != 0 || K < GEMM_KC || K % GEMM_KC != 0 || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
-        samd_set_error("samd_gemm_cs_residual: unsupported shape (8 or 16 rows, N %% 16 == 0, K %% 256 == 0, f16/bf16) or null pointer"); return SAMD_E_INVALID;
+    if (!d_A || !d_Wg || !d_x || !d_ssq || !samd_rows_fetch_ok(rows_pad) || N < 16 || N % 16 != 0 || K < GEMM_KC || K % GEMM_KC != 0 || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("samd_gemm_cs_residual: unsupported shape (5, 8, 9 or 16 rows, N %% 16 == 0, K %% 256 == 0, f16/bf16) or null pointer"); return SAMD_E_INVALID;
     }
     constexpr int lds = GEMM_WAVES * 2 * 16 * GEMM_KC * 2;                       // 128 KiB: two A chunks per wave
     hipStream_t st = (hipStream_t)stream;
@@ -1001,8 +1030,9 @@ int samd_gemm_cs_residual(const void *d_A, const void *d_Wg, int32_t rows_pad, i
 #define GO(TT, ROWS, ET) do { static unsigned long long done = 0ull; \
         e = samd_reserve_lds((const void *)k_gemm_cs_residual<TT, ROWS>, lds, &done); \
         if (e == hipSuccess) hipLaunchKernelGGL((k_gemm_cs_residual<TT, ROWS>), dim3(N / 16), dim3(64 * GEMM_WAVES), lds, st, (const ET *)d_A, (const ET *)d_Wg, (ET *)d_x, d_ssq, K, N, K / GEMM_KC, (const int *)nullptr, (int *)nullptr, 0); } while (0)
-    if (dtype == SAMD_F16) { if (rows_pad == 8) GO(GF16, 8, _Float16); else GO(GF16, 16, _Float16); }
-    else { if (rows_pad == 8) GO(GBF16, 8, __bf16); else GO(GBF16, 16, __bf16); }
+#define ROWS(TT, ET) do { if (rows_pad == 5) GO(TT, 5, ET); else if (rows_pad == 8) GO(TT, 8, ET); else if (rows_pad == 9) GO(TT, 9, ET); else GO(TT, 16, ET); } while (0)
+    if (dtype == SAMD_F16) ROWS(GF16, _Float16); else ROWS(GBF16, __bf16);
+#undef ROWS
 #undef GO
     if (e != hipSuccess) { samd_set_error("samd_gemm_cs_residual: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
     LAUNCHCHK();
@@ -1121,8 +1151,8 @@ static int gemm_qkv_rope_norm_impl(const void *d_x, const float *d_ssq, const vo
                                    const float *d_cs, const int32_t *d_cache_length, const int32_t *d_n, void *d_q_out, void *d_k_cache, void *d_v_cache,
                                    int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t max_len, int32_t dtype, void *stream, int v_t) {
     if (!d_x || !d_ssq || !d_norm_weight || !d_W64 || !d_cs || !d_cache_length || !d_n || !d_q_out || !d_k_cache || !d_v_cache || head_dim != 128 || n_heads < 1 ||
-        n_kv_heads < 1 || (rows_pad != 16 && rows_pad != 8) || K < GEMM_KC || K % GEMM_KC != 0 || K / 16 > 32 * NORM_NS || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
-        samd_set_error("samd_gemm_qkv_rope_norm: unsupported shape (8 or 16 rows, head_dim 128, K %% 256 == 0, K <= 8192, f16/bf16) or null pointer"); return SAMD_E_INVALID;
+        n_kv_heads < 1 || !samd_rows_fetch_ok(rows_pad) || K < GEMM_KC || K % GEMM_KC != 0 || K / 16 > 32 * NORM_NS || (dtype != SAMD_F16 && dtype != SAMD_BF16)) {
+        samd_set_error("samd_gemm_qkv_rope_norm: unsupported shape (5, 8, 9 or 16 rows, head_dim 128, K %% 256 == 0, K <= 8192, f16/bf16) or null pointer"); return SAMD_E_INVALID;
     }
     const int groups = qkv_tile_groups(n_heads + 2 * n_kv_heads);
     const int tiles = (n_heads + 2 * n_kv_heads) * 128 / (16 * groups);
@@ -1130,14 +1160,11 @@ static int gemm_qkv_rope_norm_impl(const void *d_x, const float *d_ssq, const vo
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSuccess;
 #define GO(TT, CG, AR) e = qkv_rope_launch<TT, 1, 4, CG, true, AR>(st, d_x, d_W64, K, tiles, d_cs, d_cache_length, d_n, d_q_out, d_k_cache, d_v_cache, n_heads, n_kv_heads, (long long)max_len, v_t, na)
-    // rows_pad 8: a draft of <= 8 nodes -- only rows 0..7 of x are fetched (the tile stays 16 rows)
-    if (rows_pad == 8) {
-        if (groups == 3) { if (dtype == SAMD_F16) GO(GF16, 3, 8); else GO(GBF16, 3, 8); }
-        else { if (dtype == SAMD_F16) GO(GF16, 4, 8); else GO(GBF16, 4, 8); }
-    } else {
-        if (groups == 3) { if (dtype == SAMD_F16) GO(GF16, 3, 16); else GO(GBF16, 3, 16); }
-        else { if (dtype == SAMD_F16) GO(GF16, 4, 16); else GO(GBF16, 4, 16); }
-    }
+    // rows_pad < 16: a draft of that many nodes -- only rows 0..rows_pad-1 of x are fetched (the tile stays 16 rows)
+#define ROWS(TT, CG) do { if (rows_pad == 5) GO(TT, CG, 5); else if (rows_pad == 8) GO(TT, CG, 8); else if (rows_pad == 9) GO(TT, CG, 9); else GO(TT, CG, 16); } while (0)
+    if (groups == 3) { if (dtype == SAMD_F16) ROWS(GF16, 3); else ROWS(GBF16, 3); }
+    else { if (dtype == SAMD_F16) ROWS(GF16, 4); else ROWS(GBF16, 4); }
+#undef ROWS
 #undef GO
     if (e != hipSuccess) { samd_set_error("samd_gemm_qkv_rope_norm: %s", hipGetErrorString(e)); return SAMD_E_HIP; }
     LAUNCHCHK();

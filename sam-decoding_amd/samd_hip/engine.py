@@ -143,8 +143,8 @@ class ScriptedAcceptance:
         session.set_start_token(self.target[n:n + 1])          # the scripted LM's continuation of the prompt
         return last
 
-    def verify(self, session, R):
-        b = self.runner.verify(session, R)
+    def verify(self, session, R, rows_fetch=None):
+        b = self.runner.verify(session, R, rows_fetch=rows_fetch)
         session.scripted_argmax(self.target, self.target_len, self.vocab, b["argmax"])
         if self.ranked_logits:
             if self.order1_hot_vocab > 0:
@@ -159,8 +159,11 @@ class ScriptedAcceptance:
     def bucket(self, n):
         return self.runner.bucket(n)
 
-    def warm(self, R):
-        self.runner.warm(R)
+    def warm(self, R, rows_fetch=None):
+        self.runner.warm(R, rows_fetch=rows_fetch)
+
+    def rows_exact(self, R):
+        return self.runner.rows_exact(R)
 
     def hidden_rows(self, R):
         return self.runner.hidden_rows(R)
@@ -199,7 +202,10 @@ class DecodeEngine:
         self.report_buf = torch.zeros(REPORT_INTS, dtype=torch.int32).pin_memory()
         self._report_np = self.report_buf.numpy()
         self.use_graphs = use_graphs
-        self._graphs = {}
+        self._graphs = {}                    # row bucket -> the step's graph over the bucket's rows
+        # (bucket, n) -> the same step with the layer projections fetching exactly n activation rows (LlamaRunner.ROWS_EXACT), captured
+        # together with the bucket's graph and replayed when the draft has exactly n nodes -- the host knows n before it launches
+        self._graphs_exact = {}
         self.bucket_steps = {}               # row bucket -> decode steps run on it (bench.py: bucket_histogram)
         self._views = session.device_views()
         self._n_ptr = self._views["dmeta"] + 4
@@ -221,8 +227,20 @@ class DecodeEngine:
         self.recycle.draft(self._views["start_token"], self.tr_tokens)
         self.session.set_draft_if_deferred(self.tr_tokens, self.tr_parent, self.recycle.n_nodes, reverse=True)
 
-    def _enqueue_step(self, R):
-        b = self.verifier.verify(self.session, R)
+    def _verify(self, R, rows_fetch=None):
+        if rows_fetch is None:                                   # (plugin verifiers take no row count)
+            return self.verifier.verify(self.session, R)
+        return self.verifier.verify(self.session, R, rows_fetch=rows_fetch)
+
+    def _rows_exact(self, R):
+        """draft sizes of bucket R that get a graph of their own: the plain SAM-only engine over a runner that has the exact-row forward"""
+        fn = getattr(self.verifier, "rows_exact", None)
+        if fn is None or self.recycle is not None or type(self) is not DecodeEngine:
+            return ()
+        return tuple(fn(R))
+
+    def _enqueue_step(self, R, rows_fetch=None):
+        b = self._verify(R, rows_fetch)
         if self.recycle is not None:
             self._recycle_update(self._views["tokens"], b["logits"], min(R, MAX_DRAFT), C.c_void_p(self._n_ptr))
         self.session.step(self.static, self.params, b["argmax"])
@@ -280,6 +298,7 @@ class DecodeEngine:
             g = self._graphs.get(R)
             if g is None:
                 g = self._capture(R)                      # (before the sequence number is read: a capture warms the bucket with real launches)
+            g = self._graphs_exact.get((R, n_next), g)
         if push is not None:
             last = int(push[0][REPORT_INTS])
         if g is None:
@@ -386,10 +405,18 @@ class DecodeEngine:
         return StepReport(self._report_np)
 
     def _capture(self, R):
-        """capture the step for row bucket R.  Capture records the launches without executing them, so the request's
+        """capture the step for row bucket R, and with it the exact-row forms of the bucket's draft sizes that have one (_rows_exact):
+        every graph a later step of this bucket may replay exists when this returns."""
+        g = self._graphs[R] = self._capture_one(R)
+        for n in self._rows_exact(R):
+            self._graphs_exact[(R, n)] = self._capture_one(R, n)
+        return g
+
+    def _capture_one(self, R, rows_fetch=None):
+        """Capture records the launches without executing them, so the request's
         state is untouched; the verifier first runs the bucket once with n = 0 rows (no K/V write, every query row
         masked) so that library handles / workspaces exist before capture."""
-        self._warm(R)
+        self._warm(R, rows_fetch)
         torch.cuda.current_stream().synchronize()
         runner = getattr(self.verifier, "runner", self.verifier)
         cuts = [int(x) for x in os.environ.get("SAMD_GRAPH_SPLIT_LAYER", "2").split(",") if x.strip()]
@@ -404,7 +431,7 @@ class DecodeEngine:
         if not cuts and not eager:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._enqueue_step(R)
+                self._enqueue_step(R, rows_fetch)
         else:
             # SEVERAL graphs per step: hipGraphLaunch builds every packet of a graph before the GPU sees the first (~100 us for the step's
             # ~265 nodes, during which the GPU idles); a short head graph (the first layers) starts the GPU early and the rest is
@@ -415,7 +442,7 @@ class DecodeEngine:
                         raise _StopForward()
                 runner.layer_hook = stop
                 try:
-                    self.verifier.verify(self.session, R)
+                    self._verify(R, rows_fetch)
                 except _StopForward:
                     pass
                 finally:
@@ -442,7 +469,7 @@ class DecodeEngine:
                         g.parts[part[0]].capture_begin()
                 runner.layer_hook = hook
                 try:
-                    self._enqueue_step(R)
+                    self._enqueue_step(R, rows_fetch)
                 except BaseException:
                     # never leave the stream in capture mode: end the open part (its graph is discarded with `g`) before re-raising
                     runner.layer_hook = None
@@ -457,13 +484,15 @@ class DecodeEngine:
                     runner.layer_hook = None
                 g.parts[part[0]].capture_end()
             cur.wait_stream(side)
-        self._graphs[R] = g
         return g
 
-    def _warm(self, R):
+    def _warm(self, R, rows_fetch=None):
         v = self.verifier
         if hasattr(v, "warm"):
-            v.warm(R)
+            if rows_fetch is None:
+                v.warm(R)
+            else:
+                v.warm(R, rows_fetch=rows_fetch)
 
 
 class TreeModelEngine(DecodeEngine):

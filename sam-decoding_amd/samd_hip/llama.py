@@ -177,6 +177,10 @@ class LlamaRunner:
     # two 64-row tiles of the attention kernel; their projections go to the library GEMM (the streaming kernels' largest row tile is 64, and a
     # 128-row product is no longer a weight stream with a little MFMA attached), so this bucket needs the row-major matrices
     BUCKETS = (1, 8, 16, 32, 48, 64, 128)
+    # draft sizes whose verify forward fetches exactly the draft's activation rows instead of the bucket's (the norm-fold form: q|k|v,
+    # o_proj, gate|up, down_proj; buffers, attention and lm_head keep the bucket's geometry): the headline workload's two commonest
+    # sizes, 75 % and 16 % of its steps (profiles/rows_exact.md).  SAMD_ROWS_EXACT=0: the bucket's rows at every size.
+    ROWS_EXACT = (5, 9)
 
     def __init__(self, shape, weights, max_cache_len, dtype=torch.float16, device="cuda", kv=None, native_gemm=True, packed_lm_head=None,
                  attention=None, weight_format=None, draft_head=False, expert_format=MOE.AUTO):
@@ -1289,7 +1293,7 @@ class LlamaRunner:
                 return b
         raise SamdError(f"draft of {n} nodes exceeds {MAX_DRAFT}")
 
-    def forward_rows(self, R, d_tokens, d_relpos, d_mask, d_L, d_n, x_in=None, d_vis=None, _span=None):
+    def forward_rows(self, R, d_tokens, d_relpos, d_mask, d_L, d_n, x_in=None, d_vis=None, _span=None, rows_fetch=None):
         """one forward over R rows; all of d_* are device pointers (ints / tensors).  Returns the buffers of bucket R
         (logits [R, V], argmax int32[64] with rows < n valid).  x_in [R, hidden]: the rows' input states instead of the
         token embedding (EAGLE draft heads feed fc([embed ; hidden])).  With `self.draft_head` the decoder is an EAGLE head:
@@ -1298,7 +1302,9 @@ class LlamaRunner:
         launches from layer _span.first on, over _span.b (the bucket's buffers with x / h / cs replaced by the slice's own), with
         _span.delta folded into the residual by the first norm, up to the first sparse layer's MLP (not run: it is one wide call over all
         slices) or, past the last layer, the final norm / lm_head / arg-max if _span.head.  Returns (b, layer whose sparse MLP is due, or
-        the number of layers).  The launches of a stretch are this function's own, so a slice's bits are those of the chunked prefill."""
+        the number of layers).  The launches of a stretch are this function's own, so a slice's bits are those of the chunked prefill.
+        rows_fetch (the norm-fold form only, see rows_exact; ignored elsewhere): the draft's own node count when the host knows it -- the
+        layer projections then fetch exactly that many activation rows; rows < rows_fetch of every result are the bucket form's bits."""
         if self.shape.moe:
             MOE.reject_unsupported(draft_head=getattr(self, "draft_head", False))     # (an attribute set after construction)
         if self._rows_pad(R) > self.native_gemm_max_rows and self.row_major_released:      # (before the bucket's buffers exist)
@@ -1309,7 +1315,7 @@ class LlamaRunner:
         resumed = _span is not None and _span.first > 0           # embedding and the rows' cos | sin were made by the slice's first stretch
         if (_span is None and self.norm_fold and RP == 16 and x_in is None and d_vis is None and not getattr(self, "draft_head", False)
                 and RP <= self.native_gemm_max_rows):
-            return self._forward_rows_fold(R, b, d_tokens, d_relpos, d_mask, d_L, d_n)
+            return self._forward_rows_fold(R, b, d_tokens, d_relpos, d_mask, d_L, d_n, rows_fetch)
 
         def hint(w, wp, fused=False, is_head=False):
             """samd_warm_t of the projection (w row-major, wp packed) that follows a glue launch, or None"""
@@ -1459,7 +1465,7 @@ class LlamaRunner:
             check(L.samd_argmax_rows(_ptr(b["logits"]), dt, R, s.vocab, s.vocab, None, _ptr(b["argmax"]), st))
         return b if _span is None else (b, len(self.w["layers"]))
 
-    def _forward_rows_fold(self, R, b, d_tokens, d_relpos, d_mask, d_L, d_n):
+    def _forward_rows_fold(self, R, b, d_tokens, d_relpos, d_mask, d_L, d_n, rows_fetch=None):
         """forward_rows at <= 16 rows in the norm-fold form: the residual stream b["x"] is complete after every projection that adds to it
         (samd_gemm_cs_residual: complete sums + residual + the rows' sums of squares), and input_layernorm / post_attention_layernorm are
         applied by the q|k|v and gate|up projections on their way into LDS.  Six launches per decoder layer instead of eight."""
@@ -1467,6 +1473,10 @@ class LlamaRunner:
         x, ssq = b["x"], b["ssq"]
         rows_cs = 8 if R <= 8 else 16            # the complete-sum projections fetch only the rows a <= 8-node draft has
         rows_a = rows_cs if os.environ.get("SAMD_NORM_ROWS8", "1") != "0" else 16      # ... and so do the norm-applying ones (round 4)
+        if rows_fetch is not None:               # the draft's own size, known on the host: both fetch exactly its rows (ROWS_EXACT)
+            if rows_fetch not in self.ROWS_EXACT or self.bucket(rows_fetch) != R:
+                raise SamdError(f"rows_fetch {rows_fetch} is not an exact-row form of bucket {R}")
+            rows_cs = rows_a = rows_fetch
         if s.head_dim == 128 and os.environ.get("SAMD_FUSE_EMBED_ROPE", "1") != "0":
             # embedding rows + their sums of squares and the rows' cos | sin: one launch (neither depends on the other)
             check(L.samd_embed_rows_ssq_rope(_ptr(d_tokens), _ptr(self.w["embed"]), _ptr(x), _ptr(ssq), 16, s.hidden, s.vocab, dt, _ptr(d_relpos), _ptr(d_L),
@@ -1810,12 +1820,12 @@ class LlamaRunner:
         session.set_start_token(b["argmax"])
         return b["logits"][0]
 
-    def warm(self, R):
-        """run the launch sequence of bucket R once with n = 0 rows (no K/V row is written, every query row is
-        masked): creates the GEMM library's handles/workspaces before hipGraph capture without touching the request."""
+    def warm(self, R, rows_fetch=None):
+        """run the launch sequence of bucket R (of its exact-row form with rows_fetch) once with n = 0 rows (no K/V row is written, every
+        query row is masked): creates the GEMM library's handles/workspaces before hipGraph capture without touching the request."""
         self.pf_n.zero_()
         scratch_L = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.forward_rows(R, self.pf_tokens, self.pf_relpos, self.pf_mask, scratch_L, self.pf_n)
+        self.forward_rows(R, self.pf_tokens, self.pf_relpos, self.pf_mask, scratch_L, self.pf_n, rows_fetch=rows_fetch)
         torch.cuda.current_stream().synchronize()
 
     def hidden_rows(self, R):
@@ -1836,11 +1846,18 @@ class LlamaRunner:
         torch.cuda.current_stream().synchronize()
         return (b["logits"][:n], b["h"][:n]) if return_hidden else b["logits"][:n]
 
-    def verify(self, session: Session, R):
-        """SamdModel.decode's LM call (SO/samd_model.py:134-138) on the session's current draft."""
+    def rows_exact(self, R):
+        """the draft sizes of bucket R that have an exact-row forward on this runner (see ROWS_EXACT)"""
+        if (not self.norm_fold or self._rows_pad(R) != 16 or self.native_gemm_max_rows < 16 or getattr(self, "draft_head", False)
+                or os.environ.get("SAMD_ROWS_EXACT", "1") == "0"):
+            return ()
+        return tuple(n for n in self.ROWS_EXACT if self.bucket(n) == R)
+
+    def verify(self, session: Session, R, rows_fetch=None):
+        """SamdModel.decode's LM call (SO/samd_model.py:134-138) on the session's current draft (rows_fetch: see forward_rows)."""
         v = session.device_views()
         n_ptr = C.c_void_p(v["dmeta"] + 4)          # dmeta[D_N]
-        return self.forward_rows(R, v["tokens"], v["position"], v["mask"], v["cache_length"], n_ptr)
+        return self.forward_rows(R, v["tokens"], v["position"], v["mask"], v["cache_length"], n_ptr, rows_fetch=rows_fetch)
 
     def compact(self, session: Session):
         """SamdStaticCache.select_indices (SO/cache.py:118-133) for all 2 x layers tensors in one launch."""
