@@ -22,6 +22,7 @@ from . import mxfp4 as MX
 from . import int4 as I4
 from . import int8 as I8
 from . import moe as MOE
+from .formats import DENSE, DENSE_FORMATS, PROJECTIONS, QUANT_FORMATS, is_f4_tensor as _is_f4_tensor
 
 
 def _env_weight_format(weight_format):
@@ -30,20 +31,14 @@ def _env_weight_format(weight_format):
 
 
 def _weight_format(weight_format, weights, dtype):
-    """"fp8", "fp8b128", "mxfp4", "int4g128", "int8g128" or None (the model dtype; the plain word "int4" stays an unknown format: the name carries the group size).  Projections that arrive as float8_e4m3fn (an FP8 checkpoint), as packed e2m1 bytes
-    (an MXFP4 checkpoint: uint8 / float4_e2m1fn_x2 [N, K/2]) or as 4-bit codes with zero points and group scales (an AWQ / GPTQ checkpoint:
-    uint8 [N, K/2] beside k + "_z" and k + "_s") make the runner FP8 / MXFP4 / INT4 by themselves.  float8_e4m3fn projections beside k + "_sinv"
-    (fp32, one scale per 128 x 128 block) are block-scaled FP8 and make the runner "fp8b128": the _sinv keys tell them from per-row "fp8".
-    8-bit codes with zero points and group scales (a GPTQ 8-bit checkpoint: uint8 [N, K] beside k + "_z8" and k + "_s8") make it "int8g128"."""
-    has_i8 = any(k + "_z8" in l for l in weights["layers"] for k in I8.PROJECTIONS)
-    has_f8b = any(k + "_sinv" in l for l in weights["layers"] for k in F8.PROJECTIONS)
-    has_f8 = any(l[k].dtype == torch.float8_e4m3fn and k + "_sinv" not in l for l in weights["layers"] for k in F8.PROJECTIONS if k in l)
-    has_i4 = any(k + "_z" in l for l in weights["layers"] for k in I4.PROJECTIONS)
-    has_f4 = any(_is_f4_tensor(l[k]) and k + "_z" not in l and k + "_z8" not in l for l in weights["layers"] for k in MX.PROJECTIONS if k in l)
+    """a name of QUANT_FORMATS or None (the model dtype), from the argument and from what the projections of `weights` arrive as: each
+    record of formats.DENSE_FORMATS says how a raw dict shows its format, and such projections make the runner that format by themselves;
+    any other weight_format against them raises."""
+    carried = [f for f in DENSE_FORMATS if f.carried_by(weights)]
     names = {torch.float16: ("fp16", "float16", "half"), torch.bfloat16: ("bf16", "bfloat16")}.get(dtype, ())
     if weight_format is None:
-        fmt = "fp8" if has_f8 else ("fp8b128" if has_f8b else ("mxfp4" if has_f4 else ("int4g128" if has_i4 else ("int8g128" if has_i8 else None))))
-    elif weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128", "int8g128"):
+        fmt = carried[0].name if carried else None
+    elif weight_format in QUANT_FORMATS:
         fmt = weight_format
     elif weight_format == dtype or (isinstance(weight_format, str) and weight_format.lower() in names):
         fmt = None
@@ -51,20 +46,10 @@ def _weight_format(weight_format, weights, dtype):
         hint = " (the AWQ / GPTQ format is spelled 'int4g128': 4-bit codes in groups of 128, the only group size the kernel has)" \
             if weight_format == "int4" else ""
         raise SamdError(f"weight_format {weight_format!r}: expected None, 'fp8', 'mxfp4', 'int4g128', 'fp8b128' or the model dtype ({dtype}), or 'int8g128'{hint}")
-    if has_f8 and fmt != "fp8":
-        raise SamdError(f"the weights carry float8_e4m3fn projections; weight_format {weight_format!r} would need them dequantised (pass None or 'fp8')")
-    if has_f8b and fmt != "fp8b128":
-        raise SamdError(f"the weights carry block-scaled FP8 projections; weight_format {weight_format!r} would need them dequantised (pass None or 'fp8b128')")
-    if has_f4 and fmt != "mxfp4":
-        raise SamdError(f"the weights carry MXFP4 projections; weight_format {weight_format!r} would need them dequantised (pass None or 'mxfp4')")
-    if has_i4 and fmt != "int4g128":
-        raise SamdError(f"the weights carry INT4 (AWQ / GPTQ) projections; weight_format {weight_format!r} would need them dequantised (pass None or 'int4g128')")
-    if has_i8 and fmt != "int8g128":
-        raise SamdError(f"the weights carry INT8 (GPTQ) projections; weight_format {weight_format!r} would need them dequantised (pass None or 'int8g128')")
+    for f in carried:
+        if fmt != f.name:
+            raise SamdError(f"the weights carry {f.label} projections; weight_format {weight_format!r} would need them dequantised (pass None or '{f.name}')")
     return fmt
-
-
-QUANT_FORMATS = ("fp8", "fp8b128", "mxfp4", "int4g128", "int8g128")
 
 
 def quant_prefill_min_rows(default):
@@ -81,10 +66,6 @@ def quant_prefill_min_rows(default):
     if rows < 2 * TILE_ROWS or rows % TILE_ROWS != 0:
         raise SamdError(f"SAMD_QUANT_PREFILL_MIN_ROWS={rows}: must be a multiple of 64 and >= 128")
     return rows
-
-
-def _is_f4_tensor(t):
-    return t.dtype == torch.uint8 or MX.is_fp4_dtype(t.dtype)
 
 
 def _cfg_get(cfg, name, default=None):
@@ -184,99 +165,31 @@ class LlamaRunner:
 
     def __init__(self, shape, weights, max_cache_len, dtype=torch.float16, device="cuda", kv=None, native_gemm=True, packed_lm_head=None,
                  attention=None, weight_format=None, draft_head=False, expert_format=MOE.AUTO):
-        # expert_format "mxfp4": the experts of every sparse layer, and nothing else, as MXFP4 (samd_hip/moe.py); the default takes env
-        # SAMD_EXPERT_FORMAT, and 4-bit expert tensors in `weights` make the runner "mxfp4" by themselves.  A knob of its own: weight_format
-        # means the four dense projections and stays rejected for models with sparse layers
-        # expert_format "int4g128": the experts as AWQ / GPTQ INT4 (codes + "_z" zero points + "_s" scales in the model dtype: the _z / _s keys
-        # tell them from MXFP4's "_scale"); INT4 expert tensors make the runner "int4g128" by themselves
-        # expert_format "fp8b128": the experts as block-scaled FP8 (float8_e4m3fn codes, or their bytes, + "_sinv" fp32 scales per 128 x 128
-        # block: the _sinv keys tell them from the others); such tensors make the runner "fp8b128" by themselves
-        # expert_format "int8g128": the experts as GPTQ INT8 (uint8 codes [E, N, K] + "_z8" zero points + "_s8" scales in the model dtype: the
-        # dense INT8 projections' suffixes, which no other expert format uses); such tensors make the runner "int8g128" by themselves
-        sparse_l = [l for l in weights["layers"] if "experts_gu" in l]
-        experts_i8 = [any(k in l for k in ("experts_gu_z8", "experts_gu_s8", "experts_down_z8", "experts_down_s8")) for l in sparse_l]
-        experts_i4 = [any(k in l for k in ("experts_gu_z", "experts_gu_s", "experts_down_z", "experts_down_s")) for l in sparse_l]
-        experts_f8 = [any(k in l for k in ("experts_gu_sinv", "experts_down_sinv")) or F8.is_fp8_dtype(l["experts_gu"].dtype)
-                      or F8.is_fp8_dtype(l["experts_down"].dtype) for l in sparse_l]
-        experts4 = [not i4e and not f8e and not i8e and (MOE.is_4bit(l["experts_gu"]) or MOE.is_4bit(l["experts_down"]))
-                    for l, i4e, f8e, i8e in zip(sparse_l, experts_i4, experts_f8, experts_i8)]
-        self.expert_format = MOE.resolve_expert_format(expert_format, any(experts4), shape.moe, carries_int4=any(experts_i4),
-                                                       carries_fp8=any(experts_f8), carries_int8=any(experts_i8))   # (before any device work, as the next)
+        # expert_format: the experts of every sparse layer, and nothing else, in one of moe.EXPERT's formats; the default takes env
+        # SAMD_EXPERT_FORMAT, and quantised expert tensors in `weights` make the runner their format by themselves.  A knob of its own:
+        # weight_format means the four dense projections and stays rejected for models with sparse layers
+        carried = MOE.experts_carried(weights["layers"])
+        self.expert_format = MOE.resolve_carried(expert_format, carried, shape.moe)       # (before any device work, as the next)
         if shape.moe:
             MOE.reject_unsupported(_weight_format(weight_format, weights, dtype), native_gemm, draft_head)
-        if any(experts4):
-            if not all(experts4):
-                raise SamdError(f"a mix of 4-bit and model-dtype sparse layers ({sum(experts4)} of {len(experts4)} carry MXFP4 experts): "
-                                "the runner takes the experts of all sparse layers in one format")
-            for i, l in enumerate(weights["layers"]):
-                if "experts_gu" in l:
-                    MOE.check_quantised_experts(l["experts_gu"], l.get("experts_gu_scale"), l["experts_down"], l.get("experts_down_scale"), dtype,
-                                                f"layer {i} experts")
-        if any(experts_i4):
-            if not all(experts_i4):
-                raise SamdError(f"a mix of INT4 and other sparse layers ({sum(experts_i4)} of {len(experts_i4)} carry INT4 experts): "
-                                "the runner takes the experts of all sparse layers in one format")
-            for i, l in enumerate(weights["layers"]):
-                if "experts_gu" in l:
-                    MOE.check_int4_experts((l["experts_gu"], l.get("experts_gu_z"), l.get("experts_gu_s")),
-                                           (l["experts_down"], l.get("experts_down_z"), l.get("experts_down_s")), dtype, f"layer {i} experts")
-        if any(experts_i8):
-            if not all(experts_i8):
-                raise SamdError(f"a mix of INT8 and other sparse layers ({sum(experts_i8)} of {len(experts_i8)} carry INT8 experts): "
-                                "the runner takes the experts of all sparse layers in one format")
-            for i, l in enumerate(weights["layers"]):
-                if "experts_gu" in l:
-                    MOE.check_int8_experts((l["experts_gu"], l.get("experts_gu_z8"), l.get("experts_gu_s8")),
-                                           (l["experts_down"], l.get("experts_down_z8"), l.get("experts_down_s8")), dtype, f"layer {i} experts")
-        if any(experts_f8):
-            if not all(experts_f8):
-                raise SamdError(f"a mix of block-scaled FP8 and other sparse layers ({sum(experts_f8)} of {len(experts_f8)} carry FP8 experts): "
-                                "the runner takes the experts of all sparse layers in one format")
-            for i, l in enumerate(weights["layers"]):
-                if "experts_gu" in l:
-                    MOE.check_fp8_experts((l["experts_gu"], l.get("experts_gu_sinv")), (l["experts_down"], l.get("experts_down_sinv")),
-                                          f"layer {i} experts")
+        for name, c in carried.items():
+            if any(c):
+                MOE.EXPERT[name].check_layers(weights["layers"], c, dtype)
         self.draft_head = bool(draft_head)                       # the decoder is an EAGLE head (forward_rows)
         require_gpu()
         self.shape, self.dtype, self.device = shape, dtype, torch.device(device)
         self.dt = torch_dtype_code(dtype)
         if self.dt not in (F16, BF16):
             raise SamdError("LlamaRunner computes in fp16 or bf16")
-        # weight_format "fp8": the four projections of every layer as OCP e4m3fn with one fp32 scale per output column (samd_hip/fp8.py),
-        # streamed by samd_gemm_skinny_f8 only -- no row-major copy, no fused or norm-fold forms; embedding and lm_head stay in the model dtype
+        # weight_format: the four projections of every layer in one of formats.DENSE_FORMATS, streamed by that format's kernel only
         self.weight_format = _weight_format(weight_format, weights, dtype)
-        # weight_format "mxfp4": the same four projections as e2m1 elements with one e8m0 scale per 32 along K (samd_hip/mxfp4.py), streamed by
-        # samd_gemm_skinny_f4 only; everything FP8 implies for the runner holds here too (quant)
-        # weight_format "int4g128": the same four projections as AWQ / GPTQ 4-bit codes with one scale (model dtype) and one zero point per 128 along
-        # K (samd_hip/int4.py), streamed by samd_gemm_skinny_i4 only; again everything FP8 implies holds
-        # weight_format "fp8b128": the same four projections as OCP e4m3fn with one fp32 scale per 128 x 128 block (the weight / weight_scale_inv
-        # of transformers' fine-grained FP8 checkpoints; samd_hip/fp8.py has the contract), streamed by samd_gemm_skinny_f8b only from
-        # (samd_gemm_pack_f8's packed codes, the checkpoint's own scale table); again everything FP8 implies holds
-        f8, f4, i4 = self.weight_format == "fp8", self.weight_format == "mxfp4", self.weight_format == "int4g128"
-        f8b = self.weight_format == "fp8b128"
-        # weight_format "int8g128": the same four projections as GPTQ 8-bit codes with one scale (model dtype) and one zero point per 128 along K
-        # (samd_hip/int8.py), streamed by samd_gemm_skinny_i8 only; again everything FP8 implies holds
-        i8 = self.weight_format == "int8g128"
-        quant = f8 or f4 or i4 or f8b or i8
-        if i8 and not native_gemm:
-            raise SamdError("INT8 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'int8g128'")
-        if f8b and not native_gemm:
-            raise SamdError("FP8 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'fp8b128'")
-        if f8b:                                                  # shapes the kernel cannot run, by projection, before any device work
-            if shape.inter % 128 != 0:
-                raise SamdError(f"block-scaled FP8 projection wgu: intermediate_size {shape.inter} is not a multiple of 128, so a 128 x 128 block "
-                                "would straddle gate and up")
-            for li, l in enumerate(weights["layers"]):
-                for k in F8.PROJECTIONS:
-                    N, K = l[k].shape
-                    if N % 128 != 0 or K % 256 != 0:
-                        raise SamdError(f"block-scaled FP8 projection {k} of layer {li}, shape ({N}, {K}): the kernel needs N % 128 == 0 and K % 256 == 0")
-        if f8 and not native_gemm:
-            raise SamdError("FP8 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'fp8'")
-        if f4 and not native_gemm:
-            raise SamdError("MXFP4 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'mxfp4'")
-        if i4 and not native_gemm:
-            raise SamdError("INT4 projections exist only in the streaming kernel's packed form: native_gemm=False is not available with weight_format 'int4g128'")
+        fmt = self._fmt = DENSE.get(self.weight_format)
+        quant = fmt is not None
+        if quant and not native_gemm:
+            raise SamdError(f"{fmt.short} projections exist only in the streaming kernel's packed form: native_gemm=False is not available "
+                            f"with weight_format '{fmt.name}'")
+        if quant and fmt.precheck is not None:
+            fmt.precheck(shape, weights)
         s = shape
         self.w = weights
         # samd_gemm_skinny streams the weights itself where the shape allows (N % 128 == 0, K % 256 == 0); a projection that
@@ -365,125 +278,13 @@ class LlamaRunner:
             out = torch.empty_like(t)
             check(lib().samd_gemm_pack_groups(_ptr(t), _ptr(out), t.shape[0], t.shape[1], current_stream()))
             return out
-        def pack_f8(l, k):
-            """(packed e4m3fn bytes, fp32 column scales) of projection k: quantised on load (symmetric per row) unless the checkpoint
-            brought its own (q, scale); the model-dtype matrix is dropped as soon as it is packed"""
-            t = l[k]
-            N, K = t.shape
-            if N % 128 != 0 or K % 256 != 0:
-                raise SamdError(f"FP8 projection {k} of shape {tuple(t.shape)}: the FP8 kernel needs N % 128 == 0 and K % 256 == 0")
-            if t.dtype == torch.float8_e4m3fn:
-                q, scale = t.to(self.device).contiguous(), l.pop(k + "_scale").to(device=self.device, dtype=torch.float32).contiguous()
-            else:
-                q, scale = F8.quantize_rows(t)
-            l[k] = torch.empty(t.shape, dtype=torch.float8_e4m3fn, device="meta")
-            del t
-            out = torch.empty_like(q)
-            check(lib().samd_gemm_pack_f8(_ptr(q), _ptr(out), N, K, current_stream()))
-            return out, scale
-        def pack_f8b(l, k):
-            """(packed e4m3fn bytes, fp32 [N/128][K/128] block scales) of projection k: quantised on load (symmetric per 128 x 128 block,
-            uncalibrated) unless the checkpoint brought its own (q, s), which are taken as they are -- the codes packed by samd_gemm_pack_f8,
-            the table untouched; the model-dtype matrix is dropped as soon as it is packed"""
-            t = l[k]
-            N, K = t.shape
-            if t.dtype == torch.float8_e4m3fn:
-                q, sinv = t.to(self.device).contiguous(), l.pop(k + "_sinv").to(device=self.device).contiguous()
-                F8.check_block_scales(q, sinv, f"block-scaled FP8 projection {k}")
-            else:
-                q, sinv = F8.quantize_blocks(t)
-            l[k] = torch.empty(t.shape, dtype=torch.float8_e4m3fn, device="meta")
-            del t
-            out = torch.empty_like(q)
-            check(lib().samd_gemm_pack_f8(_ptr(q), _ptr(out), N, K, current_stream()))
-            return out, sinv
-        def pack_f4(l, k):
-            """projection k in samd_gemm_pack_f4's form (e2m1 elements with their e8m0 block scales inline): quantised on load per block of 32
-            unless the checkpoint brought its own (q, e8), whose exponents must lie in the model dtype's exact range; the model-dtype matrix
-            is dropped as soon as it is packed"""
-            t = l[k]
-            N, K = (t.shape[0], 2 * t.shape[1]) if _is_f4_tensor(t) else t.shape
-            if N % 128 != 0 or K % 256 != 0:
-                raise SamdError(f"MXFP4 projection {k} of shape ({N}, {K}): the MXFP4 kernel needs N % 128 == 0 and K % 256 == 0")
-            if _is_f4_tensor(t):
-                q, e8 = MX.fuse_mxfp4([(t, l.pop(k + "_e8"))], self.device)
-                if tuple(e8.shape) != (N, K // 32):
-                    raise SamdError(f"MXFP4 projection {k}: block scales of shape {tuple(e8.shape)} for a ({N}, {K}) matrix")
-                MX.check_exponents(e8, dtype, f"MXFP4 projection {k}")
-            else:
-                q, e8 = MX.quantize_blocks(t, dtype)
-            l[k] = torch.empty((N, K), dtype=torch.uint8, device="meta")
-            del t
-            out = torch.empty(MX.packed_bytes(N, K), dtype=torch.uint8, device=self.device)
-            check(lib().samd_gemm_pack_f4(_ptr(q), _ptr(e8), _ptr(out), N, K, current_stream()))
-            return out
-        def pack_i4(l, k):
-            """projection k in samd_gemm_pack_i4's form (4-bit codes with their group scales and zero points inline): quantised on load per
-            group of 128 (uncalibrated) unless the checkpoint brought its own (q, z, s), whose scales are taken in the model dtype (a bf16
-            runner rounds fp16 scales once) and checked; the model-dtype matrix is dropped as soon as it is packed"""
-            t = l[k]
-            if k + "_z" in l:
-                q, z, sc = I4.fuse_int4([(t, l.pop(k + "_z"), l.pop(k + "_s"))], self.device, dtype)
-            else:
-                if t.shape[0] % 128 != 0 or t.shape[1] % 256 != 0:
-                    raise SamdError(f"INT4 projection {k} of shape {tuple(t.shape)}: the INT4 kernel needs N % 128 == 0 and K % 256 == 0")
-                q, z, sc = I4.quantize_groups(t, dtype)
-            I4.check_groups(q, z, sc, dtype, k)
-            N, K = q.shape[0], 2 * q.shape[1]
-            l[k] = torch.empty((N, K), dtype=torch.uint8, device="meta")
-            del t
-            out = torch.empty(I4.packed_bytes(N, K), dtype=torch.uint8, device=self.device)
-            check(lib().samd_gemm_pack_i4(_ptr(q), _ptr(z), _ptr(sc), _ptr(out), N, K, self.dt, current_stream()))
-            return out
-        def pack_i8(l, k):
-            """projection k in samd_gemm_pack_i8's form (8-bit codes with their group scales and zero points inline): quantised on load per
-            group of 128 (uncalibrated) unless the checkpoint brought its own (q, z, s), whose scales are taken in the model dtype (a bf16
-            runner rounds fp16 scales once) and checked; the model-dtype matrix is dropped as soon as it is packed"""
-            t = l[k]
-            if k + "_z8" in l:
-                q, z, sc = I8.fuse_int8([(t, l.pop(k + "_z8"), l.pop(k + "_s8"))], self.device, dtype)
-            else:
-                if t.shape[0] % 128 != 0 or t.shape[1] % 256 != 0:
-                    raise SamdError(f"INT8 projection {k} of shape {tuple(t.shape)}: the INT8 kernel needs N % 128 == 0 and K % 256 == 0")
-                q, z, sc = I8.quantize_groups(t, dtype)
-            I8.check_groups(q, z, sc, dtype, k)
-            N, K = q.shape
-            l[k] = torch.empty((N, K), dtype=torch.uint8, device="meta")
-            del t
-            out = torch.empty(I8.packed_bytes(N, K), dtype=torch.uint8, device=self.device)
-            check(lib().samd_gemm_pack_i8(_ptr(q), _ptr(z), _ptr(sc), _ptr(out), N, K, self.dt, current_stream()))
-            return out
         # packed_lm_head: a draft head shares the base model's lm_head, packed copy included
         layers = []
         for l in weights["layers"]:
-            if i8:
+            if quant:
                 lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
-                for k in I8.PROJECTIONS:
-                    lp[k + "_i8"] = pack_i8(l, k)
-                layers.append(lp)
-                continue
-            if i4:
-                lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
-                for k in I4.PROJECTIONS:
-                    lp[k + "_i4"] = pack_i4(l, k)
-                layers.append(lp)
-                continue
-            if f4:
-                lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
-                for k in MX.PROJECTIONS:
-                    lp[k + "_f4"] = pack_f4(l, k)
-                layers.append(lp)
-                continue
-            if f8:
-                lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
-                for k in F8.PROJECTIONS:
-                    lp[k + "_f8"] = pack_f8(l, k)
-                layers.append(lp)
-                continue
-            if f8b:
-                lp = dict(wqkv=None, wqkv64=None, wo=None, wo_g=None, wgu=None, wdown=None, wdown_g=None)
-                for k in F8.PROJECTIONS:
-                    lp[k + "_f8b"] = pack_f8b(l, k)
+                for k in PROJECTIONS:
+                    lp[k + fmt.suffix] = fmt.pack(l, k, self.device, dtype, self.dt)
                 layers.append(lp)
                 continue
             sparse = "experts_gu" in l
@@ -496,60 +297,19 @@ class LlamaRunner:
                     and not moe)
             if sparse:
                 # the experts packed once (per expert the 128-column tiles of the streaming GEMM, gate | up interleaved); no row-major copy stays
-                gu_cols = s.hidden // 2 if MOE.is_4bit(l["experts_gu"]) and "experts_gu_sinv" not in l and "experts_gu_z8" not in l else s.hidden
+                efmt = MOE.EXPERT[self.expert_format]
+                take = efmt.quantize is None or any(carried[efmt.name])      # the checkpoint's own tensors (already checked), else quantised here
+                gu_cols = s.hidden // efmt.codes_per_byte if take else s.hidden
                 if tuple(l["router"].shape) != (s.n_experts, s.hidden) or tuple(l["experts_gu"].shape) != (s.n_experts, 2 * s.moe_inter, gu_cols):
                     raise SamdError(f"sparse layer weights of shapes {tuple(l['router'].shape)}, {tuple(l['experts_gu'].shape)} do not match the shape")
-                if self.expert_format == "mxfp4":
-                    # the experts as e2m1 + e8m0 (the checkpoint's own, already checked, or quantised here), packed once; only shapes stay
-                    ekeys = ("experts_gu", "experts_gu_scale", "experts_down", "experts_down_scale")
-                    if MOE.is_4bit(l["experts_gu"]):
-                        quad = tuple(MX._bytes(l[k]).to(self.device).contiguous() for k in ekeys)
-                    else:
-                        quad = MOE.quantize_experts(l["experts_gu"], l["experts_down"], dtype, f"layer {len(layers)} experts")
-                    lp["moe_gu"], lp["moe_down"] = MOE.pack_experts_mxfp4(*quad)
-                    for k, t in zip(ekeys, quad):
-                        l[k] = torch.empty(t.shape, dtype=torch.uint8, device="meta")
-                    del quad
-                elif self.expert_format == "int4g128":
-                    # the experts as codes + zero points + scales (the checkpoint's own, already checked, or quantised here), packed once for
-                    # this dtype; only shapes stay
-                    gkeys, dkeys = ("experts_gu", "experts_gu_z", "experts_gu_s"), ("experts_down", "experts_down_z", "experts_down_s")
-                    if "experts_gu_z" in l:
-                        gu3, dn3 = (tuple(l[k].to(self.device).contiguous() for k in ks) for ks in (gkeys, dkeys))
-                    else:
-                        gu3, dn3 = MOE.quantize_experts_int4(l["experts_gu"], l["experts_down"], dtype, f"layer {len(layers)} experts")
-                    lp["moe_gu"], lp["moe_down"] = MOE.pack_experts_int4(gu3, dn3, dtype)
-                    for k, t in zip(gkeys + dkeys, gu3 + dn3):
-                        l[k] = torch.empty(t.shape, dtype=t.dtype, device="meta")
-                    del gu3, dn3
-                elif self.expert_format == "int8g128":
-                    # the experts as 8-bit codes + zero points + scales (the checkpoint's own, already checked, or quantised here), packed once
-                    # for this dtype; only shapes stay
-                    gkeys, dkeys = ("experts_gu", "experts_gu_z8", "experts_gu_s8"), ("experts_down", "experts_down_z8", "experts_down_s8")
-                    if "experts_gu_z8" in l:
-                        gu3, dn3 = (tuple(l[k].to(self.device).contiguous() for k in ks) for ks in (gkeys, dkeys))
-                    else:
-                        gu3, dn3 = MOE.quantize_experts_int8(l["experts_gu"], l["experts_down"], dtype, f"layer {len(layers)} experts")
-                    lp["moe_gu"], lp["moe_down"] = MOE.pack_experts_int8(gu3, dn3, dtype)
-                    for k, t in zip(gkeys + dkeys, gu3 + dn3):
-                        l[k] = torch.empty(t.shape, dtype=t.dtype, device="meta")
-                    del gu3, dn3
-                elif self.expert_format == "fp8b128":
-                    # the experts as e4m3fn codes + one fp32 scale per 128 x 128 block (the checkpoint's own, already checked, or quantised
-                    # here), packed once (the buffer serves both model dtypes); only shapes stay
-                    gkeys, dkeys = ("experts_gu", "experts_gu_sinv"), ("experts_down", "experts_down_sinv")
-                    if "experts_gu_sinv" in l:
-                        gu2, dn2 = (tuple(l[k].to(self.device).contiguous() for k in ks) for ks in (gkeys, dkeys))
-                    else:
-                        gu2, dn2 = MOE.quantize_experts_fp8(l["experts_gu"], l["experts_down"], f"layer {len(layers)} experts")
-                    lp["moe_gu"], lp["moe_down"] = MOE.pack_experts_fp8(gu2, dn2)
-                    for k, t in zip(gkeys + dkeys, gu2 + dn2):
-                        l[k] = torch.empty(t.shape, dtype=torch.float8_e4m3fn if t.dtype == torch.uint8 else t.dtype, device="meta")
-                    del gu2, dn2
+                if take:
+                    gu, dn = (tuple(efmt.raw_view(l[k]).to(self.device).contiguous() for k in ks) for ks in (efmt.gu_keys, efmt.down_keys))
                 else:
-                    lp["moe_gu"], lp["moe_down"] = MOE.pack_experts(l["experts_gu"], l["experts_down"])
-                    for k in ("experts_gu", "experts_down"):
-                        l[k] = torch.empty(l[k].shape, dtype=l[k].dtype, device="meta")
+                    gu, dn = efmt.quantize(l["experts_gu"], l["experts_down"], dtype, f"layer {len(layers)} experts")
+                lp["moe_gu"], lp["moe_down"] = efmt.pack(gu, dn, dtype)       # packed once; only shapes stay
+                for k, t in zip(efmt.gu_keys + efmt.down_keys, gu + dn):
+                    l[k] = torch.empty(t.shape, dtype=efmt.meta_dtype(t), device="meta")
+                del gu, dn
                 lp["wo_g"], lp["wdown_g"], lp["wdown"] = pack_groups(l["wo"], fold), None, None
                 lp["wo"] = pack(l["wo"])
                 layers.append(lp)
@@ -627,28 +387,14 @@ class LlamaRunner:
             for k in ("wqkv", "wqkv64", "wo", "wo_g", "wgu", "wdown", "wdown_g"):
                 rep["packed_" + k] = sum(nbytes(l.get(k)) for l in self.wp["layers"])
             rep["packed_lm_head"] = nbytes(self.wp["lm_head"])
-            if self.weight_format == "fp8":
-                for k in F8.PROJECTIONS:
-                    rep["packed_" + k + "_f8"] = sum(nbytes(l[k + "_f8"][0]) for l in self.wp["layers"])
-                rep["fp8_scales"] = sum(nbytes(l[k + "_f8"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
-            if self.weight_format == "fp8b128":                  # the packed codes and, beside them, the checkpoint's own block-scale tables
-                for k in F8.PROJECTIONS:
-                    rep["packed_" + k + "_f8b"] = sum(nbytes(l[k + "_f8b"][0]) for l in self.wp["layers"])
-                rep["fp8_block_scales"] = sum(nbytes(l[k + "_f8b"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
-            if self.weight_format == "mxfp4":                    # one buffer per projection: 16 KiB of elements, then their 1 KiB of scales
-                for k in MX.PROJECTIONS:
-                    rep["packed_" + k + "_f4"] = sum(nbytes(l[k + "_f4"]) * 16 // 17 for l in self.wp["layers"])
-                rep["mxfp4_scales"] = sum(nbytes(l[k + "_f4"]) // 17 for l in self.wp["layers"] for k in MX.PROJECTIONS)
-            if self.weight_format == "int4g128":                     # one buffer per projection: 16 KiB of codes, then their 1 KiB of group data
-                for k in I4.PROJECTIONS:
-                    rep["packed_" + k + "_i4"] = sum(nbytes(l[k + "_i4"]) * 16 // 17 for l in self.wp["layers"])
-                rep["int4_group_data"] = sum(nbytes(l[k + "_i4"]) // 17 for l in self.wp["layers"] for k in I4.PROJECTIONS)
-            if self.weight_format == "int8g128":                     # one buffer per projection: 32 KiB of codes, then their 1 KiB of group data
-                for k in I8.PROJECTIONS:
-                    rep["packed_" + k + "_i8"] = sum(nbytes(l[k + "_i8"]) * 32 // 33 for l in self.wp["layers"])
-                rep["int8_group_data"] = sum(nbytes(l[k + "_i8"]) // 33 for l in self.wp["layers"] for k in I8.PROJECTIONS)
+            fmt = self._fmt
+            if fmt is not None:                                  # per projection the codes, then the format's scales / group data
+                split = {k: [fmt.report_bytes(l[k + fmt.suffix]) for l in self.wp["layers"]] for k in PROJECTIONS}
+                for k in PROJECTIONS:
+                    rep["packed_" + k + fmt.suffix] = sum(c for c, _ in split[k])
+                rep[fmt.scales_key] = sum(sc for k in PROJECTIONS for _, sc in split[k])
         rep["total"] = sum(rep.values())
-        if self.weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128", "int8g128"):
+        if self._fmt is not None:
             rep["weight_format"] = self.weight_format
         if getattr(self, "_qpf_scratch", None) is not None:      # one unpacked projection of the one-pass prefill: no weights of its own, so
             rep["quant_prefill_scratch"] = nbytes(self._qpf_scratch)          # outside "total"; there from the first such prefill on
@@ -745,59 +491,24 @@ class LlamaRunner:
         SAMD_SHARE_HF_WEIGHTS, off): re-point the HF module's q/k/v and gate/up weights at row slices of the runner's concatenated
         matrices -- saves one row-major copy of the model, but the caller's parameters become views of storage the runner owns
         (matters for save_pretrained / in-place edits), so it is opt-in and logged once.
-        weight_format (default: env SAMD_WEIGHT_FORMAT, unset = the model dtype): "fp8" quantises the projections on load.
-        "fp8b128" quantises them per 128 x 128 block (no calibration: for benches and tests); a module without sparse layers whose seven
-        projections per layer are all block-scaled FP8 (`weight` float8_e4m3fn + `weight_scale_inv` fp32, weight_block_size [128, 128]: the
-        dense Qwen3-*-FP8 checkpoints) is imported as it is through fp8.linear_fp8_block and makes the runner "fp8b128" by itself.  A module whose
-        projections already hold float8_e4m3fn weights with a `weight_scale` (per tensor, [N] or [N, 1]) is imported as it is (samd_hip/fp8.py).
-        "mxfp4" quantises them per block of 32 (no calibration: for benches and tests); a module whose projections hold float4_e2m1fn_x2 or uint8
-        weights [N, K/2] with an e8m0 `weight_scale` [N, K/32] is imported as it is (samd_hip/mxfp4.py).
-        "int4g128" quantises them per group of 128 with a zero point (no calibration: for benches and tests); a module whose projections are AWQ
-        ("GEMM") or GPTQ modules -- int32 `qweight` / `qzeros` and a floating `scales` -- is imported as it is, by the layout its
-        config.quantization_config names, and makes the runner "int4g128" by itself (samd_hip/int4.py: group sizes, zero-point conventions and what
-        raises).  A bf16 runner rounds the checkpoint's fp16 scales once to bf16.
-        "int8g128" quantises them per group of 128 with an 8-bit zero point (no calibration: for benches and tests); a module whose seven
-        projections per layer are all 8-bit GPTQ modules (the `...-GPTQ-Int8` releases: bits 8 by config.quantization_config, by the module's
-        own `bits`, or by qweight's shape [K/4, N]) is imported as it is through int8.linear_int8 and makes the runner "int8g128" by itself
-        (samd_hip/int8.py: group sizes, zero-point conventions and what raises); a mix of 8-bit and 4-bit or plain projections raises, and so
-        does a module with sparse layers that carries 8-bit modules anywhere but as described under expert_format "int8g128" below (nothing
-        is dequantised silently).
-        expert_format (default: env SAMD_EXPERT_FORMAT, unset = the model dtype; models with sparse layers only): "mxfp4" quantises the EXPERTS
-        of every sparse layer on load (uncalibrated: for benches and tests); router, attention, dense MLP layers, embedding and lm_head stay in
-        the model dtype.  A module whose sparse layers carry 4-bit expert tensors with their block scales (samd_hip/moe.py has the convention)
-        is imported as it is and makes the runner "mxfp4" by itself; an explicit expert_format=None against such a module raises.
-        "int4g128" quantises the experts per group of 128 with a zero point on load (uncalibrated, as weight_format "int4g128" does).  A 4-bit
-        Qwen3-MoE checkpoint (AWQ / GPTQ) holds, in every sparse layer, an indexable `mlp.experts` of E modules whose gate_proj / up_proj /
-        down_proj are AWQ / GPTQ modules (`mlp.experts.{e}.gate_proj.qweight` ...): each is imported through int4.linear_int4 with the
-        config's quantization_config (so act-order, group sizes 32 / 64, GEMV or a v1 zero point of 15 raise by module name), gate|up are
-        fused per expert, the experts stacked, the scales rounded once for a bf16 runner, and the runner is "int4g128" by itself; an explicit
-        None or "mxfp4" against such a module raises.  The router must be a plain `weight` (an INT4 router raises).  The INT4 attention and
-        dense-MLP projections of a module with sparse layers are NOT streamed as INT4 (weight_format stays rejected for mixture-of-experts
-        models): they are dequantised ONCE at import by int4.dequantize_groups to the model dtype -- exactly the weights an INT4 launch would
-        multiply by, one rounding -- and run on the model-dtype kernels, at 16 bits instead of 4.25 per weight of those projections
-        (Qwen3-30B-A3B: 48 layers x 37.7 M attention weights = 3.6 GB instead of 0.96 GB; the experts, 97 % of the model, stay 4-bit).
-        Streaming them through samd_gemm_skinny_i4 inside a mixture-of-experts stack is the follow-up.
-        "fp8b128" quantises the experts per 128 x 128 block on load (uncalibrated, for benches and tests).  A block-scaled FP8 Qwen3-MoE
-        checkpoint (Qwen3-30B-A3B-FP8: float8_e4m3fn `weight` + fp32 `weight_scale_inv`, weight_block_size [128, 128]) holds, in every sparse
-        layer, transformers' fused FP8Experts (`mlp.experts.gate_up_proj` + `gate_up_proj_scale_inv`, `down_proj` + `down_proj_scale_inv`)
-        or per-expert modules (`mlp.experts.{e}.gate_proj.weight` + `weight_scale_inv`): the codes and scales are imported as they are
-        (samd_hip/fp8.py has the contract and the rejections, by tensor name) and the runner is "fp8b128" by itself, weight_format None.
-        The module's FP8 attention and dense-MLP projections (block-scaled, or per row / per tensor `weight_scale`) are dequantised ONCE at
-        import to rne_dtype(fl32(float(q) * s)) and run on the model-dtype kernels; the router must be a plain `weight`.  Weight-only: the
-        checkpoint's dynamic activation quantisation is not reproduced.  FP8 projections beside non-FP8 experts stay rejected.
-        "int8g128" quantises the experts per group of 128 with an 8-bit zero point on load (uncalibrated, for benches and tests).  An 8-bit
-        GPTQ Qwen3-MoE checkpoint (the `Qwen3-30B-A3B-GPTQ-Int8` kind) holds, in every sparse layer, an indexable `mlp.experts` of E modules
-        whose gate_proj / up_proj / down_proj are 8-bit GPTQ modules (qweight / qzeros / scales): each is imported through int8.linear_int8
-        with the config's quantization_config (so act-order, group sizes 32 / 64, AWQ or a stored 255 under "gptq" raise by module name),
-        gate|up are fused per expert, the experts stacked, the scales rounded once for a bf16 runner, and the runner is "int8g128" by itself;
-        any other explicit expert_format against such a module raises.  A sparse layer of which only some experts or projections are 8-bit
-        raises by module name, and so does an 8-bit router.  The checkpoint's 8-bit attention projections and dense-layer MLP projections
-        are NOT streamed as INT8 (weight_format stays rejected for mixture-of-experts models): they are dequantised ONCE at import by
-        int8.dequantize_groups to the model dtype -- one rounding, the weights an INT8 launch would multiply by -- and run on the
-        model-dtype kernels, at 16 bits instead of 8.25 per weight of those projections (Qwen3-30B-A3B: 48 layers x 37.7 M attention
-        weights = 3.6 GB instead of 1.9 GB; the experts, 97 % of the model, stay 8-bit).
-        share_weights does not apply to
-        dequantised projections (there is no HF `weight` to re-point); INT4 attention beside model-dtype or MXFP4 experts stays rejected."""
+        weight_format (default: env SAMD_WEIGHT_FORMAT, unset = the model dtype): a name of formats.DENSE_FORMATS quantises the four
+        projections of every layer on load (no calibration: for benches and tests).  A module whose projections already hold one of these
+        formats is imported as it is, codes and side data untouched, and makes the runner that format by itself; each record's doc says
+        which modules count as its format and where the rejections live.  A mix of formats raises: nothing is dequantised silently.
+        expert_format (default: env SAMD_EXPERT_FORMAT, unset = the model dtype; models with sparse layers only): a name of moe.EXPERT
+        quantises the EXPERTS of every sparse layer on load (uncalibrated: for benches and tests); router, attention, dense MLP layers,
+        embedding and lm_head stay in the model dtype.  A module whose sparse layers carry quantised experts (each record's doc: in which
+        module forms) is imported as it is and makes the runner that format by itself; any other explicit expert_format against it raises,
+        and so do a quantised router and a sparse layer of which only some experts or projections are quantised, by module name.
+        Beside INT4, INT8 or block-scaled FP8 experts, the module's attention and dense-MLP projections may be quantised likewise (an AWQ /
+        GPTQ or FP8 mixture-of-experts checkpoint).  They are NOT streamed quantised (weight_format stays rejected for mixture-of-experts
+        models): they are dequantised ONCE at import by the format's dequantize_groups / linear_fp8_dequantized to the model dtype --
+        exactly the weights a quantised launch would multiply by, one rounding -- and run on the model-dtype kernels, at 16 bits per
+        weight of those projections (Qwen3-30B-A3B: 48 layers x 37.7 M attention weights = 3.6 GB instead of 0.96 GB at 4.25 bits or
+        1.9 GB at 8.25; the experts, 97 % of the model, stay quantised).  Streaming them inside a mixture-of-experts stack is the
+        follow-up.  Weight-only: an FP8 checkpoint's dynamic activation quantisation is not reproduced.  Quantised projections beside
+        experts of another format stay rejected.  share_weights does not apply to dequantised projections (there is no HF `weight` to
+        re-point)."""
         weight_format = _env_weight_format(weight_format)
         m = lm.model
         parts = (("self_attn", "q_proj"), ("self_attn", "k_proj"), ("self_attn", "v_proj"), ("self_attn", "o_proj"), ("mlp", "gate_proj"),
@@ -867,12 +578,13 @@ class LlamaRunner:
         moe_i8_dense = ckpt_i8 and moe_i8
         if moe_i8_dense:
             ckpt_i8 = False
+        # the one dense format the module's projections are imported in, as they are (at most one detector holds); None: plain weights
+        ckpt = DENSE.get("int4g128" if ckpt_i4 else "int8g128" if ckpt_i8 else "mxfp4" if ckpt_f4 else "fp8b128" if ckpt_f8b else "fp8" if ckpt_f8 else None)
         if any(sparse) or shape.moe:
             if sparse != list(shape.sparse):
                 raise SamdError(f"the module's sparse MLP layers {[i for i, x in enumerate(sparse) if x]} are not the ones its config implies "
                                 f"{[i for i, x in enumerate(shape.sparse) if x]} (model_type '{shape.model_type}')")
-            MOE.reject_unsupported("int8g128" if ckpt_i8 else "int4g128" if ckpt_i4 else "fp8" if ckpt_f8 else "fp8b128" if ckpt_f8b else ("mxfp4" if ckpt_f4 else weight_format), kw.get("native_gemm", True),
-                                   kw.get("draft_head", False))
+            MOE.reject_unsupported(ckpt.name if ckpt is not None else weight_format, kw.get("native_gemm", True), kw.get("draft_head", False))
         # 4-bit experts: decided and checked on the module's own tensors, before anything moves to the device (the runner resolves the
         # format again from the weights it is given)
         experts4 = [not i4e and not moe_i8 and not layer_f8[i] and cls._hf_experts_are_4bit(lyr, i)
@@ -880,6 +592,8 @@ class LlamaRunner:
         experts_f8 = [layer_f8[i] for i in range(len(m.layers)) if sparse[i]]
         MOE.resolve_expert_format(expert_format, any(experts4), any(sparse) or shape.moe, carries_int4=any(experts_i4), carries_fp8=any(experts_f8),
                                   carries_int8=moe_i8)
+        # the expert format the module's sparse layers are imported in, as they are; None: HF's fused model-dtype tensors
+        ckpt_experts = MOE.EXPERT["fp8b128" if any(experts_f8) else "int4g128" if any(experts_i4) else "int8g128" if moe_i8 else "mxfp4" if any(experts4) else None]
         if any(experts_f8):
             if not all(experts_f8):
                 plain = [i for i, sp in enumerate(sparse) if sp and not layer_f8[i]][:3]
@@ -959,74 +673,20 @@ class LlamaRunner:
                 extra["bqkv"] = get(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias]))
             if qk_norm:
                 extra["q_norm"], extra["k_norm"] = get(a.q_norm.weight), get(a.k_norm.weight)
-            if ckpt_i4:                                          # canonical (q, z, s) of the AWQ / GPTQ modules; the runner checks and packs them
-                lw = {}
-                for k, names in (("wqkv", ("q_proj", "k_proj", "v_proj")), ("wo", ("o_proj",)), ("wgu", ("gate_proj", "up_proj")), ("wdown", ("down_proj",))):
-                    own = a if k in ("wqkv", "wo") else f
-                    lw[k], lw[k + "_z"], lw[k + "_s"] = I4.fuse_int4(
-                        [I4.linear_int4(getattr(own, x), f"layers.{len(layers)}.{x}", config=qcfg) for x in names], dev, dtype)
-                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
-            if ckpt_i8:                                          # canonical (q, z, s) of the 8-bit GPTQ modules; the runner checks and packs them
-                lw = {}
-                for k, names in (("wqkv", ("q_proj", "k_proj", "v_proj")), ("wo", ("o_proj",)), ("wgu", ("gate_proj", "up_proj")), ("wdown", ("down_proj",))):
-                    own = a if k in ("wqkv", "wo") else f
-                    lw[k], lw[k + "_z8"], lw[k + "_s8"] = I8.fuse_int8(
-                        [I8.linear_int8(getattr(own, x), f"layers.{len(layers)}.{x}", config=qcfg) for x in names], dev, dtype)
-                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
-            if ckpt_f4:                                          # (q, e8) as the checkpoint has them; the runner checks and packs them
-                lw = {}
-                for k, lins in (("wqkv", (a.q_proj, a.k_proj, a.v_proj)), ("wo", (a.o_proj,)), ("wgu", (f.gate_proj, f.up_proj)), ("wdown", (f.down_proj,))):
-                    lw[k], lw[k + "_e8"] = MX.fuse_mxfp4([MX.linear_mxfp4(x) for x in lins], dev)
-                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
-            if ckpt_f8b:                                         # (q, block scales) as the checkpoint has them; the runner packs the codes
-                lw, li = {}, len(layers)
-                for k, own, names in (("wqkv", a, ("q_proj", "k_proj", "v_proj")), ("wo", a, ("o_proj",)), ("wgu", f, ("gate_proj", "up_proj")),
-                                      ("wdown", f, ("down_proj",))):
-                    full = [f"layers.{li}.{'self_attn' if own is a else 'mlp'}.{x}" for x in names]
-                    lw[k], lw[k + "_sinv"] = F8.fuse_fp8_blocks([F8.linear_fp8_block(getattr(own, x), n, qcfg8) for x, n in zip(names, full)], dev, full)
-                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
-            if ckpt_f8:                                          # (q, scale) as the checkpoint has them; the runner packs them
-                lw = {}
-                for k, lins in (("wqkv", (a.q_proj, a.k_proj, a.v_proj)), ("wo", (a.o_proj,)), ("wgu", (f.gate_proj, f.up_proj)), ("wdown", (f.down_proj,))):
-                    lw[k], lw[k + "_scale"] = F8.fuse_fp8([F8.linear_fp8(x) for x in lins], dev)
-                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
             li = len(layers)
+            if ckpt is not None:                                 # the checkpoint's own codes and side data; the runner checks and packs them
+                lw = {}
+                for k, own, part, names in (("wqkv", a, "self_attn", ("q_proj", "k_proj", "v_proj")), ("wo", a, "self_attn", ("o_proj",)),
+                                            ("wgu", f, "mlp", ("gate_proj", "up_proj")), ("wdown", f, "mlp", ("down_proj",))):
+                    got = ckpt.import_hf([getattr(own, x) for x in names], names, li, part, dev, dtype, qcfg, qcfg8)
+                    lw.update({k + sfx: t for sfx, t in zip(ckpt.raw_keys, got)})
+                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
+                continue
             qkv_names, o_name = [f"layers.{li}.self_attn.{x}" for x in ("q_proj", "k_proj", "v_proj")], f"layers.{li}.self_attn.o_proj"
-            if sparse[li] and any(experts_f8):                   # router + the experts' e4m3fn codes and block scales, as they are
+            if sparse[li]:                                       # router + the experts as the module holds them (moe.EXPERT: import_hf)
                 layers.append(dict(
                     wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
-                    **MOE.import_experts_fp8(f.experts, f"layers.{li}.mlp.experts", dev, qcfg8),
-                    ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
-            if sparse[li] and any(experts_i4):                   # router + the experts' canonical (q, z, s), fused and stacked
-                layers.append(dict(
-                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
-                    **MOE.import_experts_int4(f.experts, f"layers.{li}.mlp.experts", dtype, dev, qcfg),
-                    ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
-            if sparse[li] and moe_i8:                            # router + the experts' canonical 8-bit (q, z, s), fused and stacked
-                layers.append(dict(
-                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
-                    **MOE.import_experts_int8(f.experts, f"layers.{li}.mlp.experts", dtype, dev, qcfg),
-                    ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
-            if sparse[len(layers)] and any(experts4):            # router + the 4-bit expert tensors and their block scales, as they are
-                ex, raw = f.experts, lambda t: MX._bytes(t.detach()).to(dev).contiguous()
-                layers.append(dict(
-                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
-                    experts_gu=raw(ex.gate_up_proj), experts_gu_scale=raw(ex.gate_up_proj_scale),
-                    experts_down=raw(ex.down_proj), experts_down_scale=raw(ex.down_proj_scale),
-                    ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
-            if sparse[len(layers)]:                              # router + HF's fused expert tensors [E, 2 I, H] / [E, H, I]
-                layers.append(dict(
-                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
-                    experts_gu=get(f.experts.gate_up_proj), experts_down=get(f.experts.down_proj),
+                    **ckpt_experts.import_hf(f.experts, f"layers.{li}.mlp.experts", dtype, dev, qcfg, qcfg8),
                     ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
                 continue
             layers.append(dict(
@@ -1237,19 +897,14 @@ class LlamaRunner:
         n_act = self.shape.top_k if experts is None else int(experts)
         nb = lambda t: t.numel() * t.element_size() if t.dim() != 3 else t[0].numel() * t.element_size() * min(n_act, t.shape[0])
         n = nb(self.w["lm_head"]) + nb(self.w["norm"])
-        if self.weight_format in ("mxfp4", "int4g128", "int8g128"):
-            sfx = {"mxfp4": "_f4", "int4g128": "_i4", "int8g128": "_i8"}[self.weight_format]
-            for l, lp in zip(self.w["layers"], self.wp["layers"]):
-                n += sum(nb(t) for k, t in l.items() if k not in MX.PROJECTIONS) + sum(nb(lp[k + sfx]) for k in MX.PROJECTIONS)
-            return n
-        for l in self.w["layers"]:
-            n += sum(nb(t) for t in l.values())
-        if self.expert_format == "int8g128":                     # the packed bytes, N K 33 / 32: a zero point is a 16-bit word there
-            n += sum(nb(l[k]) for l in self.w["layers"] for k in ("experts_gu_z8", "experts_down_z8") if k in l)
-        if self.weight_format == "fp8":
-            n += sum(nb(l[k + "_f8"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
-        if self.weight_format == "fp8b128":                      # one byte per weight (counted above) + 4 bytes per 128 x 128 block
-            n += sum(nb(l[k + "_f8b"][1]) for l in self.wp["layers"] for k in F8.PROJECTIONS)
+        fmt = self._fmt
+        packed = self.wp["layers"] if self.wp else [{}] * len(self.w["layers"])
+        for l, lp in zip(self.w["layers"], packed):
+            if fmt is None:
+                n += sum(nb(t) for t in l.values())
+            else:                                                # a quantised projection: what its packed operand holds
+                n += sum(nb(t) for k, t in l.items() if k not in PROJECTIONS) + sum(fmt.streamed_bytes(lp[k + fmt.suffix]) for k in PROJECTIONS)
+        n += sum(nb(l[k]) for l in self.w["layers"] for k in MOE.EXPERT[self.expert_format].recount_keys if k in l)
         return n
 
     # ------------------------------------------------------------------------------------------------
@@ -1325,30 +980,17 @@ class LlamaRunner:
             sp = 1 if (fused or is_head) else L.samd_gemm_splits(n, k, RP)
             return C.byref(Warm(wp.data_ptr(), n, k, sp, self.warm_kb, self.warm_delay, self.warm_where))
 
-        def gemm(a, w, wp, out, wg=None, f8=None, f4=None, i4=None, f8b=None, i8=None):
-            """out = a @ w.T (wp = w in the packed 128-column-tile layout, wg = w group-major: whichever exists; f8 = (packed e4m3fn, column
-            scales) of an FP8 runner; f8b = (packed e4m3fn, fp32 block-scale table) of a block-scaled FP8 runner; f4 = the packed elements + block scales of an MXFP4 runner; i4 / i8 = the packed codes + group data of an INT4 / INT8 runner); returns (operand for the consumer,
-            n_partials, partial_stride)."""
+        fmt = self._fmt
+        quantised = (lambda wp, k: wp.get(k + fmt.suffix)) if fmt is not None else (lambda wp, k: None)
+
+        def gemm(a, w, wp, out, wg=None, q=None):
+            """out = a @ w.T (wp = w in the packed 128-column-tile layout, wg = w group-major: whichever exists; q = the packed operand of a
+            quantised runner in its format's own form: a tensor, or a (codes, scales) pair); returns (operand for the consumer, n_partials,
+            partial_stride)."""
             n, k = w.shape
-            if i8 is not None:                                    # (RP <= 64 here, as for FP8; the INT8 runner's own packed buffer)
+            if q is not None:                                     # (RP <= 64 here: a quantised runner has no library-GEMM path, see the check above)
                 sp = L.samd_gemm_splits(n, k, RP)
-                check(L.samd_gemm_skinny_i8(_ptr(a), _ptr(i8), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
-                return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
-            if i4 is not None:                                    # (RP <= 64 here, as for FP8; the INT4 runner's own packed buffer)
-                sp = L.samd_gemm_splits(n, k, RP)
-                check(L.samd_gemm_skinny_i4(_ptr(a), _ptr(i4), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
-                return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
-            if f4 is not None:                                    # (RP <= 64 here, as for FP8)
-                sp = L.samd_gemm_splits(n, k, RP)
-                check(L.samd_gemm_skinny_f4(_ptr(a), _ptr(f4), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
-                return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
-            if f8b is not None:                                   # (RP <= 64 here, as for FP8)
-                sp = L.samd_gemm_splits(n, k, RP)
-                check(L.samd_gemm_skinny_f8b(_ptr(a), _ptr(f8b[0]), _ptr(f8b[1]), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
-                return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
-            if f8 is not None:                                    # (RP <= 64 here: an FP8 runner has no library-GEMM path, see the check above)
-                sp = L.samd_gemm_splits(n, k, RP)
-                check(L.samd_gemm_skinny_f8(_ptr(a), _ptr(f8[0]), _ptr(f8[1]), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
+                check(getattr(L, fmt.gemm)(_ptr(a), *fmt.pointers(q), RP, n, k, sp, _ptr(part), _ptr(out), dt, st))
                 return (out, 0, 0) if sp == 1 else (part, sp, RP * n)
             # measured on MI355X (scripts/forward_ablation.py, whole forward incl. the consumers' partial-sum reads), ours vs
             # the library GEMM: 3.46 vs 4.75 ms at <= 16 rows, 3.74 vs 4.62 at 32, 4.72 vs 5.15 at 64
@@ -1403,7 +1045,7 @@ class LlamaRunner:
                     _ptr(b["x"] if raw_in else b["h"]), _ptr(wp["wqkv64"]), RP, s.hidden, _ptr(b["cs"]), _ptr(d_L), _ptr(d_n),
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), s.heads, s.kv_heads, s.head_dim, self.max_len, dt, st))
             else:
-                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], f8=wp.get("wqkv_f8"), f8b=wp.get("wqkv_f8b"), f4=wp.get("wqkv_f4"), i4=wp.get("wqkv_i4"), i8=wp.get("wqkv_i8"))
+                src, n_p, stride = gemm(b["x"] if raw_in else b["h"], w["wqkv"], wp.get("wqkv"), b["qkv"], q=quantised(wp, "wqkv"))
             if block:
                 # RoPE + K row / V^T column write + tree attention + merge of the tile partials: one launch (csrc/attn_kernels.hip)
                 check(L.samd_attention_block(_ptr(src), n_p, stride, _ptr(b["cs"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R,
@@ -1435,7 +1077,7 @@ class LlamaRunner:
                     _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R, s.heads,
                     s.kv_heads, s.head_dim, self.max_len, _ptr(d_mask), _ptr(d_L), _ptr(d_n), self.scale,
                     _ptr(b["ws"]), b["ws_bytes"], hint(w["wo"], wp.get("wo")), st))
-            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), f8=wp.get("wo_f8"), f8b=wp.get("wo_f8b"), f4=wp.get("wo_f4"), i4=wp.get("wo_i4"), i8=wp.get("wo_i8"))
+            src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), q=quantised(wp, "wo"))
             check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(src), _ptr(w["ln2"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, n_p, stride,
                                       None, st))           # (no warm-up hint: gate|up is packed group-major, the hint describes 128-column tiles)
             if "moe_gu" in wp:
@@ -1452,9 +1094,9 @@ class LlamaRunner:
             if wp.get("wgu") is not None and RP <= self.native_gemm_max_rows:
                 check(L.samd_gemm_pairs_silu(_ptr(b["h"]), _ptr(wp["wgu"]), RP, s.inter, s.hidden, _ptr(b["act"]), dt, st))
             else:
-                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], f8=wp.get("wgu_f8"), f8b=wp.get("wgu_f8b"), f4=wp.get("wgu_f4"), i4=wp.get("wgu_i4"), i8=wp.get("wgu_i8"))     # wgu is only ever packed for the fused form (or FP8)
+                src, n_p, stride = gemm(b["h"], w["wgu"], None, b["gu"], q=quantised(wp, "wgu"))     # wgu is only ever packed for the fused form (or FP8)
                 check(L.samd_silu_mul(_ptr(src), _ptr(b["act"]), R, s.inter, dt, n_p, stride, st))
-            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), f8=wp.get("wdown_f8"), f8b=wp.get("wdown_f8b"), f4=wp.get("wdown_f4"), i4=wp.get("wdown_i4"), i8=wp.get("wdown_i8"))
+            delta, dn, dstride = gemm(b["act"], w["wdown"], wp.get("wdown"), b["d"], wg=wp.get("wdown_g"), q=quantised(wp, "wdown"))
         if _span is not None and not _span.head:
             return b, len(self.w["layers"])
         check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(delta), _ptr(self.w["norm"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, dn, dstride,
@@ -1525,7 +1167,7 @@ class LlamaRunner:
             return self._prefill_wide(session, ids, on_chunk)
         if N >= self.MOE_PF_MIN_ROWS and os.environ.get("SAMD_PREFILL", "wide") != "chunked" and self.shape.moe:
             return self._prefill_moe(session, ids, on_chunk)
-        if (self.weight_format in QUANT_FORMATS and not self.shape.moe and os.environ.get("SAMD_PREFILL", "wide") != "chunked"
+        if (self._fmt is not None and not self.shape.moe and os.environ.get("SAMD_PREFILL", "wide") != "chunked"
                 and N >= quant_prefill_min_rows(self.QUANT_PF_MIN_ROWS)):
             return self._prefill_wide(session, ids, on_chunk)        # (each projection unpacked into a scratch matrix: _pf_weight)
         v = session.device_views()
@@ -1698,27 +1340,18 @@ class LlamaRunner:
         none -- its packed buffer unpacked (samd_gemm_unpack_*: the weights the streaming launch multiplies by) into the scratch matrix,
         which the next projection overwrites.  The scratch ([max N x K over the four projections], model dtype) is allocated at the first
         one-pass prefill and kept; memory_report() shows it, weight_bytes() does not count it."""
-        w = self.w["layers"][li][key]
-        if self.weight_format not in QUANT_FORMATS:
+        w, fmt = self.w["layers"][li][key], self._fmt
+        if fmt is None:
             return w
         N, K = w.shape
         if getattr(self, "_qpf_scratch", None) is None:
-            elems = max(self.w["layers"][0][k].shape[0] * self.w["layers"][0][k].shape[1] for k in F8.PROJECTIONS)
+            elems = max(self.w["layers"][0][k].shape[0] * self.w["layers"][0][k].shape[1] for k in PROJECTIONS)
             self._qpf_scratch = torch.empty(elems, dtype=self.dtype, device=self.device)
         if N * K > self._qpf_scratch.numel():
             raise SamdError(f"projection {key} of layer {li}, shape ({N}, {K}), exceeds the prefill scratch of {self._qpf_scratch.numel()} elements")
         out = self._qpf_scratch[:N * K].view(N, K)
         L, lp, st = lib(), self.wp["layers"][li], current_stream()
-        if self.weight_format == "fp8":
-            check(L.samd_gemm_unpack_f8(_ptr(lp[key + "_f8"][0]), _ptr(lp[key + "_f8"][1]), N, K, _ptr(out), self.dt, st))
-        elif self.weight_format == "fp8b128":
-            check(L.samd_gemm_unpack_f8b(_ptr(lp[key + "_f8b"][0]), _ptr(lp[key + "_f8b"][1]), N, K, _ptr(out), self.dt, st))
-        elif self.weight_format == "mxfp4":
-            check(L.samd_gemm_unpack_f4(_ptr(lp[key + "_f4"]), N, K, _ptr(out), self.dt, st))
-        elif self.weight_format == "int4g128":
-            check(L.samd_gemm_unpack_i4(_ptr(lp[key + "_i4"]), N, K, _ptr(out), self.dt, st))
-        else:
-            check(L.samd_gemm_unpack_i8(_ptr(lp[key + "_i8"]), N, K, _ptr(out), self.dt, st))
+        check(getattr(L, fmt.unpack)(*fmt.pointers(lp[key + fmt.suffix]), N, K, _ptr(out), self.dt, st))
         return out
 
     def _pf_mm(self, x, w, out, key, bias=None):

@@ -51,11 +51,14 @@ import os
 
 import torch
 
+from typing import Callable, NamedTuple, Optional
+
 from . import SamdError, _ptr, check, current_stream, lib, torch_dtype_code
 from . import fp8 as F8
 from . import int4 as I4
 from . import int8 as I8
 from . import mxfp4 as MX
+from .formats import QUANT_FORMATS
 
 MAX_EXPERTS = 256
 MAX_TOPK = 8
@@ -106,7 +109,7 @@ def check_shape(hidden, moe_inter, n_experts, top_k):
 
 def reject_unsupported(weight_format=None, native_gemm=True, draft_head=False):
     """what a runner with sparse layers does not offer; raises before any device work"""
-    if weight_format in ("fp8", "fp8b128", "mxfp4", "int4g128", "int8g128"):
+    if weight_format in QUANT_FORMATS:
         raise SamdError(f"mixture-of-experts models are not available with weight_format '{weight_format}': quantised experts are not supported")
     if not native_gemm:
         raise SamdError("mixture-of-experts layers exist only in the streaming kernels' packed form: native_gemm=False is not available")
@@ -599,62 +602,17 @@ class MoeBuffers:
         check(lib().samd_moe_lists(_ptr(self.topk_idx), _ptr(d_n), self.rows_pad, self.n_experts, self.top_k, _ptr(self.ws), current_stream()))
 
     def experts(self, h, wgu_packed, wdown_packed, d_n, expert_format=None):
-        """the two expert launches over buffers of pack_experts (expert_format None), pack_experts_mxfp4 ("mxfp4"), pack_experts_int4
-        ("int4g128"; packed for this runner's dtype), pack_experts_fp8 ("fp8b128") or pack_experts_int8 ("int8g128"; packed for this
-        runner's dtype)"""
+        """the two expert launches over the buffers that expert_format's packer returned (EXPERT: pack; the INT4 and INT8 ones are packed
+        for this runner's dtype)"""
         if expert_format not in EXPERT_FORMATS_SERVED:
             raise _format_error(expert_format)
-        if expert_format != "int8g128" and "int8g128" in (getattr(wgu_packed, "expert_format", None), getattr(wdown_packed, "expert_format", None)):
-            raise SamdError(f"an INT8 expert buffer (pack_experts_int8) under expert_format {expert_format!r}: pass expert_format='int8g128'")
-        if expert_format == "int8g128":                          # (the guards come before any device work)
-            _check_expert_buffers(self, wgu_packed, wdown_packed, expert_format)
-        L, st = lib(), current_stream()
-        if expert_format == "int8g128":
-            check(L.samd_moe_gate_up_silu_i8(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts,
-                                             self.top_k, _ptr(self.act), self.dt, st))
-            check(L.samd_moe_down_combine_i8(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws),
-                                             self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k, _ptr(self.out), self.dt, st))
-            return self.out
-        if expert_format == "fp8b128":
-            # the byte count tells this buffer from every other one of the shape (gate|up and down differ too: swapped buffers raise)
-            for what, t, want in (("gate|up", wgu_packed, self.n_experts * F8.packed_block_bytes(2 * self.moe_inter, self.hidden)),
-                                  ("down", wdown_packed, self.n_experts * F8.packed_block_bytes(self.hidden, self.moe_inter))):
-                if t.dtype != torch.uint8 or t.numel() != want:
-                    raise SamdError(f"FP8 {what} expert buffer of {t.numel()} {t.dtype} elements; pack_experts_fp8 gives {want} bytes for this shape")
-            check(L.samd_moe_gate_up_silu_f8(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts,
-                                             self.top_k, _ptr(self.act), self.dt, st))
-            check(L.samd_moe_down_combine_f8(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws),
-                                             self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k, _ptr(self.out), self.dt, st))
-            return self.out
-        if expert_format == "int4g128":
-            for t, want in ((wgu_packed, self.n_experts * I4.packed_bytes(2 * self.moe_inter, self.hidden)),
-                            (wdown_packed, self.n_experts * I4.packed_bytes(self.hidden, self.moe_inter))):
-                if t.dtype != torch.uint8 or t.numel() != want:
-                    raise SamdError(f"INT4 expert buffer of {t.numel()} {t.dtype} elements; pack_experts_int4 gives {want} bytes for this shape")
-                if getattr(t, "expert_format", None) != "int4g128":
-                    raise SamdError("expert_format 'int4g128' over a buffer that pack_experts_int4 did not return (an MXFP4 buffer of this shape "
-                                    "has the same byte count and other contents; a copy or a view of an INT4 buffer loses the packer's mark)")
-            check(L.samd_moe_gate_up_silu_i4(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts,
-                                             self.top_k, _ptr(self.act), self.dt, st))
-            check(L.samd_moe_down_combine_i4(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws),
-                                             self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k, _ptr(self.out), self.dt, st))
-            return self.out
-        if expert_format == "mxfp4":
-            for t, want in ((wgu_packed, self.n_experts * MX.packed_bytes(2 * self.moe_inter, self.hidden)),
-                            (wdown_packed, self.n_experts * MX.packed_bytes(self.hidden, self.moe_inter))):
-                if t.dtype != torch.uint8 or t.numel() != want:
-                    raise SamdError(f"MXFP4 expert buffer of {t.numel()} {t.dtype} elements; pack_experts_mxfp4 gives {want} bytes for this shape")
-            check(L.samd_moe_gate_up_silu_f4(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts,
-                                             self.top_k, _ptr(self.act), self.dt, st))
-            check(L.samd_moe_down_combine_f4(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws),
-                                             self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k, _ptr(self.out), self.dt, st))
-            return self.out
-        if wgu_packed.dtype == torch.uint8 or wdown_packed.dtype == torch.uint8:
-            raise SamdError("uint8 expert buffers are MXFP4 ones: pass expert_format='mxfp4'")
-        check(L.samd_moe_gate_up_silu(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k,
-                                      _ptr(self.act), self.dt, st))
-        check(L.samd_moe_down_combine(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws),
-                                      self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k, _ptr(self.out), self.dt, st))
+        _check_expert_buffers(self, wgu_packed, wdown_packed, expert_format)      # (the guards come before any device work)
+        L, st, sfx = lib(), current_stream(), EXPERT[expert_format].launch_suffix
+        check(getattr(L, "samd_moe_gate_up_silu" + sfx)(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter,
+                                                        self.n_experts, self.top_k, _ptr(self.act), self.dt, st))
+        check(getattr(L, "samd_moe_down_combine" + sfx)(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n),
+                                                        _ptr(self.ws), self.rows_pad, self.hidden, self.moe_inter, self.n_experts, self.top_k,
+                                                        _ptr(self.out), self.dt, st))
         return self.out
 
     def routing_state(self):
@@ -762,7 +720,7 @@ class MoeWideBuffers:
         if expert_format not in EXPERT_FORMATS_SERVED:
             raise _format_error(expert_format)
         _check_expert_buffers(self, wgu_packed, wdown_packed, expert_format)
-        L, st, code, rows = lib(), current_stream(), WIDE_FORMAT_CODES_SERVED[expert_format], self._rows(rows)
+        L, st, code, rows = lib(), current_stream(), EXPERT[expert_format].wide_code, self._rows(rows)
         check(L.samd_moe_wide_gate_up_silu(_ptr(h), _ptr(wgu_packed), _ptr(self.ws), rows, self.hidden, self.moe_inter, self.n_experts, self.top_k,
                                            code, _ptr(self.act), self.dt, st))
         check(L.samd_moe_wide_down_combine(_ptr(self.act), _ptr(wdown_packed), _ptr(self.topk_idx), _ptr(self.topk_w), _ptr(d_n), _ptr(self.ws), rows,
@@ -786,20 +744,154 @@ class MoeWideBuffers:
 
 
 def _check_expert_buffers(b, wgu_packed, wdown_packed, expert_format):
-    """the byte counts and marks MoeBuffers.experts asks of packed expert buffers, for the wide calls (and its own INT8 launch)"""
-    if expert_format != "int8g128" and "int8g128" in (getattr(wgu_packed, "expert_format", None), getattr(wdown_packed, "expert_format", None)):
-        raise SamdError(f"an INT8 expert buffer (pack_experts_int8) under expert_format {expert_format!r}: pass expert_format='int8g128'")
-    if expert_format is None:
+    """the byte counts and marks the expert launches (MoeBuffers.experts and the wide calls) ask of packed expert buffers"""
+    fmt = EXPERT[expert_format]
+    for other in EXPERT.values():                                # a buffer whose packer's mark says it may pass as nothing else
+        if other.mark_exclusive and other is not fmt and other.name in (getattr(wgu_packed, "expert_format", None), getattr(wdown_packed, "expert_format", None)):
+            raise SamdError(f"an {other.label} expert buffer ({other.packer}) under expert_format {expert_format!r}: pass expert_format='{other.name}'")
+    if fmt.packed_bytes is None:
         if wgu_packed.dtype == torch.uint8 or wdown_packed.dtype == torch.uint8:
             raise SamdError("uint8 expert buffers are MXFP4 ones: pass expert_format='mxfp4'")
         return
-    nbytes = {"fp8b128": F8.packed_block_bytes, "int4g128": I4.packed_bytes, "mxfp4": MX.packed_bytes, "int8g128": I8.packed_bytes}[expert_format]
-    for what, t, want in (("gate|up", wgu_packed, b.n_experts * nbytes(2 * b.moe_inter, b.hidden)), ("down", wdown_packed, b.n_experts * nbytes(b.hidden, b.moe_inter))):
+    for what, t, want in (("gate|up", wgu_packed, b.n_experts * fmt.packed_bytes(2 * b.moe_inter, b.hidden)),
+                          ("down", wdown_packed, b.n_experts * fmt.packed_bytes(b.hidden, b.moe_inter))):
         if t.dtype != torch.uint8 or t.numel() != want:
-            raise SamdError(f"{expert_format} {what} expert buffer of {t.numel()} {t.dtype} elements; the packer gives {want} bytes for this shape")
-        if expert_format == "int4g128" and getattr(t, "expert_format", None) != "int4g128":
-            raise SamdError("expert_format 'int4g128' over a buffer that pack_experts_int4 did not return (an MXFP4 buffer of this shape "
-                            "has the same byte count and other contents; a copy or a view of an INT4 buffer loses the packer's mark)")
-        if expert_format == "int8g128" and getattr(t, "expert_format", None) != "int8g128":
-            raise SamdError("expert_format 'int8g128' over a buffer that pack_experts_int8 did not return (the byte count alone does not "
-                            "tell a packed INT8 buffer from other bytes; a copy or a view of an INT8 buffer loses the packer's mark)")
+            raise SamdError(f"{fmt.name} {what} expert buffer of {t.numel()} {t.dtype} elements is no {fmt.label} expert buffer of this shape: "
+                            f"{fmt.packer} gives {want} bytes")
+        if fmt.mark_why is not None and getattr(t, "expert_format", None) != fmt.name:
+            raise SamdError(f"expert_format '{fmt.name}' over a buffer that {fmt.packer} did not return ({fmt.mark_why}; a copy or a view of "
+                            f"an {fmt.label} buffer loses the packer's mark)")
+
+
+# ---- the expert formats, one record each: everything LlamaRunner and the launches above need to know about a format.  A new format is one
+# more record (DESIGN.md section 3), beside its check_* / quantize_experts_* / pack_experts_* / import_experts_* functions above.
+class ExpertFormat(NamedTuple):
+    name: Optional[str]      # the expert_format; None: the model dtype
+    doc: str                 # which module forms from_hf takes as this format (the module docstring has the numeric contract)
+    label: str               # "<label> experts", "an <label> expert buffer"
+    mix_label: str           # "a mix of <mix_label> sparse layers"
+    raw_keys: tuple          # the suffixes of the raw weights dict's entries of gate|up ("experts_gu" + ...) and down: codes, then side data
+    carried: Callable        # (sparse layer dict) -> does it carry this format's expert tensors?
+    carries_kw: str          # resolve_expert_format's keyword for "the weights carry this format"
+    check: Callable          # (gu, down, dtype, name): check_*_experts over the two key tuples' tensors
+    quantize: Optional[Callable]    # (gate_up, down, dtype, name) -> (gu, down) tuples: quantize_experts_*; None: nothing to quantise
+    pack: Callable           # (gu, down, dtype) -> (packed gate|up, packed down): pack_experts_*
+    packer: str              # ... its name, for messages
+    import_hf: Callable      # (HF experts module, name, dtype, device, qcfg, qcfg8) -> the raw-dict entries: import_experts_*
+    packed_bytes: Optional[Callable]    # (N, K) -> bytes of one expert's packed matrix; None: the model dtype's N * K elements
+    launch_suffix: str       # samd_moe_gate_up_silu<suffix> / samd_moe_down_combine<suffix>
+    meta_dtype: Callable = lambda t: t.dtype      # (tensor) -> the dtype its released meta shape keeps
+    codes_per_byte: int = 1  # a raw code tensor's K is the matrix's K over this
+    raw_view: Callable = lambda t: t      # how a carried tensor is read (MXFP4: float4 / e8m0 dtypes as their bytes)
+    mark_why: Optional[str] = None        # not None: the launches take only buffers that carry the packer's mark, and this is why
+    mark_exclusive: bool = False          # a buffer with this format's mark is refused under every other expert_format
+    recount_keys: tuple = ()              # raw entries weight_bytes counts a second time (their packed form is twice as wide)
+
+    @property
+    def wide_code(self):
+        """the wide calls' expert_format code"""
+        return WIDE_FORMAT_CODES_SERVED[self.name]
+
+    @property
+    def gu_keys(self):
+        return tuple("experts_gu" + s for s in self.raw_keys)
+
+    @property
+    def down_keys(self):
+        return tuple("experts_down" + s for s in self.raw_keys)
+
+    def check_layers(self, layers, carried, dtype):
+        """every sparse layer of a raw weights dict carries this format (or none does), with tensors the kernels take"""
+        if not all(carried):
+            raise SamdError(f"a mix of {self.mix_label} sparse layers ({sum(carried)} of {len(carried)} carry {self.label} experts): "
+                            "the runner takes the experts of all sparse layers in one format")
+        for i, l in enumerate(layers):
+            if "experts_gu" in l:
+                self.check(*(tuple(l[k] if j == 0 else l.get(k) for j, k in enumerate(ks)) for ks in (self.gu_keys, self.down_keys)), dtype,
+                           f"layer {i} experts")
+
+
+def _has_any(keys):
+    return lambda l: any(k in l for k in keys)
+
+
+def _import_experts_plain(ex, name, dtype, dev, qcfg, qcfg8):
+    """HF's fused expert tensors [E, 2 I, H] / [E, H, I] in the model dtype"""
+    return {k: t.detach().to(device=dev, dtype=dtype).contiguous() for k, t in (("experts_gu", ex.gate_up_proj), ("experts_down", ex.down_proj))}
+
+
+def _import_experts_mxfp4(ex, name, dtype, dev, qcfg, qcfg8):
+    """the 4-bit expert tensors and their block scales, as they are"""
+    raw = lambda t: MX._bytes(t.detach()).to(dev).contiguous()
+    return dict(experts_gu=raw(ex.gate_up_proj), experts_gu_scale=raw(ex.gate_up_proj_scale),
+                experts_down=raw(ex.down_proj), experts_down_scale=raw(ex.down_proj_scale))
+
+
+def _quantize_experts_mxfp4(gate_up, down, dtype, name):
+    quad = quantize_experts(gate_up, down, dtype, name)
+    return quad[:2], quad[2:]
+
+
+_PLAIN = ExpertFormat(
+    name=None, label="model-dtype",
+    doc="HF's fused expert tensors mlp.experts.gate_up_proj [E, 2 I, H] / down_proj [E, H, I], in the model dtype",
+    mix_label="", raw_keys=("",), carried=lambda l: False, carries_kw="", check=None, quantize=None,
+    pack=lambda gu, down, dtype: pack_experts(gu[0], down[0]), packer="pack_experts", import_hf=_import_experts_plain,
+    packed_bytes=None, launch_suffix="")
+_INT8 = ExpertFormat(
+    name="int8g128", label="INT8",
+    doc="every sparse layer holds an indexable `mlp.experts` of E modules whose gate_proj / up_proj / down_proj are ALL 8-bit GPTQ modules "
+        "(the `Qwen3-30B-A3B-GPTQ-Int8` kind): each is imported through int8.linear_int8 with the config's quantization_config (so "
+        "act-order, group sizes 32 / 64, AWQ or a stored 255 under 'gptq' raise by module name), gate|up fused per expert, the experts "
+        "stacked, the scales rounded once for a bf16 runner", mix_label="INT8 and other", raw_keys=("", "_z8", "_s8"),
+    carried=_has_any(("experts_gu_z8", "experts_gu_s8", "experts_down_z8", "experts_down_s8")), carries_kw="carries_int8",
+    check=check_int8_experts, quantize=quantize_experts_int8, pack=pack_experts_int8, packer="pack_experts_int8",
+    import_hf=lambda ex, name, dtype, dev, qcfg, qcfg8: import_experts_int8(ex, name, dtype, dev, qcfg),
+    packed_bytes=I8.packed_bytes, launch_suffix="_i8",
+    mark_why="the byte count alone does not tell a packed INT8 buffer from other bytes", mark_exclusive=True,
+    recount_keys=("experts_gu_z8", "experts_down_z8"))       # the packed bytes are N K 33 / 32: a zero point is a 16-bit word there
+_INT4 = ExpertFormat(
+    name="int4g128", label="INT4",
+    doc="every sparse layer holds an indexable `mlp.experts` of E modules whose gate_proj / up_proj / down_proj are AWQ / GPTQ modules "
+        "(`mlp.experts.{e}.gate_proj.qweight` ...): each is imported through int4.linear_int4 with the config's quantization_config (so "
+        "act-order, group sizes 32 / 64, GEMV or a v1 zero point of 15 raise by module name), gate|up fused per expert, the experts "
+        "stacked, the scales rounded once for a bf16 runner", mix_label="INT4 and other", raw_keys=("", "_z", "_s"),
+    carried=_has_any(("experts_gu_z", "experts_gu_s", "experts_down_z", "experts_down_s")), carries_kw="carries_int4",
+    check=check_int4_experts, quantize=quantize_experts_int4, pack=pack_experts_int4, packer="pack_experts_int4",
+    import_hf=lambda ex, name, dtype, dev, qcfg, qcfg8: import_experts_int4(ex, name, dtype, dev, qcfg),
+    packed_bytes=I4.packed_bytes, launch_suffix="_i4",
+    codes_per_byte=2, mark_why="an MXFP4 buffer of this shape has the same byte count and other contents")
+_FP8 = ExpertFormat(
+    name="fp8b128", label="FP8",
+    doc="every sparse layer holds transformers' fused FP8Experts (`mlp.experts.gate_up_proj` + `gate_up_proj_scale_inv`, `down_proj` + "
+        "`down_proj_scale_inv`; Qwen3-30B-A3B-FP8: weight_block_size [128, 128]) or per-expert modules (`mlp.experts.{e}.gate_proj.weight` "
+        "+ `weight_scale_inv`): codes and scales are imported as they are (samd_hip/fp8.py has the rejections, by tensor name)",
+    mix_label="block-scaled FP8 and other", raw_keys=("", "_sinv"),
+    carried=lambda l: "experts_gu_sinv" in l or "experts_down_sinv" in l or F8.is_fp8_dtype(l["experts_gu"].dtype) or F8.is_fp8_dtype(l["experts_down"].dtype),
+    carries_kw="carries_fp8", check=lambda gu, down, dtype, name: check_fp8_experts(gu, down, name),
+    quantize=lambda gate_up, down, dtype, name: quantize_experts_fp8(gate_up, down, name),
+    pack=lambda gu, down, dtype: pack_experts_fp8(gu, down), packer="pack_experts_fp8",      # (the buffer serves both model dtypes)
+    import_hf=lambda ex, name, dtype, dev, qcfg, qcfg8: import_experts_fp8(ex, name, dev, qcfg8),
+    packed_bytes=F8.packed_block_bytes, launch_suffix="_f8", meta_dtype=lambda t: torch.float8_e4m3fn if t.dtype == torch.uint8 else t.dtype)
+_MXFP4 = ExpertFormat(
+    name="mxfp4", label="MXFP4",
+    doc="every sparse layer's fused expert tensors are 4-bit, with their block scales (this project's own convention, the module "
+        "docstring): imported as they are", mix_label="4-bit and model-dtype", raw_keys=("", "_scale"),
+    # 4-bit tensors that no other format's keys claim
+    carried=lambda l: not any(f.carried(l) for f in (_INT8, _INT4, _FP8)) and (is_4bit(l["experts_gu"]) or is_4bit(l["experts_down"])),
+    carries_kw="carries_4bit", check=lambda gu, down, dtype, name: check_quantised_experts(*gu, *down, dtype, name),
+    quantize=_quantize_experts_mxfp4, pack=lambda gu, down, dtype: pack_experts_mxfp4(*gu, *down), packer="pack_experts_mxfp4",
+    import_hf=_import_experts_mxfp4, packed_bytes=MX.packed_bytes, launch_suffix="_f4", meta_dtype=lambda t: torch.uint8, codes_per_byte=2,
+    raw_view=MX._bytes)
+EXPERT = {f.name: f for f in (_PLAIN, _MXFP4, _INT4, _FP8, _INT8)}
+
+
+def experts_carried(layers):
+    """{expert format: per sparse layer of a raw weights dict, does it carry that format's expert tensors?}"""
+    sparse = [l for l in layers if "experts_gu" in l]
+    return {f.name: [f.carried(l) for l in sparse] for f in EXPERT.values() if f.name is not None}
+
+
+def resolve_carried(expert_format, carried, has_sparse):
+    """resolve_expert_format over experts_carried's answer"""
+    return resolve_expert_format(expert_format, has_sparse=has_sparse, **{EXPERT[n].carries_kw: any(c) for n, c in carried.items()})
