@@ -120,6 +120,15 @@ int samd_static_derived_info(const samd_static_t *sam, int64_t out[6]);
  * next to the image, like everything samd_static_derived_info reports.  Blocks come only with the bigram table and never with the edge table;
  * a failed derivation leaves none of the three. */
 int samd_static_edge_blocks_info(const samd_static_t *sam, int64_t out[4]);
+/* host copies of the derived walk tables exactly as they lie on the device, for tests that model their layout (the static analog of
+ * samd_session_export_table): 16-byte slots as 4 x uint32 -- the bigram table (samd_static_derived_info out[3] slots), the root entries
+ * (vocab slots), the child bitmap ((vocab + 31) / 32 words), the edge table (out[5] slots), the hot words (n_states slots), the edge blocks
+ * (samd_static_edge_blocks_info out[2] slots), the chain words (n_states slots).  A null buffer skips its table; a buffer for a table the
+ * handle does not have is SAMD_E_INVALID.  Synchronous device-to-host copies only: no kernel is launched and nothing changes.  No stream
+ * argument is needed: every call that derives these tables (samd_static_upload, samd_static_adopt_device, samd_static_set_bigram_slots) is
+ * blocking -- it synchronises the stream it launched on before it returns -- so the tables are complete whenever the handle says it has them. */
+int samd_static_export_tables(const samd_static_t *sam, uint32_t *h_bigram, uint32_t *h_root16, uint32_t *h_rc_bits, uint32_t *h_edge_table,
+                              uint32_t *h_hot, uint32_t *h_blocks, uint32_t *h_chain);
 /* re-size the bigram table of an uploaded automaton: slots_per_pair in 2 .. 64 (0 = the default, 4).  A tuning entry with no reference
  * counterpart: a sparser table only helps the BATCHED walk (samd_static_walk* / samd_static_lookup_batch: 64 cursors in lock-step pay a
  * second probe round when any collides -- 16 per pair measured best, profiles/r04_walk.md); one-cursor walks of a session are

@@ -318,6 +318,32 @@ int samd_static_derived_info(const samd_static_t *s, int64_t out[6]) {
     return SAMD_OK;
 }
 
+// host copies of the derived walk tables as they lie on the device (tests that model their layout): synchronous D2H copies, no launch, no
+// change of state.  A null buffer skips its table; a buffer for a table the handle does not have is an error.
+int samd_static_export_tables(const samd_static_t *s, uint32_t *h_bigram, uint32_t *h_root16, uint32_t *h_rc_bits, uint32_t *h_edge_table,
+                              uint32_t *h_hot, uint32_t *h_blocks, uint32_t *h_chain) {
+    if (!s || !s->uploaded) { samd_set_error("samd_static_export_tables: the automaton is not uploaded"); return SAMD_E_INVALID; }
+    const bool blocks = s->d_hot && s->d_blocks;
+    const struct { void *dst; const void *src; int64_t bytes; const char *what; } t[] = {
+        { h_bigram, s->d_d1hash, s->n_d1hash * 16, "bigram table" },
+        { h_root16, s->d_d1hash ? s->d_root16 : nullptr, s->vocab * 16, "root entries" },
+        { h_rc_bits, s->d_d1hash ? s->d_rc_bits : nullptr, ((s->vocab + 31) / 32) * 4, "child bitmap" },
+        { h_edge_table, s->d_ehash, s->n_ehash * 16, "edge table" },
+        { h_hot, blocks ? s->d_hot : nullptr, s->n_states * 16, "hot words" },
+        { h_blocks, blocks ? s->d_blocks : nullptr, s->n_block_slots * 16, "edge blocks" },
+        { h_chain, s->d_chain, s->n_states * 16, "chain words" },
+    };
+    for (const auto &e : t)
+        if (e.dst && !e.src) { samd_set_error("samd_static_export_tables: the handle has no %s", e.what); return SAMD_E_INVALID; }
+    for (const auto &e : t) {
+        if (!e.dst || e.bytes <= 0) continue;
+        if (hipMemcpy(e.dst, e.src, (size_t)e.bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+            (void)hipGetLastError(); samd_set_error("samd_static_export_tables: copying the %s failed", e.what); return SAMD_E_HIP;
+        }
+    }
+    return SAMD_OK;
+}
+
 int samd_static_edge_blocks_info(const samd_static_t *s, int64_t out[4]) {
     if (!s || !out) return SAMD_E_INVALID;
     const bool on = s->d_hot && s->d_blocks;

@@ -84,6 +84,7 @@ _PROTOS = {
     "samd_static_from_pickle": (C.c_int, [C.c_char_p, _I32, _VP, _VP]),
     "samd_static_derived_info": (C.c_int, [_VP, _VP]),
     "samd_static_edge_blocks_info": (C.c_int, [_VP, _VP]),
+    "samd_static_export_tables": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "samd_static_set_bigram_slots": (C.c_int, [_VP, _I32, _VP]),
     "samd_static_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "samd_static_device_image": (C.c_int, [_VP, _VP, _VP]),
@@ -394,6 +395,20 @@ class StaticAutomaton:
         walk likes 16"""
         check(lib().samd_static_set_bigram_slots(self._h, int(slots_per_pair), current_stream()))
         return self
+
+    def export_tables(self):
+        """the derived walk tables as they lie on the device (samd_static_export_tables): uint32 [slots, 4] arrays (rc_bits: uint32 [words]),
+        None for a table the handle does not have.  Tests compare them with a model of the hashes and the fill."""
+        i, d = self.info(), self.derived_info()
+        n, vocab = i["n_states"], i["vocab"]
+        blocks = d["hot_word_bytes"] > 0
+        rows = dict(bigram=d["bigram_slots"] or None, root16=vocab if d["bigram_slots"] else None, edge_table=d["edge_table_slots"] or None,
+                    hot=n if blocks else None, blocks=d["edge_block_slots"] if blocks else None, chain=n if d["chain_bytes"] else None)
+        out = {k: (None if r is None else np.zeros((r, 4), np.uint32)) for k, r in rows.items()}
+        out["rc_bits"] = np.zeros((vocab + 31) // 32, np.uint32) if d["bigram_slots"] else None
+        order = ("bigram", "root16", "rc_bits", "edge_table", "hot", "blocks", "chain")
+        check(lib().samd_static_export_tables(self._h, *[_ptr(out[k]) if out[k] is not None and out[k].size else None for k in order]))
+        return out
 
     def export(self):
         i = self.info()
