@@ -20,7 +20,13 @@ PROJECTIONS = ("wqkv", "wo", "wgu", "wdown")
 
 
 def is_f4_tensor(t):
-    return t.dtype == torch.uint8 or MX.is_fp4_dtype(t.dtype)
+    """is this tensor 4-bit codes -- packed bytes or float4_e2m1fn_x2?  (None is not.)  moe.is_4bit is the same test"""
+    return t is not None and (t.dtype == torch.uint8 or MX.is_fp4_dtype(t.dtype))
+
+
+def tiles(N, K):
+    """does an [N, K] matrix fit the streaming kernels' tiles?"""
+    return N % 128 == 0 and K % 256 == 0
 
 
 def _nbytes(t):
@@ -66,7 +72,7 @@ class DenseFormat(NamedTuple):
 
 
 def _need_tiles(N, K, what, kernel):
-    if N % 128 != 0 or K % 256 != 0:
+    if not tiles(N, K):
         raise SamdError(f"{what}: the {kernel} kernel needs N % 128 == 0 and K % 256 == 0")
 
 
@@ -112,7 +118,7 @@ def precheck_f8b(shape, weights):
     for li, l in enumerate(weights["layers"]):
         for k in PROJECTIONS:
             N, K = l[k].shape
-            if N % 128 != 0 or K % 256 != 0:
+            if not tiles(N, K):
                 raise SamdError(f"block-scaled FP8 projection {k} of layer {li}, shape ({N}, {K}): the kernel needs N % 128 == 0 and K % 256 == 0")
 
 

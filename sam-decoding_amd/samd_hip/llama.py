@@ -17,12 +17,9 @@ import torch
 
 from . import (F16, BF16, MAX_DRAFT, TILE_ROWS, QkvEpilogue, SamdError, Session, Warm, _ptr, check, current_stream, lib, require_gpu,
                torch_dtype_code)
-from . import fp8 as F8
-from . import mxfp4 as MX
-from . import int4 as I4
-from . import int8 as I8
+from . import hf_import as HF
 from . import moe as MOE
-from .formats import DENSE, DENSE_FORMATS, PROJECTIONS, QUANT_FORMATS, is_f4_tensor as _is_f4_tensor
+from .formats import DENSE, DENSE_FORMATS, PROJECTIONS, QUANT_FORMATS
 
 
 def _env_weight_format(weight_format):
@@ -510,341 +507,16 @@ class LlamaRunner:
         experts of another format stay rejected.  share_weights does not apply to dequantised projections (there is no HF `weight` to
         re-point)."""
         weight_format = _env_weight_format(weight_format)
-        m = lm.model
-        parts = (("self_attn", "q_proj"), ("self_attn", "k_proj"), ("self_attn", "v_proj"), ("self_attn", "o_proj"), ("mlp", "gate_proj"),
-                 ("mlp", "up_proj"), ("mlp", "down_proj"))
-        linears = [(f"layers.{i}.{a}.{b}", getattr(getattr(lyr, a), b)) for i, lyr in enumerate(m.layers) for a, b in parts
-                   if hasattr(getattr(lyr, a), b)]               # (a sparse layer's MLP has no gate / up / down projections of its own)
-        qcfg = I4.quant_config(getattr(lm, "config", None))
-        # 8-bit GPTQ modules are decided first: they carry qweight / qzeros / scales too, so the INT4 test below is true for them
-        # In a module with sparse layers they are taken when EVERY sparse layer's experts are 8-bit GPTQ modules throughout (expert_format
-        # "int8g128"); then the attention and dense-MLP projections may be 8-bit too (dequantised once at import, the docstring).  Anywhere
-        # else in such a module -- some experts or projections of a layer only, a router, 8-bit projections beside other experts -- an 8-bit
-        # module raises by name
-        sparse0 = cls._hf_sparse_layers(m.layers)
-        full8 = [sp and cls._hf_experts_are_int8(lyr, qcfg) for lyr, sp in zip(m.layers, sparse0)]
-        moe_i8 = any(sparse0) and full8 == sparse0
-        if any(sparse0):
-            served = {f"{a}.{b}" for a, b in parts} if moe_i8 else set()
-            for i in sorted(range(len(m.layers)), key=lambda i: full8[i]):       # (a layer whose experts are 8-bit only in part is named first)
-                lyr = m.layers[i]
-                for n, mod in lyr.named_modules():
-                    if n and I8.is_int8_module(mod, qcfg) and n not in served and not (moe_i8 and sparse0[i] and n.startswith("mlp.experts.")):
-                        if moe_i8 and n == "mlp.gate":
-                            raise SamdError(f"layers.{i}.{n}: an 8-bit router is not supported: the router stays a plain `weight` in the model dtype")
-                        if moe_i8:
-                            raise SamdError(f"layers.{i}.{n}: an 8-bit GPTQ module in a mixture-of-experts model with INT8 experts: only the "
-                                            "experts, the attention projections and a dense layer's MLP projections may be 8-bit")
-                        raise SamdError(f"layers.{i}.{n}: an 8-bit GPTQ module in a mixture-of-experts model whose sparse layers' experts are not "
-                                        "all 8-bit GPTQ modules throughout: 8-bit modules are taken there only beside such experts (expert_format "
-                                        "'int8g128'); weight_format 'int8g128' covers dense models only, and nothing is dequantised silently")
-        ckpt_i8 = I8.checkpoint_is_int8(linears, qcfg)           # all seven projections of every layer, or a SamdError for a mix
-        ckpt_i4 = (not ckpt_i8) and I4.checkpoint_is_int4(linears)   # AWQ / GPTQ modules (qweight / qzeros / scales, no `weight`)
-        # a module with block-scaled FP8 EXPERTS (the official Qwen3-MoE FP8 checkpoints) is not a weight_format "fp8" one: its FP8 attention
-        # and dense-MLP projections are dequantised once at import (the docstring).  Decided before checkpoint_is_fp8, which rejects block scales
-        layer_f8 = [cls._hf_experts_are_fp8(lyr, i) for i, lyr in enumerate(m.layers)]
-        moe_f8_dense = any(layer_f8)
-        qcfg8 = getattr(getattr(lm, "config", None), "quantization_config", None)
-        # a module WITHOUT sparse layers whose projections are all block-scaled FP8 (the dense Qwen3-*-FP8 checkpoints) is imported as it is,
-        # codes and scales untouched, and the runner is "fp8b128" by itself; modules with sparse layers are left to the branches above
-        ckpt_f8b = (not ckpt_i4) and (not ckpt_i8) and (not moe_f8_dense) and not any(cls._hf_sparse_layers(m.layers)) and F8.checkpoint_is_fp8_block(linears, qcfg8)
-        if ckpt_f8b:
-            if weight_format not in (None, "fp8b128"):
-                raise SamdError(f"the module carries block-scaled FP8 projections; weight_format {weight_format!r} would need them dequantised "
-                                "(pass None or 'fp8b128')")
-            for name, lin in linears:                            # shapes the kernel cannot run, by projection, before any device work
-                N, K = lin.weight.shape
-                if N % 128 != 0 or K % 256 != 0:
-                    raise SamdError(f"{name}: a block-scaled FP8 projection of shape ({N}, {K}); the kernel needs N % 128 == 0 and K % 256 == 0")
-        ckpt_f8 = (not ckpt_i4) and (not ckpt_i8) and (not moe_f8_dense) and (not ckpt_f8b) and F8.checkpoint_is_fp8(linears)
-        ckpt_f4 = (not ckpt_i4) and (not ckpt_i8) and MX.checkpoint_is_mxfp4(linears)
-        if F8.is_fp8_dtype(lm.lm_head.weight.dtype) or F8.is_fp8_dtype(m.embed_tokens.weight.dtype):
-            raise SamdError("FP8 embedding / lm_head weights are not supported: they stay in the model dtype")
-        if _is_f4_tensor(lm.lm_head.weight) or _is_f4_tensor(m.embed_tokens.weight):
-            raise SamdError("4-bit embedding / lm_head weights are not supported: they stay in the model dtype")
-        dtype = dtype or next(p.dtype for p in lm.parameters() if p.dtype.is_floating_point and p.dtype.itemsize >= 2)
-        qkv_bias, qk_norm = cls._hf_layer_extras(m.layers)
-        shape = LlamaShape(lm.config, qkv_bias=qkv_bias, qk_norm=qk_norm)
-        sparse = cls._hf_sparse_layers(m.layers)
-        # a module with INT4 EXPERTS whose attention / dense-MLP projections are INT4 too (an AWQ / GPTQ mixture-of-experts checkpoint):
-        # these are dequantised once at import (the docstring), so the runner is not a weight_format "int4g128" one.  INT4 projections
-        # beside model-dtype or MXFP4 experts stay rejected as before
-        experts_i4 = [not moe_i8 and cls._hf_experts_are_int4(lyr, i) for i, lyr in enumerate(m.layers) if sparse[i]]
-        moe_i4_dense = ckpt_i4 and any(experts_i4)
-        if moe_i4_dense:
-            ckpt_i4 = False
-        # the same for a module with INT8 EXPERTS whose attention / dense-MLP projections are 8-bit too (a GPTQ-Int8 mixture-of-experts
-        # checkpoint): dequantised once at import, the runner is not a weight_format "int8g128" one
-        moe_i8_dense = ckpt_i8 and moe_i8
-        if moe_i8_dense:
-            ckpt_i8 = False
-        # the one dense format the module's projections are imported in, as they are (at most one detector holds); None: plain weights
-        ckpt = DENSE.get("int4g128" if ckpt_i4 else "int8g128" if ckpt_i8 else "mxfp4" if ckpt_f4 else "fp8b128" if ckpt_f8b else "fp8" if ckpt_f8 else None)
-        if any(sparse) or shape.moe:
-            if sparse != list(shape.sparse):
-                raise SamdError(f"the module's sparse MLP layers {[i for i, x in enumerate(sparse) if x]} are not the ones its config implies "
-                                f"{[i for i, x in enumerate(shape.sparse) if x]} (model_type '{shape.model_type}')")
-            MOE.reject_unsupported(ckpt.name if ckpt is not None else weight_format, kw.get("native_gemm", True), kw.get("draft_head", False))
-        # 4-bit experts: decided and checked on the module's own tensors, before anything moves to the device (the runner resolves the
-        # format again from the weights it is given)
-        experts4 = [not i4e and not moe_i8 and not layer_f8[i] and cls._hf_experts_are_4bit(lyr, i)
-                    for (i, lyr), i4e in zip(((i, lyr) for i, lyr in enumerate(m.layers) if sparse[i]), experts_i4)]
-        experts_f8 = [layer_f8[i] for i in range(len(m.layers)) if sparse[i]]
-        MOE.resolve_expert_format(expert_format, any(experts4), any(sparse) or shape.moe, carries_int4=any(experts_i4), carries_fp8=any(experts_f8),
-                                  carries_int8=moe_i8)
-        # the expert format the module's sparse layers are imported in, as they are; None: HF's fused model-dtype tensors
-        ckpt_experts = MOE.EXPERT["fp8b128" if any(experts_f8) else "int4g128" if any(experts_i4) else "int8g128" if moe_i8 else "mxfp4" if any(experts4) else None]
-        if any(experts_f8):
-            if not all(experts_f8):
-                plain = [i for i, sp in enumerate(sparse) if sp and not layer_f8[i]][:3]
-                raise SamdError(f"a mix of block-scaled FP8 and other sparse layers ({sum(experts_f8)} of {len(experts_f8)} carry FP8 experts; "
-                                f"e.g. layers {plain} do not): the runner takes the experts of all sparse layers in one format")
-            for i, lyr in enumerate(m.layers):
-                if not sparse[i]:
-                    continue
-                ex = lyr.mlp.experts
-                n_ex = ex.gate_up_proj.shape[0] if hasattr(ex, "gate_up_proj") else len(ex)
-                if n_ex != shape.n_experts:
-                    raise SamdError(f"layers.{i}.mlp.experts: {n_ex} experts, the config says num_experts = {shape.n_experts}")
-                gate = getattr(lyr.mlp, "gate", None)
-                if gate is None or getattr(gate, "weight", None) is None or F8.is_fp8_dtype(gate.weight.dtype):
-                    raise SamdError(f"layers.{i}.mlp.gate: an FP8 router is not supported: the router stays a plain `weight` in the model dtype")
-        if any(experts_i4) and not all(experts_i4):
-            plain = [i for i, sp in enumerate(sparse) if sp and not cls._hf_experts_are_int4(m.layers[i], i)][:3]
-            raise SamdError(f"a mix of INT4 and other sparse layers ({sum(experts_i4)} of {len(experts_i4)} carry INT4 experts; e.g. layers "
-                            f"{plain} do not): the runner takes the experts of all sparse layers in one format")
-        for i, lyr in enumerate(m.layers):
-            if sparse[i] and (any(experts_i4) or moe_i8) and len(lyr.mlp.experts) != shape.n_experts:
-                raise SamdError(f"layers.{i}.mlp.experts: {len(lyr.mlp.experts)} expert modules, the config says num_experts = {shape.n_experts}")
-            if sparse[i] and I4.is_int4_module(getattr(lyr.mlp, "gate", None)):
-                raise SamdError(f"layers.{i}.mlp.gate: an INT4 router is not supported: the router stays a plain `weight` in the model dtype")
-        if any(experts4):
-            if not all(experts4):
-                plain = [i for i, sp in enumerate(sparse) if sp and not cls._hf_experts_are_4bit(m.layers[i], i)][:3]
-                raise SamdError(f"a mix of 4-bit and model-dtype sparse layers ({sum(experts4)} of {len(experts4)} carry MXFP4 experts; e.g. "
-                                f"layers {plain} do not): the runner takes the experts of all sparse layers in one format")
-            for i, lyr in enumerate(m.layers):
-                if sparse[i]:
-                    ex = lyr.mlp.experts
-                    MOE.check_quantised_experts(ex.gate_up_proj.detach(), getattr(ex, "gate_up_proj_scale", None), ex.down_proj.detach(),
-                                                getattr(ex, "down_proj_scale", None), dtype, f"layers.{i}.mlp.experts")
-        dev = torch.device(device)
+        # samd_hip/hf_import.py: every question about the module and every refusal that needs no device, then the import loop
+        ckpt = HF.classify(lm, weight_format, expert_format, dtype, kw.get("native_gemm", True), kw.get("draft_head", False))
+        weights = HF.load(lm, ckpt, device, share_weights)
+        return cls(ckpt.shape, weights, max_cache_len, ckpt.dtype, device, weight_format=weight_format, expert_format=expert_format, **kw)
 
-        def get(t):
-            return t.detach().to(device=dev, dtype=dtype).contiguous()
-        m = lm.model
-        layers = []
-        # The runner reads q|k|v and gate|up as ONE matrix each.  When the HF module already lives on this device in this dtype, its
-        # separate projection weights are re-pointed at row slices of the concatenated matrices (same values, the module keeps working),
-        # so the model exists once row-major (+ once packed) instead of the HF copy + the concatenated copy + the packed copy.
-        # Opt-in (share_weights=True / SAMD_SHARE_HF_WEIGHTS=1): by default the caller's module is left untouched.
-        share = (os.environ.get("SAMD_SHARE_HF_WEIGHTS", "0") == "1") if share_weights is None else bool(share_weights)
-        shared = [0]
-
-        def lin_w(mod, name):
-            """a projection's weight; an INT4 module's (a module with sparse layers only) dequantised: rne_dtype((q - z) * s), one rounding"""
-            if moe_f8_dense and F8.is_fp8_dtype(mod.weight.dtype):   # beside FP8 experts: rne_dtype(fl32(float(q) * s)), one rounding
-                return F8.linear_fp8_dequantized(mod, name, qcfg8).to(dtype)
-            if not I4.is_int4_module(mod):
-                return mod.weight
-            if I8.is_int8_module(mod, qcfg):                     # beside INT8 experts: rne_dtype((q - z) * s) again, through int8.py
-                q, z, sc = I8.linear_int8(mod, name, config=qcfg)
-                return I8.dequantize_groups(q, z, I8.as_scales(sc, dtype, name)).to(dtype)
-            q, z, sc = I4.linear_int4(mod, name, config=qcfg)
-            return I4.dequantize_groups(q, z, I4.as_scales(sc, dtype, name)).to(dtype)
-
-        def fuse(linears, names=None):
-            if moe_i4_dense or moe_i8_dense or (moe_f8_dense and any(F8.is_fp8_dtype(l.weight.dtype) for l in linears)):
-                return get(torch.cat([lin_w(l, n).to(dtype) for l, n in zip(linears, names)], dim=0))
-            ws = [l.weight for l in linears]
-            cat = get(torch.cat(ws, dim=0))
-            if share and all(w.device == cat.device and w.dtype == cat.dtype for w in ws):
-                r = 0
-                for l in linears:
-                    n = l.weight.shape[0]
-                    l.weight.data = cat[r:r + n]
-                    r += n
-                shared[0] += 1
-            return cat
-        for lyr in m.layers:
-            a, f = lyr.self_attn, lyr.mlp
-            extra = {}                                           # Qwen2 q|k|v bias, Qwen3 q / k norm (samd_rope_kv_write_epi)
-            if qkv_bias:
-                extra["bqkv"] = get(torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias]))
-            if qk_norm:
-                extra["q_norm"], extra["k_norm"] = get(a.q_norm.weight), get(a.k_norm.weight)
-            li = len(layers)
-            if ckpt is not None:                                 # the checkpoint's own codes and side data; the runner checks and packs them
-                lw = {}
-                for k, own, part, names in (("wqkv", a, "self_attn", ("q_proj", "k_proj", "v_proj")), ("wo", a, "self_attn", ("o_proj",)),
-                                            ("wgu", f, "mlp", ("gate_proj", "up_proj")), ("wdown", f, "mlp", ("down_proj",))):
-                    got = ckpt.import_hf([getattr(own, x) for x in names], names, li, part, dev, dtype, qcfg, qcfg8)
-                    lw.update({k + sfx: t for sfx, t in zip(ckpt.raw_keys, got)})
-                layers.append(dict(lw, ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
-            qkv_names, o_name = [f"layers.{li}.self_attn.{x}" for x in ("q_proj", "k_proj", "v_proj")], f"layers.{li}.self_attn.o_proj"
-            if sparse[li]:                                       # router + the experts as the module holds them (moe.EXPERT: import_hf)
-                layers.append(dict(
-                    wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names), wo=get(lin_w(a.o_proj, o_name)), router=get(f.gate.weight),
-                    **ckpt_experts.import_hf(f.experts, f"layers.{li}.mlp.experts", dtype, dev, qcfg, qcfg8),
-                    ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-                continue
-            layers.append(dict(
-                wqkv=fuse((a.q_proj, a.k_proj, a.v_proj), qkv_names),
-                wo=get(lin_w(a.o_proj, o_name)),
-                wgu=fuse((f.gate_proj, f.up_proj), [f"layers.{li}.mlp.gate_proj", f"layers.{li}.mlp.up_proj"]),
-                wdown=get(lin_w(f.down_proj, f"layers.{li}.mlp.down_proj")),
-                ln1=get(lyr.input_layernorm.weight), ln2=get(lyr.post_attention_layernorm.weight), **extra))
-        weights = dict(embed=get(m.embed_tokens.weight), layers=layers, norm=get(m.norm.weight), lm_head=get(lm.lm_head.weight))
-        if shared[0]:
-            import logging
-            logging.getLogger("samd_hip").info("LlamaRunner.from_hf: %d fused projection groups now back the HF module's q/k/v and gate/up "
-                                               "weights (share_weights); its parameters are views of the runner's matrices", shared[0])
-        return cls(shape, weights, max_cache_len, dtype, device, weight_format=weight_format, expert_format=expert_format, **kw)
-
-    @classmethod
-    def _hf_experts_are_4bit(cls, lyr, i):
-        """does sparse layer i carry pre-quantised experts?  Both fused tensors 4-bit: True; neither: False; one of them raises by name"""
-        ex = lyr.mlp.experts
-        gu, dn = MOE.is_4bit(ex.gate_up_proj), MOE.is_4bit(ex.down_proj)
-        if gu != dn:
-            raise SamdError(f"layers.{i}.mlp.experts: gate_up_proj is {ex.gate_up_proj.dtype} and down_proj {ex.down_proj.dtype}; "
-                            "4-bit experts need both tensors 4-bit")
-        return gu
-
-    @classmethod
-    def _hf_experts_are_fp8(cls, lyr, i):
-        """does layer i hold FP8 experts -- the fused form (transformers' FP8Experts: float8 gate_up_proj and down_proj) or an indexable
-        `mlp.experts` of modules whose gate_proj / up_proj / down_proj weights are all float8?  All: True; none (or no experts): False; some
-        only: raises by name"""
-        ex = getattr(getattr(lyr, "mlp", None), "experts", None)
-        if ex is None:
-            return False
-        if hasattr(ex, "gate_up_proj"):
-            kinds = [(f"layers.{i}.mlp.experts.{p}", F8.is_fp8_dtype(getattr(ex, p).dtype)) for p in ("gate_up_proj", "down_proj")
-                     if getattr(ex, p, None) is not None]
-        elif hasattr(ex, "__len__") and hasattr(ex, "__getitem__"):
-            kinds = [(f"layers.{i}.mlp.experts.{e}.{p}", F8.is_fp8_dtype(getattr(ex[e], p).weight.dtype))
-                     for e in range(len(ex)) for p in MOE.INT4_EXPERT_PROJECTIONS if getattr(getattr(ex[e], p, None), "weight", None) is not None]
-        else:
-            return False
-        n8 = sum(k for _, k in kinds)
-        if 0 < n8 < len(kinds):
-            plain = [n for n, k in kinds if not k][:3]
-            raise SamdError(f"layers.{i}.mlp.experts: a mix of FP8 and other expert tensors ({n8} of {len(kinds)} are FP8; e.g. "
-                            f"{', '.join(plain)} are not): FP8 experts need every expert tensor float8_e4m3fn")
-        return n8 > 0
-
-    @classmethod
-    def _hf_experts_are_int8(cls, lyr, config=None):
-        """does the layer hold per-expert 8-bit GPTQ modules -- an indexable `mlp.experts` of modules whose gate_proj, up_proj and down_proj
-        are ALL 8-bit (int8.is_int8_module)?  Anything less is False: from_hf then refuses whatever 8-bit module it finds, by name"""
-        ex = getattr(getattr(lyr, "mlp", None), "experts", None)
-        if ex is None or hasattr(ex, "gate_up_proj") or not hasattr(ex, "__len__") or not hasattr(ex, "__getitem__") or len(ex) == 0:
-            return False
-        return all(I8.is_int8_module(getattr(ex[e], p, None), config) for e in range(len(ex)) for p in MOE.INT4_EXPERT_PROJECTIONS)
-
-    @classmethod
-    def _hf_experts_are_int4(cls, lyr, i):
-        """does layer i hold per-expert INT4 (AWQ / GPTQ) modules -- an indexable `mlp.experts` of modules with gate_proj / up_proj / down_proj
-        that are all INT4 (int4.is_int4_module)?  All: True; none (or the fused form, or no experts): False; some experts or some of the
-        three projections only: raises by name"""
-        ex = getattr(getattr(lyr, "mlp", None), "experts", None)
-        if ex is None or hasattr(ex, "gate_up_proj") or not hasattr(ex, "__len__") or not hasattr(ex, "__getitem__"):
-            return False
-        kinds = [(f"layers.{i}.mlp.experts.{e}.{p}", I4.is_int4_module(getattr(ex[e], p, None)))
-                 for e in range(len(ex)) for p in MOE.INT4_EXPERT_PROJECTIONS]
-        n4 = sum(k for _, k in kinds)
-        if 0 < n4 < len(kinds):
-            plain = [n for n, k in kinds if not k][:3]
-            raise SamdError(f"layers.{i}.mlp.experts: a mix of INT4 and other expert projections ({n4} of {len(kinds)} are INT4; e.g. "
-                            f"{', '.join(plain)} are not): INT4 experts need gate_proj, up_proj and down_proj of every expert INT4")
-        return n4 > 0
-
-    # the parameters of a decoder layer that from_hf reads (named_parameters; FP8 checkpoints' weight_scale tensors are buffers)
-    _LAYER_PARAMS = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
-                     "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight", "input_layernorm.weight", "post_attention_layernorm.weight")
-    _QKV_BIAS = ("self_attn.q_proj.bias", "self_attn.k_proj.bias", "self_attn.v_proj.bias")
-    _QK_NORM = ("self_attn.q_norm.weight", "self_attn.k_norm.weight")
-
-    @classmethod
-    def _hf_layer_extras(cls, layers):
-        """(qkv_bias, qk_norm) of an HF decoder stack (Llama, Qwen2, Qwen3).  Every layer's named parameters must be exactly the set the runner
-        consumes: the Llama ones, plus q|k|v biases, plus q / k norm weights, the same in every layer (an FP8 projection's weight_scale /
-        input_scale count as its own, whether buffers or parameters).  Anything else -- an o_proj or MLP bias, a parameter the runner would
-        not read -- raises instead of being dropped.  A Qwen3-MoE layer whose MLP is a sparse block holds, instead of the three MLP projections,
-        the router `mlp.gate.weight` and the fused expert tensors `mlp.experts.gate_up_proj` / `mlp.experts.down_proj` (dense and sparse layers
-        may alternate); a shared expert or any other MLP parameter raises by name."""
-        if len(layers) == 0:
-            raise SamdError("the model has no decoder layers")
-        def names_of(lyr, i):
-            # an FP8 projection's scales may be parameters as well as buffers (fbgemm / compressed-tensors layers): the runner reads
-            # weight_scale through samd_hip/fp8.py (input scales are not used: weight-only FP8), so they are not extra parameters
-            # (the same holds for an MXFP4 projection -- a float4_e2m1fn_x2 or uint8 weight -- and its e8m0 weight_scale)
-            skip = {f"{n[:-len('.weight')]}.{sc}" for n, p in lyr.named_parameters()
-                    if n.endswith(".weight") and (F8.is_fp8_dtype(p.dtype) or _is_f4_tensor(p))
-                    for sc in ("weight_scale", "input_scale", "weight_scale_inv")}
-            # the block scales of 4-bit expert tensors (samd_hip/moe.py), which the runner reads; beside plain experts they are extra
-            params = dict(lyr.named_parameters())
-            # an AWQ / GPTQ projection holds qweight / qzeros / scales (/ g_idx) and maybe a bias, as buffers or parameters, in place of a
-            # `weight`: it counts as that weight, and its bias counts as a bias
-            for n, mod in lyr.named_modules():
-                if n and I4.is_int4_module(mod):
-                    for own in list(params):
-                        if own.startswith(n + "."):
-                            del params[own]
-                    params[n + ".weight"] = None
-                    if getattr(mod, "bias", None) is not None:
-                        params[n + ".bias"] = None
-            if any(MOE.is_4bit(params.get(n)) for n in MOE.SPARSE_MLP_PARAMS[1:]):
-                skip |= set(MOE.EXPERT_SCALE_PARAMS)
-            # per-expert INT4 modules (mlp.experts.{e}.gate_proj ...; their tensors are buffers) count as the two fused expert tensors; a
-            # bias of one of them stays in the set and raises by name below
-            # FP8 experts (samd_hip/moe.py): the fused form's two scale tensors are read; the per-expert form (mlp.experts.{e}.gate_proj.weight
-            # + weight_scale_inv, skipped above) counts as the two fused expert tensors
-            if cls._hf_experts_are_fp8(lyr, i):
-                skip |= set(MOE.FP8_EXPERT_SCALE_PARAMS)
-                if not hasattr(lyr.mlp.experts, "gate_up_proj"):
-                    for e in range(len(lyr.mlp.experts)):
-                        for pn in MOE.INT4_EXPERT_PROJECTIONS:
-                            params.pop(f"mlp.experts.{e}.{pn}.weight", None)
-                    params.update({n: None for n in MOE.SPARSE_MLP_PARAMS[1:]})
-            if cls._hf_experts_are_int4(lyr, i):
-                for e in range(len(lyr.mlp.experts)):
-                    for pn in MOE.INT4_EXPERT_PROJECTIONS:
-                        params.pop(f"mlp.experts.{e}.{pn}.weight", None)
-                params.update({n: None for n in MOE.SPARSE_MLP_PARAMS[1:]})
-            return set(params) - skip
-        names0 = names_of(layers[0], 0)
-        qkv_bias = any(n in names0 for n in cls._QKV_BIAS)
-        qk_norm = any(n in names0 for n in cls._QK_NORM)
-        want = set(cls._LAYER_PARAMS) | (set(cls._QKV_BIAS) if qkv_bias else set()) | (set(cls._QK_NORM) if qk_norm else set())
-        want_sparse = (want - set(MOE.DENSE_MLP_PARAMS)) | set(MOE.SPARSE_MLP_PARAMS)
-        for i, lyr in enumerate(layers):
-            names = names_of(lyr, i)
-            if names == want:
-                continue
-            if any(n.startswith("mlp.experts.") or n == "mlp.gate.weight" for n in names):      # a sparse (Qwen3-MoE) layer
-                if names == want_sparse:
-                    continue
-                if any("shared_expert" in n for n in names):
-                    raise SamdError(f"layer {i}: a shared expert is not supported (parameters {sorted(n for n in names if 'shared_expert' in n)})")
-                raise SamdError(f"layer {i}: sparse MLP parameters the runner does not consume {sorted(names - want_sparse)}, or lacks "
-                                f"{sorted(want_sparse - names)} (it reads mlp.gate.weight and the fused mlp.experts.gate_up_proj / down_proj)")
-            extra, missing = sorted(names - want), sorted(want - names)
-            if "self_attn.o_proj.bias" in extra:
-                raise SamdError(f"layer {i}: o_proj bias is not supported (q|k|v biases are)")
-            if any(n.startswith("mlp.") and n.endswith(".bias") for n in extra):
-                raise SamdError(f"layer {i}: MLP projection biases are not supported")
-            raise SamdError(f"layer {i}: parameters the runner does not consume {extra}, or lacks {missing} "
-                            f"(it reads the Llama layer, q|k|v biases (Qwen2) and q / k norm weights (Qwen3))")
-        return qkv_bias, qk_norm
-
-    @classmethod
-    def _hf_sparse_layers(cls, layers):
-        """per decoder layer: does its MLP hold experts (an HF Qwen3MoeSparseMoeBlock)?"""
-        return [any(n.startswith("mlp.experts.") for n, _ in lyr.named_parameters()) or cls._hf_experts_are_int4(lyr, i)
-                for i, lyr in enumerate(layers)]
+    # what reads an HF module lives in samd_hip/hf_import.py; its callers' names stay
+    _hf_experts_are_4bit, _hf_experts_are_fp8 = staticmethod(HF.experts_are_4bit), staticmethod(HF.experts_are_fp8)
+    _hf_experts_are_int8, _hf_experts_are_int4 = staticmethod(HF.experts_are_int8), staticmethod(HF.experts_are_int4)
+    _hf_layer_extras, _hf_sparse_layers = staticmethod(HF.layer_extras), staticmethod(HF.sparse_layers)
+    _LAYER_PARAMS, _QKV_BIAS, _QK_NORM = HF.LAYER_PARAMS, HF.QKV_BIAS, HF.QK_NORM
 
     @classmethod
     def random_init(cls, cfg, max_cache_len, dtype=torch.float16, device="cuda", seed=0, std=0.02, weight_format=None, expert_format=MOE.AUTO, **kw):

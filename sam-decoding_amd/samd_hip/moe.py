@@ -58,7 +58,7 @@ from . import fp8 as F8
 from . import int4 as I4
 from . import int8 as I8
 from . import mxfp4 as MX
-from .formats import QUANT_FORMATS
+from .formats import QUANT_FORMATS, is_f4_tensor
 
 MAX_EXPERTS = 256
 MAX_TOPK = 8
@@ -172,8 +172,7 @@ def resolve_expert_format(expert_format, carries_4bit, has_sparse, carries_int4=
     return expert_format
 
 
-def is_4bit(t):
-    return t is not None and (t.dtype == torch.uint8 or MX.is_fp4_dtype(t.dtype))
+is_4bit = is_f4_tensor
 
 
 def gate_up_tile_order(moe_inter, device=None):
@@ -800,11 +799,17 @@ class ExpertFormat(NamedTuple):
     def down_keys(self):
         return tuple("experts_down" + s for s in self.raw_keys)
 
+    def mix_refusal(self, carried, lacking=None):
+        """the refusal of sparse layers of which only some carry this format (carried: one answer per sparse layer); lacking: the decoder
+        layers that do not, where the caller knows them by index"""
+        eg = "" if lacking is None else f"; e.g. layers {lacking[:3]} do not"
+        return SamdError(f"a mix of {self.mix_label} sparse layers ({sum(carried)} of {len(carried)} carry {self.label} experts{eg}): "
+                         "the runner takes the experts of all sparse layers in one format")
+
     def check_layers(self, layers, carried, dtype):
         """every sparse layer of a raw weights dict carries this format (or none does), with tensors the kernels take"""
         if not all(carried):
-            raise SamdError(f"a mix of {self.mix_label} sparse layers ({sum(carried)} of {len(carried)} carry {self.label} experts): "
-                            "the runner takes the experts of all sparse layers in one format")
+            raise self.mix_refusal(carried)
         for i, l in enumerate(layers):
             if "experts_gu" in l:
                 self.check(*(tuple(l[k] if j == 0 else l.get(k) for j, k in enumerate(ks)) for ks in (self.gu_keys, self.down_keys)), dtype,
