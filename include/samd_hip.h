@@ -427,6 +427,16 @@ int samd_tree_attention_warm(const void *d_q, const void *d_k_cache, const void 
                              int32_t n_q_pad, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t max_len,
                              const uint64_t *d_mask, const int32_t *d_cache_length, const int32_t *d_n, float scale,
                              void *d_workspace, int64_t workspace_bytes, const samd_warm_t *next, void *stream);
+/* Act-order GPTQ: ONE entry for samd_tree_attention_warm (v_transposed 0) and samd_tree_attention_vt (1) with an
+ * optional table.  d_inv_perm int32 [H * 128], a permutation of 0 .. H * 128 - 1: the merge launch stores element c = h * 128 + d of every row
+ * at column d_inv_perm[c] -- with d_inv_perm the inverse of the output projection's K order `perm`, out[r][i] = attention[r][perm[i]]: the same
+ * values as without the table, rows >= n zeroed, only placed elsewhere in their row.  d_inv_perm == NULL is exactly the two entries above,
+ * through their own kernels.  With a table the merge has no warm-up workgroups: `next` must be NULL or ride on the split launch (where 0). */
+int samd_tree_attention_perm(const void *d_q, const void *d_k_cache, const void *d_v_cache, void *d_out, int32_t dtype,
+                             int32_t n_q_pad, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t max_len,
+                             const uint64_t *d_mask, const int32_t *d_cache_length, const int32_t *d_n, float scale,
+                             void *d_workspace, int64_t workspace_bytes, int32_t v_transposed, const int32_t *d_inv_perm,
+                             const samd_warm_t *next, void *stream);
 
 /* The attention block of one decoder layer in ONE launch (csrc/attn_kernels.hip): RoPE on q and k, the K/V row write of
  * SamdStaticCache.update (SO/cache.py:103-115) at [write_pos, write_pos + n), tree-mask attention (SO/model_patch/llama.py:82-96 +
@@ -554,6 +564,16 @@ int samd_rmsnorm(void *d_x, const void *d_delta, const void *d_weight, void *d_o
 /* the same, plus the warm-up workgroups for the projection that consumes d_out (next may be NULL) */
 int samd_rmsnorm_warm(void *d_x, const void *d_delta, const void *d_weight, void *d_out, int32_t rows, int32_t hidden, float eps,
                       int32_t dtype, int32_t n_partials, int64_t partial_stride, const samd_warm_t *next, void *stream);
+/* Act-order GPTQ: samd_rmsnorm_warm with an optional table.  d_perm int32 [hidden], a permutation of 0 .. hidden - 1:
+ * d_out[r][i] = normed[r][d_perm[i]], the norm's own bits (same arithmetic, same summation order), placed in the K order of the act-order
+ * projection that consumes them; the residual stream d_x is updated in natural order as before.  d_out must not be d_x; `next` must be NULL
+ * with a table.  d_perm == NULL is exactly samd_rmsnorm_warm, through its own kernel. */
+int samd_rmsnorm_perm(void *d_x, const void *d_delta, const void *d_weight, void *d_out, int32_t rows, int32_t hidden, float eps,
+                      int32_t dtype, int32_t n_partials, int64_t partial_stride, const int32_t *d_perm, const samd_warm_t *next, void *stream);
+/* d_out[r][i] = d_in[r][d_perm[i]] over rows x K elements of `dtype` (f16 / bf16): the input of an act-order projection that neither a norm
+ * nor an attention merge produces (the one-pass prefill's).  d_perm int32 [K], a permutation of 0 .. K - 1; K a multiple of 8, <= 32768.
+ * d_out may be d_in (a workgroup reads its rows completely before it writes them). */
+int samd_gather_cols(const void *d_in, const int32_t *d_perm, void *d_out, int32_t rows, int32_t K, int32_t dtype, void *stream);
 /* rotary embedding of q,k at positions L + rel_pos[r] (SO/samd_model.py:127-132) and
  * SamdStaticCache.update (SO/cache.py:103-115): K/V rows written at [L, L+n).  d_qkv [rows][(H+2Hkv)*D]. */
 int samd_rope_kv_write(const void *d_qkv, const int32_t *d_rel_pos, const int32_t *d_cache_length, const int32_t *d_n,

@@ -172,6 +172,90 @@ __global__ __launch_bounds__(1024) void k_rmsnorm(T *__restrict__ x, const T *__
     }
 }
 
+// Act-order GPTQ ("Act-order GPTQ"): the projection that consumes the norm's output holds its K axis reordered by
+// `perm`, so the norm stores out[r][i] = normed[r][perm[i]].  k_rmsnorm's arithmetic, expression for expression (same thread count, same
+// block_sum order: the same bits), then the scaled row goes through LDS: the global read and the global write stay 16-byte and coalesced,
+// only the LDS read is scattered.  The row's eight perm entries per output vector are requested at entry with the operands.  A kernel of
+// its own, so that k_rmsnorm stays the instructions it was.
+template <typename T, bool ADD>
+__global__ __launch_bounds__(1024) void k_rmsnorm_perm(T *__restrict__ x, const T *__restrict__ delta, const T *__restrict__ w,
+                                                      T *__restrict__ out, int hidden, float eps, int n_part, long long part_stride,
+                                                      const int *__restrict__ perm) {
+    __shared__ float red[16];
+    __shared__ __attribute__((aligned(16))) T row[8192];     // hidden <= 8192
+    constexpr int MAXV = 4;
+    const size_t base = (size_t)blockIdx.x * hidden;
+    const int stride = blockDim.x * 8;
+    Vec8<T> xv[MAXV], wv[MAXV];
+    int4 pa[MAXV], pb[MAXV];
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; i++) {
+        const int c = threadIdx.x * 8 + i * stride;
+        if (c >= hidden) break;
+        Vec8<T> a = ld8(x + base + c);
+        wv[i] = ld8(w + c);
+        pa[i] = *reinterpret_cast<const int4 *>(perm + c);
+        pb[i] = *reinterpret_cast<const int4 *>(perm + c + 4);
+        if (ADD) {
+            const Vec8<T> d = ld8_or_partials<T>(delta, reinterpret_cast<const float *>(delta), n_part, (size_t)part_stride, base + c);
+#pragma unroll
+            for (int j = 0; j < 8; j++) a.v[j] = (T)((float)a.v[j] + (float)d.v[j]);
+            st8(x + base + c, a);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) { const float f = (float)a.v[j]; ss += f * f; }
+        xv[i] = a;
+    }
+    const float tot = block_sum(ss, red);
+    const float rs = rsqrtf(tot / (float)hidden + eps);
+#pragma unroll
+    for (int i = 0; i < MAXV; i++) {
+        const int c = threadIdx.x * 8 + i * stride;
+        if (c >= hidden) break;
+        Vec8<T> o;
+#pragma unroll
+        for (int j = 0; j < 8; j++) { const T h = (T)((float)xv[i].v[j] * rs); o.v[j] = (T)((float)wv[i].v[j] * (float)h); }
+        st8(row + c, o);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < MAXV; i++) {
+        const int c = threadIdx.x * 8 + i * stride;
+        if (c >= hidden) break;
+        Vec8<T> o;
+        o.v[0] = row[pa[i].x]; o.v[1] = row[pa[i].y]; o.v[2] = row[pa[i].z]; o.v[3] = row[pa[i].w];
+        o.v[4] = row[pb[i].x]; o.v[5] = row[pb[i].y]; o.v[6] = row[pb[i].z]; o.v[7] = row[pb[i].w];
+        st8(out + base + c, o);
+    }
+}
+
+// samd_gather_cols: out[r][i] = in[r][perm[i]] over rows x K (the inputs of an act-order projection that no norm or merge launch produces:
+// the one-pass prefill's).  One workgroup per tile of `tile_rows` rows: the tile is copied into LDS with 16-byte loads, then every thread
+// takes eight perm entries ONCE and gathers that output vector for each row of the tile -- the table is read once per tile, not once per
+// row -- and stores 16 bytes.  A workgroup reads its rows completely before it writes any of them, so out may be in.
+template <typename T>
+__global__ __launch_bounds__(256) void k_gather_cols(const T *in, const int *__restrict__ perm, T *out, int rows, int K, int tile_rows) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gather_tile[];
+    T *tile = reinterpret_cast<T *>(gather_tile);
+    const int r0 = (int)blockIdx.x * tile_rows, nr = rows - r0 < tile_rows ? rows - r0 : tile_rows, vecs = K >> 3;
+    for (int i = threadIdx.x; i < nr * vecs; i += blockDim.x) {
+        const int r = i / vecs, c = (i - r * vecs) * 8;
+        st8(tile + (size_t)r * K + c, ld8(in + (size_t)(r0 + r) * K + c));
+    }
+    __syncthreads();
+    for (int v = threadIdx.x; v < vecs; v += blockDim.x) {
+        const int4 pa = *reinterpret_cast<const int4 *>(perm + 8 * v), pb = *reinterpret_cast<const int4 *>(perm + 8 * v + 4);
+        for (int r = 0; r < nr; r++) {
+            const T *src = tile + (size_t)r * K;
+            Vec8<T> o;
+            o.v[0] = src[pa.x]; o.v[1] = src[pa.y]; o.v[2] = src[pa.z]; o.v[3] = src[pa.w];
+            o.v[4] = src[pb.x]; o.v[5] = src[pb.y]; o.v[6] = src[pb.z]; o.v[7] = src[pb.w];
+            st8(out + (size_t)(r0 + r) * K + 8 * v, o);
+        }
+    }
+}
+
 // RoPE (HF rotate_half convention, cos/sin tables fp32 [max_pos][D/2]) on q and k, then
 //   q_out[r][h][:]            <- rotated q
 //   k_cache[kvh][L + r][:]    <- rotated k        (SamdStaticCache.update, cache.py:106-109)
@@ -500,6 +584,43 @@ int samd_rmsnorm_warm(void *d_x, const void *d_delta, const void *d_weight, void
         if (d_delta) hipLaunchKernelGGL((k_rmsnorm<__bf16, true>), dim3(grid), dim3(rms_threads), 0, st, (__bf16 *)d_x, (const __bf16 *)d_delta, (const __bf16 *)d_weight, (__bf16 *)d_out, hidden, eps, n_part, pst, rows, wa);
         else hipLaunchKernelGGL((k_rmsnorm<__bf16, false>), dim3(grid), dim3(rms_threads), 0, st, (__bf16 *)d_x, (const __bf16 *)nullptr, (const __bf16 *)d_weight, (__bf16 *)d_out, hidden, eps, n_part, pst, rows, wa);
     } else { samd_set_error("samd_rmsnorm: dtype must be f16/bf16"); return SAMD_E_INVALID; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_rmsnorm_perm(void *d_x, const void *d_delta, const void *d_weight, void *d_out, int32_t rows, int32_t hidden, float eps,
+                      int32_t dtype, int32_t n_partials, int64_t partial_stride, const int32_t *d_perm, const samd_warm_t *next, void *stream) {
+    if (!d_perm) return samd_rmsnorm_warm(d_x, d_delta, d_weight, d_out, rows, hidden, eps, dtype, n_partials, partial_stride, next, stream);
+    if (next) { samd_set_error("samd_rmsnorm_perm: the permuting form has no warm-up workgroups (next must be NULL)"); return SAMD_E_INVALID; }
+    const int n_part = n_partials; const long long pst = partial_stride;
+    if (n_partials < 0 || (n_partials > 0 && !d_delta)) { samd_set_error("samd_rmsnorm_perm: partials without a source"); return SAMD_E_INVALID; }
+    if (!d_x || !d_weight || !d_out || d_out == d_x || rows < 1 || hidden % 8 != 0 || hidden > 8192) { samd_set_error("samd_rmsnorm_perm: invalid argument (hidden must be a multiple of 8, <= 8192; out must not be x)"); return SAMD_E_INVALID; }
+    hipStream_t st = (hipStream_t)stream;
+    int rms_threads = ((hidden / 8 + 63) / 64) * 64;                 // samd_rmsnorm_warm's choice: the block sum then adds in the same order
+    rms_threads = rms_threads < 64 ? 64 : (rms_threads > 1024 ? 1024 : rms_threads);
+    if (dtype == SAMD_F16) {
+        if (d_delta) hipLaunchKernelGGL((k_rmsnorm_perm<_Float16, true>), dim3(rows), dim3(rms_threads), 0, st, (_Float16 *)d_x, (const _Float16 *)d_delta, (const _Float16 *)d_weight, (_Float16 *)d_out, hidden, eps, n_part, pst, d_perm);
+        else hipLaunchKernelGGL((k_rmsnorm_perm<_Float16, false>), dim3(rows), dim3(rms_threads), 0, st, (_Float16 *)d_x, (const _Float16 *)nullptr, (const _Float16 *)d_weight, (_Float16 *)d_out, hidden, eps, n_part, pst, d_perm);
+    } else if (dtype == SAMD_BF16) {
+        if (d_delta) hipLaunchKernelGGL((k_rmsnorm_perm<__bf16, true>), dim3(rows), dim3(rms_threads), 0, st, (__bf16 *)d_x, (const __bf16 *)d_delta, (const __bf16 *)d_weight, (__bf16 *)d_out, hidden, eps, n_part, pst, d_perm);
+        else hipLaunchKernelGGL((k_rmsnorm_perm<__bf16, false>), dim3(rows), dim3(rms_threads), 0, st, (__bf16 *)d_x, (const __bf16 *)nullptr, (const __bf16 *)d_weight, (__bf16 *)d_out, hidden, eps, n_part, pst, d_perm);
+    } else { samd_set_error("samd_rmsnorm_perm: dtype must be f16/bf16"); return SAMD_E_INVALID; }
+    LAUNCHCHK();
+    return SAMD_OK;
+}
+
+int samd_gather_cols(const void *d_in, const int32_t *d_perm, void *d_out, int32_t rows, int32_t K, int32_t dtype, void *stream) {
+    if (!d_in || !d_perm || !d_out || rows < 1 || K < 8 || K % 8 != 0 || K > 32768) { samd_set_error("samd_gather_cols: invalid argument (K must be a multiple of 8, <= 32768)"); return SAMD_E_INVALID; }
+    if (dtype != SAMD_F16 && dtype != SAMD_BF16) { samd_set_error("samd_gather_cols: dtype must be f16/bf16"); return SAMD_E_INVALID; }
+    // up to four rows share one read of the table, as many as 64 KiB of LDS hold; few rows: one per workgroup, so that they spread over the CUs
+    int tile_rows = 65536 / (2 * K);
+    tile_rows = tile_rows > 4 ? 4 : tile_rows;
+    if (rows <= 16) tile_rows = 1;
+    const int grid = (rows + tile_rows - 1) / tile_rows;
+    const size_t lds = (size_t)tile_rows * K * 2;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == SAMD_F16) hipLaunchKernelGGL(k_gather_cols<_Float16>, dim3(grid), dim3(256), lds, st, (const _Float16 *)d_in, d_perm, (_Float16 *)d_out, rows, K, tile_rows);
+    else hipLaunchKernelGGL(k_gather_cols<__bf16>, dim3(grid), dim3(256), lds, st, (const __bf16 *)d_in, d_perm, (__bf16 *)d_out, rows, K, tile_rows);
     LAUNCHCHK();
     return SAMD_OK;
 }

@@ -575,6 +575,43 @@ __global__ __launch_bounds__(128) void k_attn_combine(const float *__restrict__ 
     }
 }
 
+// Act-order GPTQ: the output projection holds its K axis reordered, so the merge stores element c = h * 128 + d of a row
+// at column inv[c] -- out_perm[r][i] = out[r][perm[i]] with inv the inverse of perm.  k_attn_combine's loads, sums and rounding; the table entry
+// is requested at entry with the partials.  A kernel of its own (no warm-up workgroups, no arrival counter: quantised runners use neither), so
+// that k_attn_combine stays the instructions it was.  A column outside the row is not stored.
+template <typename E>
+__global__ __launch_bounds__(128) void k_attn_combine_perm(const float *__restrict__ ws, E *__restrict__ out, int n_q_pad, int n_heads,
+                                                           const int *__restrict__ d_L, const int *__restrict__ d_n, const int *__restrict__ inv) {
+    const int h = att_head_of_block(blockIdx.x, n_heads), row = blockIdx.y, d = threadIdx.x;
+    float mv[ATT_SPLITS], lv[ATT_SPLITS], pv[ATT_SPLITS];
+    const int lane = d & 63;
+    const int col = inv[h * ATT_D + d];
+    float2 ml = make_float2(-INFINITY, 0.f);
+    if (lane < ATT_SPLITS) ml = *reinterpret_cast<const float2 *>(ws + (((size_t)lane * n_q_pad + row) * n_heads + h) * (ATT_D + 2) + ATT_D);
+#pragma unroll
+    for (int s = 0; s < ATT_SPLITS; s++) pv[s] = ws[(((size_t)s * n_q_pad + row) * n_heads + h) * (ATT_D + 2) + d];
+#pragma unroll
+    for (int s = 0; s < ATT_SPLITS; s++) { mv[s] = __shfl(ml.x, s); lv[s] = __shfl(ml.y, s); }
+    int n = d_n[0]; n = n > n_q_pad ? n_q_pad : n;
+    float res = 0.f;
+    if (row < n) {
+        const int ntiles = (d_L[0] + n + ATT_TILE - 1) / ATT_TILE;
+        const int used = ntiles < ATT_SPLITS ? ntiles : ATT_SPLITS;
+        float M = -INFINITY;
+#pragma unroll
+        for (int s = 0; s < ATT_SPLITS; s++) if (s < used) M = fmaxf(M, mv[s]);
+        float num = 0.f, den = 0.f;
+#pragma unroll
+        for (int s = 0; s < ATT_SPLITS; s++) {
+            if (s >= used || mv[s] == -INFINITY) continue;
+            const float wgt = exp2f(mv[s] - M);
+            num += wgt * pv[s]; den += wgt * lv[s];
+        }
+        res = den > 0.f ? num / den : 0.f;
+    }
+    if ((unsigned)col < (unsigned)(n_heads * ATT_D)) out[(size_t)row * n_heads * ATT_D + col] = (E)res;
+}
+
 // ================================================================================================
 // k_tree_attention with RoPE and the K/V row write folded in (the k_rope_kv launch disappears): same 16 KV splits over the
 // cached keys, plus ONE more workgroup per head (split ATT_SPLITS) that owns the n new keys.
@@ -1258,7 +1295,7 @@ static int att_direct_rows() {                 // SAMD_ATT_DIRECT_ROWS: the wide
 static int tree_attention_impl(const void *d_q, const void *d_k_cache, const void *d_v_cache, void *d_out, int32_t dtype, int32_t n_q_pad,
                                int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t max_len, const uint64_t *d_mask,
                                const int32_t *d_cache_length, const int32_t *d_n, float scale, void *d_workspace, int64_t workspace_bytes,
-                               const samd_warm_t *next, int *d_arrive, void *stream, int v_transposed = 0) {
+                               const samd_warm_t *next, int *d_arrive, void *stream, int v_transposed = 0, const int *d_inv = nullptr) {
     if (v_transposed && (max_len < 8 || max_len % 8 != 0)) { samd_set_error("samd_tree_attention_vt: max_len must be a multiple of 8"); return SAMD_E_INVALID; }
     // the output projection's warm-up rides on the split launch (the longest glue launch of a layer) or on the merge launch
     const WarmArgs none = warm_args(nullptr);
@@ -1287,10 +1324,12 @@ static int tree_attention_impl(const void *d_q, const void *d_k_cache, const voi
                            (const unsigned long long *)d_mask, d_cache_length, d_n, scale_log2, wa_split)
     if (dtype == SAMD_F16) {
         if (row_tiles > 1) { ATT_GO(F16, _Float16, true); } else { ATT_GO(F16, _Float16, false); }
-        hipLaunchKernelGGL(k_attn_combine<_Float16>, dim3(n_heads, n_q_pad + warm_rows), dim3(ATT_D), 0, st, ws, (_Float16 *)d_out, n_q_pad, n_heads, d_cache_length, d_n, wa, d_arrive);
+        if (d_inv) hipLaunchKernelGGL(k_attn_combine_perm<_Float16>, dim3(n_heads, n_q_pad), dim3(ATT_D), 0, st, ws, (_Float16 *)d_out, n_q_pad, n_heads, d_cache_length, d_n, d_inv);
+        else hipLaunchKernelGGL(k_attn_combine<_Float16>, dim3(n_heads, n_q_pad + warm_rows), dim3(ATT_D), 0, st, ws, (_Float16 *)d_out, n_q_pad, n_heads, d_cache_length, d_n, wa, d_arrive);
     } else {
         if (row_tiles > 1) { ATT_GO(BF16, __bf16, true); } else { ATT_GO(BF16, __bf16, false); }
-        hipLaunchKernelGGL(k_attn_combine<__bf16>, dim3(n_heads, n_q_pad + warm_rows), dim3(ATT_D), 0, st, ws, (__bf16 *)d_out, n_q_pad, n_heads, d_cache_length, d_n, wa, d_arrive);
+        if (d_inv) hipLaunchKernelGGL(k_attn_combine_perm<__bf16>, dim3(n_heads, n_q_pad), dim3(ATT_D), 0, st, ws, (__bf16 *)d_out, n_q_pad, n_heads, d_cache_length, d_n, d_inv);
+        else hipLaunchKernelGGL(k_attn_combine<__bf16>, dim3(n_heads, n_q_pad + warm_rows), dim3(ATT_D), 0, st, ws, (__bf16 *)d_out, n_q_pad, n_heads, d_cache_length, d_n, wa, d_arrive);
     }
 #undef ATT_GO
     LAUNCHCHK();
@@ -1314,6 +1353,18 @@ int samd_tree_attention_vt(const void *d_q, const void *d_k_cache, const void *d
                            const samd_warm_t *next, void *stream) {
     return tree_attention_impl(d_q, d_k_cache, d_vt_cache, d_out, dtype, n_q_pad, n_heads, n_kv_heads, head_dim, max_len, d_mask, d_cache_length, d_n, scale,
                                d_workspace, workspace_bytes, next, nullptr, stream, 1);
+}
+
+/* act-order GPTQ: one entry for samd_tree_attention_warm (v_transposed 0) and samd_tree_attention_vt (1) whose merge stores through d_inv_perm
+ * (k_attn_combine_perm); d_inv_perm == NULL is exactly those two.  The permuting merge has no warm-up workgroups: `next` may ride on the split
+ * launch (where == 0) only. */
+int samd_tree_attention_perm(const void *d_q, const void *d_k_cache, const void *d_v_cache, void *d_out, int32_t dtype, int32_t n_q_pad,
+                             int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t max_len, const uint64_t *d_mask,
+                             const int32_t *d_cache_length, const int32_t *d_n, float scale, void *d_workspace, int64_t workspace_bytes,
+                             int32_t v_transposed, const int32_t *d_inv_perm, const samd_warm_t *next, void *stream) {
+    if (d_inv_perm && next && next->where != 0) { samd_set_error("samd_tree_attention_perm: the permuting merge carries no warm-up (next->where must be 0)"); return SAMD_E_INVALID; }
+    return tree_attention_impl(d_q, d_k_cache, d_v_cache, d_out, dtype, n_q_pad, n_heads, n_kv_heads, head_dim, max_len, d_mask, d_cache_length, d_n, scale,
+                               d_workspace, workspace_bytes, next, nullptr, stream, v_transposed ? 1 : 0, d_inv_perm);
 }
 
 int samd_tree_attention_signal(const void *d_q, const void *d_k_cache, const void *d_v_cache, void *d_out, int32_t dtype, int32_t n_q_pad,

@@ -49,6 +49,8 @@ class DenseFormat(NamedTuple):
     scales_key: str          # memory_report's key for the scales / group data
     codes_per_scale: Optional[int] = None    # one buffer: this many KiB of codes, then 1 KiB of side data; None: (codes, scales) tensors
     precheck: Optional[Callable] = None      # (shape, weights): shapes the kernel cannot run, refused before any device work
+    import_layer: Optional[Callable] = None  # (dense decoder layer module, index, device, dtype, qcfg) -> all four projections' raw entries at
+                                             # once, for a format whose projections depend on each other (act-order: ACT_ORDER_KEYS beside them)
 
     def tensors(self, op):
         """the device tensors of a packed operand: the entry points take one pointer each, in this order"""
@@ -167,6 +169,42 @@ pack_i4 = _pack_groups(I4, I4.fuse_int4, "_z", "_s", "INT4", 2, "samd_gemm_pack_
 pack_i8 = _pack_groups(I8, I8.fuse_int8, "_z8", "_s8", "INT8", 1, "samd_gemm_pack_i8")
 
 
+# Act-order GPTQ: a layer's raw dict may carry, beside its INT4 / INT8 projections, the K order of three inputs as
+# int32 [K] device tensors -- the projection holds W[:, perm], the launch that produces its input stores x[perm].  Absent: plain order.
+ACT_ORDER_KEYS = ("perm_attn", "perm_o", "perm_mlp")         # the inputs of q|k|v, of o_proj, of gate|up (down_proj's is folded at import)
+QKV, GATE_UP = ("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj")
+
+
+def _import_groups_layer(linear_ordered, fuse, raw_keys):
+    """import_layer of INT4 / INT8: the seven GPTQ / AWQ modules of a dense decoder layer -> the four projections' raw entries, act-order
+    resolved.  q, k, v share one input and so must share one g_idx, likewise gate and up: else SamdError by layer and projections.
+    down_proj's input index is the output column of gate|up, so its permutation is folded into the ROWS of gate_proj and up_proj (codes,
+    zero points and scales together) and costs nothing at run time."""
+    def import_layer(lyr, li, dev, dtype, qcfg):
+        got = {p: linear_ordered(getattr(own, p), f"layers.{li}.{p}", config=qcfg)
+               for own, ps in ((lyr.self_attn, QKV + ("o_proj",)), (lyr.mlp, GATE_UP + ("down_proj",))) for p in ps}
+
+        def shared(ps):
+            first = got[ps[0]][3]
+            for p in ps[1:]:
+                pm = got[p][3]
+                if (pm is None) != (first is None) or (pm is not None and not torch.equal(pm, first)):
+                    raise SamdError(f"layers.{li}.{ps[0]}: act-order g_idx differs from layers.{li}.{p}'s: {', '.join(ps)} read one input, "
+                                    "which one launch stores in one order, so they must carry the same g_idx")
+            return first
+        perms = dict(perm_attn=shared(QKV), perm_o=got["o_proj"][3], perm_mlp=shared(GATE_UP))
+        fold = got["down_proj"][3]
+        if fold is not None:
+            for p in GATE_UP:
+                q, z, s, pm = got[p]
+                got[p] = (q[fold], z[fold], s[fold], pm)
+        out = {k: pm.to(device=dev, dtype=torch.int32).contiguous() for k, pm in perms.items() if pm is not None}
+        for k, ps in (("wqkv", QKV), ("wo", ("o_proj",)), ("wgu", GATE_UP), ("wdown", ("down_proj",))):
+            out.update({k + sfx: t for sfx, t in zip(raw_keys, fuse([got[p][:3] for p in ps], dev, dtype))})
+        return out
+    return import_layer
+
+
 def _import_f8b(mods, names, li, part, dev, dtype, qcfg, qcfg8):
     full = [f"layers.{li}.{part}.{x}" for x in names]
     return F8.fuse_fp8_blocks([F8.linear_fp8_block(m, n, qcfg8) for m, n in zip(mods, full)], dev, full)
@@ -213,7 +251,8 @@ DENSE_FORMATS = (
         pack=pack_i4, raw_keys=("", "_z", "_s"),
         import_hf=lambda mods, names, li, part, dev, dtype, qcfg, qcfg8: I4.fuse_int4(
             [I4.linear_int4(m, f"layers.{li}.{x}", config=qcfg) for m, x in zip(mods, names)], dev, dtype),
-        gemm="samd_gemm_skinny_i4", unpack="samd_gemm_unpack_i4", packer="samd_gemm_pack_i4", scales_key="int4_group_data", codes_per_scale=16),
+        gemm="samd_gemm_skinny_i4", unpack="samd_gemm_unpack_i4", packer="samd_gemm_pack_i4", scales_key="int4_group_data", codes_per_scale=16,
+        import_layer=_import_groups_layer(I4.linear_int4_ordered, I4.fuse_int4, ("", "_z", "_s"))),
     DenseFormat(
         name="int8g128", suffix="_i8", label="INT8 (GPTQ)", short="INT8",
         doc="GPTQ 8-bit codes with one scale (model dtype) and one zero point per 128 along K (samd_hip/int8.py).  uint8 [N, K] beside "
@@ -226,7 +265,8 @@ DENSE_FORMATS = (
         pack=pack_i8, raw_keys=("", "_z8", "_s8"),
         import_hf=lambda mods, names, li, part, dev, dtype, qcfg, qcfg8: I8.fuse_int8(
             [I8.linear_int8(m, f"layers.{li}.{x}", config=qcfg) for m, x in zip(mods, names)], dev, dtype),
-        gemm="samd_gemm_skinny_i8", unpack="samd_gemm_unpack_i8", packer="samd_gemm_pack_i8", scales_key="int8_group_data", codes_per_scale=32),
+        gemm="samd_gemm_skinny_i8", unpack="samd_gemm_unpack_i8", packer="samd_gemm_pack_i8", scales_key="int8_group_data", codes_per_scale=32,
+        import_layer=_import_groups_layer(I8.linear_int8_ordered, I8.fuse_int8, ("", "_z8", "_s8"))),
 )
 DENSE = {f.name: f for f in DENSE_FORMATS}
 QUANT_FORMATS = tuple(DENSE)

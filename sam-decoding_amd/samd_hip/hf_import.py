@@ -314,10 +314,11 @@ def classify(lm, weight_format=None, expert_format=MOE.AUTO, dtype=None, native_
 
 
 def _dequantise_groups(Q, linear):
-    """INT4 / INT8: rne_dtype((q - z) * s), one rounding"""
+    """INT4 / INT8: rne_dtype((q - z) * s), one rounding; an act-order projection's W[:, perm] is put back into natural K order"""
     def dequantise(mod, name, dtype, ckpt):
-        q, z, sc = linear(mod, name, config=ckpt.qcfg)
-        return Q.dequantize_groups(q, z, Q.as_scales(sc, dtype, name)).to(dtype)
+        q, z, sc, perm = linear(mod, name, config=ckpt.qcfg)
+        w = Q.dequantize_groups(q, z, Q.as_scales(sc, dtype, name)).to(dtype)
+        return w if perm is None else w[:, I4.inverse_perm(perm).to(w.device)]
     return dequantise
 
 
@@ -328,8 +329,8 @@ def _dequantise_fp8(mod, name, dtype, ckpt):
 
 
 # Checkpoint.dequantise -> (module, name, dtype, ckpt) -> the projection's weight, exactly what a quantised launch would multiply by
-DEQUANTISE = {None: lambda mod, name, dtype, ckpt: mod.weight, "int4g128": _dequantise_groups(I4, I4.linear_int4),
-              "int8g128": _dequantise_groups(I8, I8.linear_int8), "fp8b128": _dequantise_fp8}
+DEQUANTISE = {None: lambda mod, name, dtype, ckpt: mod.weight, "int4g128": _dequantise_groups(I4, I4.linear_int4_ordered),
+              "int8g128": _dequantise_groups(I8, I8.linear_int8_ordered), "fp8b128": _dequantise_fp8}
 
 
 def load(lm, ckpt, device, share=None):
@@ -370,9 +371,12 @@ def load(lm, ckpt, device, share=None):
         groups, lw = [("wqkv", a, "self_attn", ("q_proj", "k_proj", "v_proj")), ("wo", a, "self_attn", ("o_proj",))], {}
         if not ckpt.sparse[li]:
             groups += [("wgu", f, "mlp", ("gate_proj", "up_proj")), ("wdown", f, "mlp", ("down_proj",))]
+        if dense is not None and dense.import_layer is not None and not ckpt.sparse[li]:
+            lw.update(dense.import_layer(lyr, li, dev, dtype, ckpt.qcfg))      # the four projections at once (act-order ties them together)
+            groups = []
         for k, own, part, names in groups:
             mods = [getattr(own, x) for x in names]
-            if dense is not None:                                # the checkpoint's own codes and side data; the runner checks and packs them
+            if dense is not None:                              # the checkpoint's own codes and side data; the runner checks and packs them
                 lw.update({k + sfx: t for sfx, t in zip(dense.raw_keys, dense.import_hf(mods, names, li, part, dev, dtype, ckpt.qcfg, ckpt.qcfg8))})
             else:
                 lw[k] = fuse(mods, [f"layers.{li}.{part}.{x}" for x in names])

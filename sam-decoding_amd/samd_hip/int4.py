@@ -12,8 +12,8 @@ ONE rounding, to the model dtype (fp16: with subnormals, what v_pk_mul_f16 deliv
 (as_scales) -- its weights are then the contract's W for the rounded scales, not the fp16 ones.
 
 The kernel's group size is 128 and only 128: the importers expand a checkpoint whose group_size is a multiple of 128 that divides K, or -1
-(one group per row), by repeating z and s; group sizes 32 and 64, act-order (a g_idx other than k // g), bit widths other than 4 and
-AWQ's "GEMV" layout raise.
+(one group per row), by repeating z and s; group sizes 32 and 64, bit widths other than 4 and AWQ's "GEMV" layout raise.  Act-order
+(a g_idx other than k // g): linear_int4_ordered returns W[:, perm] and perm; hf_import puts perm on the producer of the projection's input.
 
 quantize_groups is the uncalibrated path (asymmetric min / max per group, round to nearest): for benches, random-init models and tests.  On
 Gaussian rows it costs 10.1 % relative RMS weight error (tests/test_int4_weights_cpu.py measures it: 0.1006 in fp16 and in bf16);
@@ -152,16 +152,57 @@ def _unpack_awq_cols(t):
     return out.reshape(t.shape[0], 8 * t.shape[1])
 
 
+NO_ACT_ORDER = ("only the seven projections of a dense decoder layer take act-order: the permutation rides on the launch that produces a "
+                "projection's input, and each expert of a sparse layer has its own permutation of the one input all experts share")
+
+
+def act_order_perm(g_idx, K, g, name, allowed):
+    """the K order of an act-order GPTQ projection: None for the plain order (no g_idx, or g_idx == k // g), else perm int64 [K], the
+    stable argsort of g_idx -- W[:, perm] has its groups contiguous again, group j at columns [j g, (j + 1) g), so y = W[:, perm] x[perm].
+    Raises SamdError unless every group has exactly g members, and -- `allowed` false -- for any order but the plain one."""
+    if not torch.is_tensor(g_idx):
+        return None
+    gi = g_idx.detach().reshape(-1).to(torch.int64)
+    if gi.numel() == K and torch.equal(gi, torch.arange(K, device=gi.device) // g):
+        return None
+    if not allowed:
+        raise SamdError(f"{name}: act-order (a g_idx other than k // group_size) GPTQ checkpoints are not supported here: {NO_ACT_ORDER}")
+    if gi.numel() != K or int(gi.min()) < 0 or int(gi.max()) >= K // g:
+        raise SamdError(f"{name}: act-order g_idx of {gi.numel()} entries in [{int(gi.min())}, {int(gi.max())}] for K = {K} in {K // g} groups")
+    sizes = torch.bincount(gi, minlength=K // g)
+    if bool((sizes != g).any()):
+        bad = int((sizes != g).nonzero()[0])
+        raise SamdError(f"{name}: act-order group {bad} has {int(sizes[bad])} input channels, group_size is {g}: the kernel's groups are "
+                        "contiguous runs of equal size, so every group must have exactly group_size members")
+    return torch.argsort(gi, stable=True)
+
+
+def inverse_perm(perm):
+    """inv with inv[perm[i]] = i"""
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(perm.numel(), dtype=perm.dtype, device=perm.device)
+    return inv
+
+
 def linear_int4(mod, name="projection", zero_offset=None, config=None):
-    """(q uint8 [N, K/2], z uint8 [N, K/128], s [N, K/128] in the checkpoint's scale dtype) of an AWQ or GPTQ projection module, or None for
+    """linear_int4_ordered for the plain K order only: its (q, z, s), or None; act-order raises"""
+    r = linear_int4_ordered(mod, name, zero_offset, config, act_order=False)
+    return None if r is None else r[:3]
+
+
+def linear_int4_ordered(mod, name="projection", zero_offset=None, config=None, act_order=True):
+    """(q, z, s, perm): linear_int4's canonical tensors plus the act-order permutation (act_order_perm; None: plain order).  With a perm,
+    q / z / s describe W[:, perm] -- codes reordered along K, groups contiguous -- which is what the packers and kernels take; the
+    projection's input must then arrive as x[perm].  act_order=False raises for any order but the plain one.
+    (q uint8 [N, K/2], z uint8 [N, K/128], s [N, K/128] in the checkpoint's scale dtype) of an AWQ or GPTQ projection module, or None for
     a module that is not INT4 (is_int4_module).  `config` is the model's quantization_config (dict or object: quant_method "awq" / "gptq",
     bits, group_size, version, checkpoint_format, desc_act); without one the layout is decided by qweight.shape against
     (in_features, out_features) and GPTQ v1 is assumed.  zero_offset: what is added to the stored zero point (default: 1 for GPTQ
     checkpoint_format "gptq", 0 for "gptq_v2" and AWQ).
       AWQ "GEMM": qweight [K, N/8], nibble p of [k][j] = q[8 j + AWQ_ORDER[p]][k]; qzeros [K/g, N/8] likewise; scales [K/g, N].
       GPTQ:       qweight [K/8, N], nibble p of [r][n] = q[n][8 r + p]; qzeros [K/g, N/8], nibble p of [G][j] = column 8 j + p;
-                  scales [K/g, N]; optional g_idx [K], which must be k // g.
-    Raises SamdError for AWQ "GEMV", bits != 4, group sizes that are no multiple of 128 dividing K (32, 64), act-order, a stored zero
+                  scales [K/g, N]; optional g_idx [K]: k // g, or any assignment with g members per group (act-order).
+    Raises SamdError for AWQ "GEMV", bits != 4, group sizes that are no multiple of 128 dividing K (32, 64), desc_act without a g_idx, a stored zero
     point of 15 under GPTQ v1 (public loaders disagree on whether it means 16 or wraps to 0), ill-shaped tensors."""
     if not is_int4_module(mod):
         return None
@@ -206,6 +247,7 @@ def linear_int4(mod, name="projection", zero_offset=None, config=None):
                         "that divide K and -1 (per channel) only")
     if tuple(qz.shape) != (n_groups, N // 8):
         raise SamdError(f"{name}: qzeros of shape {tuple(qz.shape)}; expected [{n_groups}, {N // 8}]")
+    perm = None
     if method == "awq":
         codes = _unpack_awq_cols(qw).t()                           # [N, K]
         zeros = _unpack_awq_cols(qz).t()                           # [N, K/g]
@@ -214,12 +256,10 @@ def linear_int4(mod, name="projection", zero_offset=None, config=None):
         g_idx = getattr(mod, "g_idx", None)
         if _cfg(config, "desc_act", False) and g_idx is None:
             raise SamdError(f"{name}: act-order (desc_act) GPTQ checkpoints are not supported")
-        if torch.is_tensor(g_idx):
-            gi = g_idx.detach()
-            want = torch.arange(K, device=gi.device) // g
-            if gi.numel() != K or not torch.equal(gi.reshape(-1).to(want.dtype), want):
-                raise SamdError(f"{name}: act-order (a g_idx other than k // group_size) GPTQ checkpoints are not supported")
+        perm = act_order_perm(g_idx, K, g, name, act_order)
         codes = _nibbles(qw).permute(1, 0, 2).reshape(N, K)
+        if perm is not None:
+            codes = codes[:, perm.to(codes.device)]
         zeros = _nibbles(qz).reshape(n_groups, N).t()
         fmt = str(_cfg(config, "checkpoint_format", "gptq") or "gptq").lower()
         if fmt not in ("gptq", "gptq_v2"):
@@ -232,7 +272,7 @@ def linear_int4(mod, name="projection", zero_offset=None, config=None):
     rep = g // GROUP
     z = zeros.to(torch.uint8).repeat_interleave(rep, dim=1).contiguous()
     s = sc.t().repeat_interleave(rep, dim=1).contiguous()
-    return pack_nibbles(codes.contiguous()), z, s
+    return pack_nibbles(codes.contiguous()), z, s, perm
 
 
 def fuse_int4(parts, device, dtype=None):

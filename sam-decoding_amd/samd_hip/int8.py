@@ -13,8 +13,8 @@ runner takes them as they are, a bf16 runner rounds each scale ONCE to bf16 at i
 for the rounded scales, not the fp16 ones.
 
 The kernel's group size is 128 and only 128: the importer expands a checkpoint whose group_size is a multiple of 128 that divides K, or -1
-(one group per row), by repeating z and s; group sizes 32 and 64, act-order (a g_idx other than k // g), bit widths other than 8 and AWQ
-modules raise.  4-bit modules are int4.py's.
+(one group per row), by repeating z and s; group sizes 32 and 64, bit widths other than 8 and AWQ modules raise.  Act-order (a g_idx
+other than k // g) is int4.py's: linear_int8_ordered returns W[:, perm] and perm.  4-bit modules are int4.py's.
 
 quantize_groups is the uncalibrated path (asymmetric min / max per group, round to nearest): for benches, random-init models and tests.  On
 Gaussian rows it costs 0.6 % relative RMS weight error (tests/test_int8_weights_cpu.py measures it: 0.00592 in fp16, 0.00617 in bf16, whose
@@ -23,7 +23,7 @@ on any device."""
 import torch
 
 from . import SamdError
-from .int4 import _cfg, quant_config, is_int4_module       # noqa: F401  (the config reader and the qweight / qzeros / scales test are shared)
+from .int4 import _cfg, quant_config, is_int4_module, act_order_perm       # noqa: F401  (the config reader and the qweight / qzeros / scales test are shared)
 
 GROUP = 128
 PROJECTIONS = ("wqkv", "wo", "wgu", "wdown")
@@ -139,13 +139,21 @@ def _bytes(t):
 
 
 def linear_int8(mod, name="projection", zero_offset=None, config=None):
-    """(q uint8 [N, K], z uint8 [N, K/128], s [N, K/128] in the checkpoint's scale dtype) of a GPTQ 8-bit projection module, or None for a
+    """linear_int8_ordered for the plain K order only: its (q, z, s), or None; act-order raises"""
+    r = linear_int8_ordered(mod, name, zero_offset, config, act_order=False)
+    return None if r is None else r[:3]
+
+
+def linear_int8_ordered(mod, name="projection", zero_offset=None, config=None, act_order=True):
+    """(q, z, s, perm): the canonical tensors plus the act-order permutation (int4.act_order_perm; None: plain order).  With a perm,
+    q / z / s describe W[:, perm], and the projection's input must arrive as x[perm].  act_order=False raises for any order but the plain.
+    (q uint8 [N, K], z uint8 [N, K/128], s [N, K/128] in the checkpoint's scale dtype) of a GPTQ 8-bit projection module, or None for a
     module that is not a quantised one (int4.is_int4_module).  `config` is the model's quantization_config (dict or object: quant_method
     "gptq", bits, group_size, checkpoint_format, desc_act); without one GPTQ v1 is assumed.  zero_offset: what is added to the stored zero
     point (default: 1 for checkpoint_format "gptq", 0 for "gptq_v2").
       GPTQ: qweight [K/4, N], byte p of [r][n] = q[n][4 r + p]; qzeros [K/g, N/4], byte p of [G][j] = column 4 j + p; scales [K/g, N];
-            optional g_idx [K], which must be k // g.
-    Raises SamdError for bits != 8, quant_method "awq", group sizes that are no multiple of 128 dividing K (32, 64), act-order, a stored
+            optional g_idx [K]: k // g, or any assignment with g members per group (act-order).
+    Raises SamdError for bits != 8, quant_method "awq", group sizes that are no multiple of 128 dividing K (32, 64), desc_act without a g_idx, a stored
     zero point of 255 under GPTQ v1 (public loaders disagree on whether it means 256 or wraps to 0), ill-shaped tensors."""
     if not is_int4_module(mod):
         return None
@@ -180,16 +188,14 @@ def linear_int8(mod, name="projection", zero_offset=None, config=None):
     g_idx = getattr(mod, "g_idx", None)
     if _cfg(config, "desc_act", False) and g_idx is None:
         raise SamdError(f"{name}: act-order (desc_act) GPTQ checkpoints are not supported")
-    if torch.is_tensor(g_idx):
-        gi = g_idx.detach()
-        want = torch.arange(K, device=gi.device) // g
-        if gi.numel() != K or not torch.equal(gi.reshape(-1).to(want.dtype), want):
-            raise SamdError(f"{name}: act-order (a g_idx other than k // group_size) GPTQ checkpoints are not supported")
+    perm = act_order_perm(g_idx, K, g, name, act_order)
     fmt = str(_cfg(config, "checkpoint_format", "gptq") or "gptq").lower()
     if fmt not in ("gptq", "gptq_v2"):
         raise SamdError(f"{name}: GPTQ checkpoint_format {fmt!r}; the importer takes 'gptq' and 'gptq_v2'")
     offset = (1 if fmt == "gptq" else 0) if zero_offset is None else int(zero_offset)
     codes = _bytes(qw).permute(1, 0, 2).reshape(N, K)
+    if perm is not None:
+        codes = codes[:, perm.to(codes.device)]
     zeros = _bytes(qz).reshape(n_groups, N).t().to(torch.int32) + offset
     if bool((zeros > QMAX).any()):
         raise SamdError(f"{name}: a stored zero point of 255 with the GPTQ v1 offset of +1 ('gptq' checkpoint_format): public loaders disagree "
@@ -197,7 +203,7 @@ def linear_int8(mod, name="projection", zero_offset=None, config=None):
     rep = g // GROUP
     z = zeros.to(torch.uint8).repeat_interleave(rep, dim=1).contiguous()
     s = sc.t().repeat_interleave(rep, dim=1).contiguous()
-    return codes.contiguous(), z, s
+    return codes.contiguous(), z, s, perm
 
 
 def fuse_int8(parts, device, dtype=None):

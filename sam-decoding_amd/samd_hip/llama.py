@@ -19,7 +19,8 @@ from . import (F16, BF16, MAX_DRAFT, TILE_ROWS, QkvEpilogue, SamdError, Session,
                torch_dtype_code)
 from . import hf_import as HF
 from . import moe as MOE
-from .formats import DENSE, DENSE_FORMATS, PROJECTIONS, QUANT_FORMATS
+from . import int4 as I4
+from .formats import ACT_ORDER_KEYS, DENSE, DENSE_FORMATS, PROJECTIONS, QUANT_FORMATS
 
 
 def _env_weight_format(weight_format):
@@ -226,6 +227,19 @@ class LlamaRunner:
         if self.qkv_epilogue and self.attention not in ("split", "split3"):
             raise SamdError(f"attention mode '{self.attention}' rotates q / k inside its own kernel, which has no q|k|v bias or q / k norm: "
                             f"use 'split' or 'split3' for this model")
+        # act-order GPTQ: per layer the K orders of the inputs of q|k|v, o_proj and gate|up (formats.ACT_ORDER_KEYS) as
+        # device tables, or None for a layer in plain order, which takes the launches it always took.  The tables ride on the launches that
+        # produce those inputs -- the two norms and the KV-split merge -- so only the modes that have that merge launch exist
+        self.perms = [self._act_order_tables(l, li) for li, l in enumerate(weights["layers"])]
+        self.act_order = [p is not None for p in self.perms]
+        if any(self.act_order):
+            if not quant or fmt.import_layer is None:
+                raise SamdError("act-order permutation tables (perm_attn / perm_o / perm_mlp) beside projections that are not INT4 / INT8")
+            if self.attention not in ("split", "split3"):
+                raise SamdError(f"attention mode '{self.attention}' writes the attention output inside its own kernel, which has no act-order "
+                                f"form: use 'split' or 'split3' for this checkpoint")
+            if self.draft_head:
+                raise SamdError("an act-order draft head is not supported (its first layer has no norm launch to carry the permutation)")
         # round 6: "split" / "split3" keep V TRANSPOSED too ([H_kv][D][max_len]) wherever the cache length allows 16-byte loads along it: at <= 16 rows
         # samd_tree_attention_vt then runs one wave per (head, KV split) that feeds its MFMAs straight from the V^T rows -- no LDS staging, no
         # workgroup barrier, 11.9 -> 11.0 us per layer at 8 rows (profiles/r06_attention.md).  SAMD_V_LAYOUT=rows keeps the row-major cache (A/B).
@@ -366,14 +380,33 @@ class LlamaRunner:
         if os.environ.get("SAMD_RELEASE_ROW_MAJOR", "0") == "1":
             self.release_row_major()
 
+    def _act_order_tables(self, l, li):
+        """the act-order tables of raw layer l, checked (every entry indexes LDS or a row of the attention output inside a kernel), plus
+        inv_o, the inverse of perm_o, through which the merge launch stores; None for a layer that carries none"""
+        s, t = self.shape, {}
+        for k, n in zip(ACT_ORDER_KEYS, (s.hidden, s.heads * s.head_dim, s.hidden)):
+            p = l.get(k)
+            if p is None:
+                continue
+            if p.dtype != torch.int32 or p.device.type != self.device.type or not p.is_contiguous() or tuple(p.shape) != (n,):
+                raise SamdError(f"layer {li}: {k} must be a contiguous int32 tensor of {n} entries on the GPU")
+            if not torch.equal(torch.sort(p.long()).values, torch.arange(n, device=p.device)):
+                raise SamdError(f"layer {li}: {k} is not a permutation of 0 .. {n - 1}")
+            t[k] = p
+        if "perm_o" in t:
+            t["inv_o"] = I4.inverse_perm(t["perm_o"].long()).to(torch.int32).contiguous()
+        return t or None
+
     def memory_report(self):
         """bytes of HBM the weights take, by form (documented in DESIGN.md section 2): row-major originals (the wide prefill's library
         GEMMs), and the packed forms the streaming kernels read"""
         def nbytes(t):
             return 0 if t is None or t.device.type == "meta" else t.numel() * t.element_size()
         epi_keys = ("bqkv", "q_norm", "k_norm")
-        rep = dict(row_major=sum(nbytes(t) for l in self.w["layers"] for k, t in l.items() if k not in epi_keys and k != "router")
+        rep = dict(row_major=sum(nbytes(t) for l in self.w["layers"] for k, t in l.items() if k not in epi_keys + ACT_ORDER_KEYS and k != "router")
                    + nbytes(self.w["lm_head"]) + nbytes(self.w["embed"]))
+        if any(self.act_order):                                  # act-order GPTQ: the int32 K-order tables of the layers that have them
+            rep["act_order_tables"] = sum(nbytes(t) for p in self.perms if p is not None for t in p.values())
         if self.shape.moe:                                       # routers (model dtype, [E, H]) and the packed experts of the sparse layers
             rep["moe_router"] = sum(nbytes(l.get("router")) for l in self.w["layers"])
             for k in ("moe_gu", "moe_down"):
@@ -706,8 +739,12 @@ class LlamaRunner:
             if self.layer_hook is not None:
                 self.layer_hook(li)
             wp = packed[li]
+            po = self.perms[li] or {}                             # act-order tables; a layer in plain order takes the launches below as ever
             raw_in = head and li == 0                             # eagle2_model.py:516-519: no input layer-norm in the head's layer
-            if not raw_in:
+            if "perm_attn" in po:
+                check(L.samd_rmsnorm_perm(_ptr(b["x"]), _ptr(delta), _ptr(w["ln1"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, dn, dstride,
+                                          _ptr(po["perm_attn"]), None, st))
+            elif not raw_in:
                 check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(delta), _ptr(w["ln1"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, dn, dstride,
                                           hint(w["wqkv"], wp.get("wqkv")), st))
             fused_qkv = wp.get("wqkv64") is not None and self.attention == "split" and RP <= self.native_gemm_max_rows and d_vis is None
@@ -745,13 +782,23 @@ class LlamaRunner:
                         _ptr(src), _ptr(d_relpos), _ptr(d_L), _ptr(d_n), _ptr(self.cos), _ptr(self.sin),
                         _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), R, s.heads, s.kv_heads,
                         s.head_dim, self.max_len, self.rope_rows, dt, n_p, stride, st))
-                check((L.samd_tree_attention_vt if vt else L.samd_tree_attention_warm)(
-                    _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R, s.heads,
-                    s.kv_heads, s.head_dim, self.max_len, _ptr(d_mask), _ptr(d_L), _ptr(d_n), self.scale,
-                    _ptr(b["ws"]), b["ws_bytes"], hint(w["wo"], wp.get("wo")), st))
+                if "inv_o" in po:                             # the merge launch stores the rows in o_proj's K order
+                    check(L.samd_tree_attention_perm(
+                        _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R, s.heads,
+                        s.kv_heads, s.head_dim, self.max_len, _ptr(d_mask), _ptr(d_L), _ptr(d_n), self.scale,
+                        _ptr(b["ws"]), b["ws_bytes"], int(vt), _ptr(po["inv_o"]), None, st))
+                else:
+                    check((L.samd_tree_attention_vt if vt else L.samd_tree_attention_warm)(
+                        _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(b["attn"]), dt, R, s.heads,
+                        s.kv_heads, s.head_dim, self.max_len, _ptr(d_mask), _ptr(d_L), _ptr(d_n), self.scale,
+                        _ptr(b["ws"]), b["ws_bytes"], hint(w["wo"], wp.get("wo")), st))
             src, n_p, stride = gemm(b["attn"].view(b["attn"].shape[0], -1), w["wo"], wp.get("wo"), b["o"], wg=wp.get("wo_g"), q=quantised(wp, "wo"))
-            check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(src), _ptr(w["ln2"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, n_p, stride,
-                                      None, st))           # (no warm-up hint: gate|up is packed group-major, the hint describes 128-column tiles)
+            if "perm_mlp" in po:
+                check(L.samd_rmsnorm_perm(_ptr(b["x"]), _ptr(src), _ptr(w["ln2"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, n_p, stride,
+                                          _ptr(po["perm_mlp"]), None, st))
+            else:
+                check(L.samd_rmsnorm_warm(_ptr(b["x"]), _ptr(src), _ptr(w["ln2"]), _ptr(b["h"]), R, s.hidden, s.eps, dt, n_p, stride,
+                                          None, st))       # (no warm-up hint: gate|up is packed group-major, the hint describes 128-column tiles)
             if "moe_gu" in wp:
                 # sparse layer: route -> gathered expert gate|up + SiLU -> gathered expert down + combine (csrc/gemm_kernels.hip, samd_hip/moe.py)
                 if _span is not None:
@@ -1072,9 +1119,16 @@ class LlamaRunner:
         d_n = torch.full((1,), N, dtype=torch.int32, device=dev)
         check(L.samd_embed_rows(_ptr(ids), _ptr(self.w["embed"]), _ptr(x), N, s.hidden, s.vocab, dt, st))
         delta = None
+
+        def reorder(t, perm):
+            """act-order: the rows of a library product's input into the K order of its unpacked operand, in place (samd_gather_cols)"""
+            if perm is not None:
+                check(L.samd_gather_cols(_ptr(t), _ptr(perm), _ptr(t), t.shape[0], t.shape[1], dt, st))
+            return t
         for li, w in enumerate(self.w["layers"]):
+            po = self.perms[li] or {}
             check(L.samd_rmsnorm(_ptr(x), _ptr(delta), _ptr(w["ln1"]), _ptr(h), N, s.hidden, s.eps, dt, 0, 0, st))
-            self._pf_mm(h, self._pf_weight(li, "wqkv"), qkv, "wqkv", bias=w.get("bqkv"))
+            self._pf_mm(reorder(h, po.get("perm_attn")), self._pf_weight(li, "wqkv"), qkv, "wqkv", bias=w.get("bqkv"))
             if self.epi is not None:
                 # Qwen2 / Qwen3: the bias is already in the product; q / k norm (if any) in front of the RoPE
                 check(L.samd_rope_kv_write_epi(_ptr(qkv), _ptr(relpos), _ptr(d_L), _ptr(d_n), _ptr(self.cos), _ptr(self.sin), None, _ptr(q),
@@ -1098,15 +1152,15 @@ class LlamaRunner:
                 check((L.samd_prefill_attention_vt if self.v_transposed else L.samd_prefill_attention)(
                     _ptr(q), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), _ptr(ao), dt, N, 0, s.heads, s.kv_heads,
                     s.head_dim, self.max_len, self.scale, st))
-                self._pf_mm(ao, self._pf_weight(li, "wo"), o, "wo")
+                self._pf_mm(reorder(ao, po.get("perm_o")), self._pf_weight(li, "wo"), o, "wo")
             else:
                 kk = self.kv[li, 0][:, :Np]
                 if s.kv_heads != s.heads:
                     kk, vv = kk.repeat_interleave(s.heads // s.kv_heads, dim=0), vv.repeat_interleave(s.heads // s.kv_heads, dim=0)
                 att = torch.nn.functional.scaled_dot_product_attention(qp.transpose(0, 1)[None], kk[None], vv[None], is_causal=True, scale=self.scale)
-                self._pf_mm(att[0, :, :N].transpose(0, 1).reshape(N, -1), self._pf_weight(li, "wo"), o, "wo")
+                self._pf_mm(reorder(att[0, :, :N].transpose(0, 1).reshape(N, -1), po.get("perm_o")), self._pf_weight(li, "wo"), o, "wo")
             check(L.samd_rmsnorm(_ptr(x), _ptr(o), _ptr(w["ln2"]), _ptr(h), N, s.hidden, s.eps, dt, 0, 0, st))
-            self._pf_mm(h, self._pf_weight(li, "wgu"), gu, "wgu")
+            self._pf_mm(reorder(h, po.get("perm_mlp")), self._pf_weight(li, "wgu"), gu, "wgu")
             check(L.samd_silu_mul(_ptr(gu), _ptr(act), N, s.inter, dt, 0, 0, st))
             self._pf_mm(act, self._pf_weight(li, "wdown"), d, "wdown")
             delta = d
