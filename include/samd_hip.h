@@ -405,8 +405,11 @@ typedef struct samd_warm {
  * out [n_q_pad][H][D] (rows >= n are zeroed); mask u64[n_q_pad] row i bit j = node i attends node j; n_q_pad <= 128 (round 5), run as
  * 64-row tiles: for n_q_pad > 64 the mask is u64[2][SAMD_MAX_DRAFT] -- the low words (nodes 0..63) of all rows, then, SAMD_MAX_DRAFT
  * entries further, the high words (nodes 64..127).  L and n are read from device
- * memory (d_cache_length, d_n).  head_dim must be 128, dtype f16 or bf16.  d_workspace: scratch of
- * samd_tree_attention_workspace() bytes (split-KV partials). */
+ * memory (d_cache_length, d_n).  head_dim must be 128 or 64, dtype f16 or bf16.  d_workspace: scratch of
+ * samd_tree_attention_workspace() bytes (split-KV partials).
+ * head_dim 64 (samd_tree_attention, _warm, _perm with v_transposed 0 and a table over H * 64 entries): a kernel of its own, one workgroup
+ * per (KV head, KV split, 16-row tile) that stages each K / V tile once for all query heads of the group; the row-major
+ * cache only -- samd_tree_attention_vt and samd_tree_attention_signal return an error at 64 -- and `next` is ignored. */
 int64_t samd_tree_attention_workspace(int32_t n_q_pad, int32_t n_heads, int32_t head_dim);
 int samd_tree_attention(const void *d_q, const void *d_k_cache, const void *d_v_cache, void *d_out, int32_t dtype,
                         int32_t n_q_pad, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t max_len,

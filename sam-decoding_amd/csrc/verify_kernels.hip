@@ -520,8 +520,10 @@ __global__ __launch_bounds__(64) void k_tree_attention_direct(const typename TT:
     }
 }
 
-template <typename E>
-__global__ __launch_bounds__(128) void k_attn_combine(const float *__restrict__ ws, E *__restrict__ out, int n_q_pad, int n_heads,
+// D = the head width (template parameter: 128, or 64 behind k_tree_attention_gqa64 below): D threads per (row, head); the D = 128 instantiations
+// are the kernels of before
+template <typename E, int D = ATT_D>
+__global__ __launch_bounds__(D) void k_attn_combine(const float *__restrict__ ws, E *__restrict__ out, int n_q_pad, int n_heads,
                                                       const int *__restrict__ d_L, const int *__restrict__ d_n, WarmArgs warm, int *__restrict__ arrive) {
     // workgroup (head slot, row) with k_tree_attention's head mapping (att_head_of_block): a head's merge runs on the XCD whose L2 its sixteen
     // split workgroups just wrote the partials through (round 4; the grid was (row, head) before)
@@ -539,13 +541,13 @@ __global__ __launch_bounds__(128) void k_attn_combine(const float *__restrict__ 
     float mv[ATT_SPLITS], lv[ATT_SPLITS], pv[ATT_SPLITS];
     const int lane = d & 63;
     float2 ml = make_float2(-INFINITY, 0.f);
-    if (lane < ATT_SPLITS) ml = *reinterpret_cast<const float2 *>(ws + (((size_t)lane * n_q_pad + row) * n_heads + h) * (ATT_D + 2) + ATT_D);
+    if (lane < ATT_SPLITS) ml = *reinterpret_cast<const float2 *>(ws + (((size_t)lane * n_q_pad + row) * n_heads + h) * (D + 2) + D);
 #pragma unroll
-    for (int s = 0; s < ATT_SPLITS; s++) pv[s] = ws[(((size_t)s * n_q_pad + row) * n_heads + h) * (ATT_D + 2) + d];
+    for (int s = 0; s < ATT_SPLITS; s++) pv[s] = ws[(((size_t)s * n_q_pad + row) * n_heads + h) * (D + 2) + d];
 #pragma unroll
     for (int s = 0; s < ATT_SPLITS; s++) { mv[s] = __shfl(ml.x, s); lv[s] = __shfl(ml.y, s); }
     int n = d_n[0]; n = n > n_q_pad ? n_q_pad : n;
-    E *dst = out + ((size_t)row * n_heads + h) * ATT_D + d;
+    E *dst = out + ((size_t)row * n_heads + h) * D + d;
     float res = 0.f;
     if (row < n) {
         // the splits k_tree_attention actually ran: split s owns the key tiles s, s + ATT_SPLITS, ...
@@ -579,17 +581,17 @@ __global__ __launch_bounds__(128) void k_attn_combine(const float *__restrict__ 
 // at column inv[c] -- out_perm[r][i] = out[r][perm[i]] with inv the inverse of perm.  k_attn_combine's loads, sums and rounding; the table entry
 // is requested at entry with the partials.  A kernel of its own (no warm-up workgroups, no arrival counter: quantised runners use neither), so
 // that k_attn_combine stays the instructions it was.  A column outside the row is not stored.
-template <typename E>
-__global__ __launch_bounds__(128) void k_attn_combine_perm(const float *__restrict__ ws, E *__restrict__ out, int n_q_pad, int n_heads,
+template <typename E, int D = ATT_D>
+__global__ __launch_bounds__(D) void k_attn_combine_perm(const float *__restrict__ ws, E *__restrict__ out, int n_q_pad, int n_heads,
                                                            const int *__restrict__ d_L, const int *__restrict__ d_n, const int *__restrict__ inv) {
     const int h = att_head_of_block(blockIdx.x, n_heads), row = blockIdx.y, d = threadIdx.x;
     float mv[ATT_SPLITS], lv[ATT_SPLITS], pv[ATT_SPLITS];
     const int lane = d & 63;
-    const int col = inv[h * ATT_D + d];
+    const int col = inv[h * D + d];
     float2 ml = make_float2(-INFINITY, 0.f);
-    if (lane < ATT_SPLITS) ml = *reinterpret_cast<const float2 *>(ws + (((size_t)lane * n_q_pad + row) * n_heads + h) * (ATT_D + 2) + ATT_D);
+    if (lane < ATT_SPLITS) ml = *reinterpret_cast<const float2 *>(ws + (((size_t)lane * n_q_pad + row) * n_heads + h) * (D + 2) + D);
 #pragma unroll
-    for (int s = 0; s < ATT_SPLITS; s++) pv[s] = ws[(((size_t)s * n_q_pad + row) * n_heads + h) * (ATT_D + 2) + d];
+    for (int s = 0; s < ATT_SPLITS; s++) pv[s] = ws[(((size_t)s * n_q_pad + row) * n_heads + h) * (D + 2) + d];
 #pragma unroll
     for (int s = 0; s < ATT_SPLITS; s++) { mv[s] = __shfl(ml.x, s); lv[s] = __shfl(ml.y, s); }
     int n = d_n[0]; n = n > n_q_pad ? n_q_pad : n;
@@ -609,7 +611,224 @@ __global__ __launch_bounds__(128) void k_attn_combine_perm(const float *__restri
         }
         res = den > 0.f ? num / den : 0.f;
     }
-    if ((unsigned)col < (unsigned)(n_heads * ATT_D)) out[(size_t)row * n_heads * ATT_D + col] = (E)res;
+    if ((unsigned)col < (unsigned)(n_heads * D)) out[(size_t)row * n_heads * D + col] = (E)res;
+}
+
+// ================================================================================================
+// tree-mask attention for head_dim 64 (Llama-3.2-1B, TinyLlama, SmolLM2), packed by KV head.  At this width k_tree_attention's split -- one
+// workgroup per QUERY head, four waves x 16 rows -- runs one wave at <= 16 rows while each of a KV head's G query heads fetches the same
+// 8 KiB K and V tiles again.  Here one workgroup owns (KV head, KV split, 16-row tile of the draft):
+//  * all 256 threads fetch the split's 64 x 64 K tile and V tile ONCE (two + two 16-byte loads per thread, a wave's instruction = 1 KiB
+//    contiguous) and stage them in LDS: K as a padded row-major image (row = key, 144 B apart: the B operand of Q K^T is then one 16-byte
+//    LDS read per MFMA), V transposed with key pairs packed per dword (k_tree_attention's Vt image: P V's B operand likewise);
+//  * the four waves take the group's query heads kvh G + w, + 4 (HPW = 2 heads per wave when G > 4; a group of more than 8 heads is cut
+//    into workgroups of 8), every wave at 16 rows.  With G < 4 the waves left over take further 16-row tiles (tpb = 4 / G tiles per
+//    workgroup for G = 1, 2); at G = 3 the fourth wave only helps staging;
+//  * Q K^T = 4 key blocks x 2 k-steps of v_mfma_f32_16x16x32, P V = 4 output tiles x 2 k-steps; online softmax in registers (exp2);
+//  * the next tile of the split is requested right after this one went to LDS, so its latency lies under the MFMAs and the softmax;
+//  * loads that need neither L nor n (Q, mask rows, the split's first tile) go out before the two scalars are read; keys are clamped to
+//    the cache, what lies beyond L + n is masked (K) / zeroed (V), query rows >= n are zeroed;
+//  * partials in k_tree_attention's workspace format with D = 64, merged by k_attn_combine<E, 64>.
+// WIDE = a draft of 65..128 nodes (up to eight 16-row tiles, two mask words per row); the <= 64-node instantiation has no second word.
+// ================================================================================================
+#define A64_D 64
+#define K64_STRIDE (A64_D + 8)        // halfs per staged K row: 144 B, 16 rows of one ds_read_b128 start in 16 different bank groups
+
+template <typename TT, bool WIDE, int HPW>
+__global__ __launch_bounds__(256) void k_tree_attention_gqa64(const typename TT::elem *__restrict__ q, const typename TT::elem *__restrict__ kc,
+                                                              const typename TT::elem *__restrict__ vc, float *__restrict__ ws,
+                                                              int n_q_pad, int n_heads, int n_kv_heads, long long max_len,
+                                                              const unsigned long long *__restrict__ mask, const int *__restrict__ d_L,
+                                                              const int *__restrict__ d_n, float scale_log2, int tpb) {
+    typedef typename TT::elem E;
+    typedef typename TT::vec8 V8;
+    __shared__ __attribute__((aligned(16))) E Ks[ATT_TILE * K64_STRIDE];
+    __shared__ __attribute__((aligned(16))) E Vt[A64_D * VT_STRIDE];
+    __shared__ __attribute__((aligned(16))) E Pw[4 * HPW * 16 * P_STRIDE];
+
+    const int G = n_heads / n_kv_heads, chunks = (G + 7) >> 3;               // chunk = up to 8 query heads of the KV head
+    const int kvh = blockIdx.x / chunks, g0 = 8 * (blockIdx.x % chunks), split = blockIdx.y;
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, lr = l & 15, lg = l >> 4;
+    const int hw = 4 / tpb;                                                  // waves side by side over heads; tpb row tiles per workgroup
+    const int row_base = 16 * ((int)blockIdx.z * tpb + w / hw);
+    const int gs = g0 + w % hw;                                              // this wave's heads within the group: gs, gs + 4
+    const bool tile_exists = row_base < n_q_pad;
+    // ---- loads that need neither L nor n: Q fragments, mask rows, the split's first K / V tile
+    bool act[HPW];
+    int head[HPW];
+    V8 qa[HPW][2];
+#pragma unroll
+    for (int j = 0; j < HPW; j++) {
+        const int g = gs + 4 * j, qrow = row_base + lr;
+        act[j] = tile_exists && g < G;
+        head[j] = kvh * G + (g < G ? g : 0);
+#pragma unroll
+        for (int kk = 0; kk < 2; kk++) {
+            uint4 raw = make_uint4(0, 0, 0, 0);
+            if (act[j] && qrow < n_q_pad) raw = *reinterpret_cast<const uint4 *>(q + ((size_t)qrow * n_heads + head[j]) * A64_D + 32 * kk + 8 * lg);
+            qa[j][kk] = __builtin_bit_cast(V8, raw);
+        }
+    }
+    unsigned long long mrow[4], mrow_hi[WIDE ? 4 : 1];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int row = row_base + 4 * lg + r;
+        mrow[r] = row < n_q_pad ? mask[row] : 0ull;
+        if constexpr (WIDE) mrow_hi[r] = row < n_q_pad ? mask[SAMD_MAX_DRAFT + row] : 0ull;
+    }
+    const E *kbase = kc + (size_t)kvh * max_len * A64_D;
+    const E *vbase = vc + (size_t)kvh * max_len * A64_D;
+    uint4 kra, krb, vra, vrb;
+    const int vp = tid >> 3, vch = tid & 7;            // K: keys vp and vp + 32, V: the key pair (2 vp, 2 vp + 1), each x columns 8 vch .. + 8
+    auto load_kv = [&](int key0) {
+        const int last = (int)max_len - 1;
+        int ka = key0 + vp, kb = ka + 32;
+        ka = ka < last ? ka : last; kb = kb < last ? kb : last;
+        kra = *reinterpret_cast<const uint4 *>(kbase + (size_t)ka * A64_D + 8 * vch);
+        krb = *reinterpret_cast<const uint4 *>(kbase + (size_t)kb * A64_D + 8 * vch);
+        ka = key0 + 2 * vp; kb = ka + 1;
+        ka = ka < last ? ka : last; kb = kb < last ? kb : last;
+        vra = *reinterpret_cast<const uint4 *>(vbase + (size_t)ka * A64_D + 8 * vch);
+        vrb = *reinterpret_cast<const uint4 *>(vbase + (size_t)kb * A64_D + 8 * vch);
+    };
+    load_kv(split * ATT_TILE);
+    const int L = d_L[0];
+    int n = d_n[0]; n = n > n_q_pad ? n_q_pad : n;
+    const int total = L + n;
+    const int ntiles = (total + ATT_TILE - 1) / ATT_TILE;
+    if (split >= ntiles) return;                       // no keys for this split: the merge only reads the splits in use
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < HPW; j++) {
+        act[j] = act[j] && row_base < n;
+        any = any || act[j];
+        if (row_base + lr >= n) { qa[j][0] = __builtin_bit_cast(V8, make_uint4(0, 0, 0, 0)); qa[j][1] = qa[j][0]; }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) if (row_base + 4 * lg + r >= n) { mrow[r] = 0ull; if constexpr (WIDE) mrow_hi[r] = 0ull; }
+
+    float m_run[HPW][4], l_run[HPW][4];
+    floatx4 o[HPW][4];
+#pragma unroll
+    for (int j = 0; j < HPW; j++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) { m_run[j][r] = -INFINITY; l_run[j][r] = 0.f; }
+#pragma unroll
+        for (int dt = 0; dt < 4; dt++) o[j][dt] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    }
+
+    for (int t = split; t < ntiles; t += ATT_SPLITS) {
+        const int key0 = t * ATT_TILE;
+        __syncthreads();                                   // the previous tile's Ks / Vt / Pw reads are done
+        // ---- stage K (row-major, padded) and V^T (key pairs packed per dword; rows past L + n are zero: their P is 0, but 0 x garbage could be NaN)
+        *reinterpret_cast<uint4 *>(&Ks[vp * K64_STRIDE + 8 * vch]) = kra;
+        *reinterpret_cast<uint4 *>(&Ks[(vp + 32) * K64_STRIDE + 8 * vch]) = krb;
+        {
+            const int ka = key0 + 2 * vp, kb = ka + 1;
+            const unsigned ma = ka < total ? 0xFFFFFFFFu : 0u, mb = kb < total ? 0xFFFFFFFFu : 0u;
+            const unsigned a[4] = {vra.x & ma, vra.y & ma, vra.z & ma, vra.w & ma}, b[4] = {vrb.x & mb, vrb.y & mb, vrb.z & mb, vrb.w & mb};
+            unsigned int *vdst = reinterpret_cast<unsigned int *>(&Vt[8 * vch * VT_STRIDE + 2 * vp]);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {                  // columns 8 vch + 2 j, + 2 j + 1: key 2 vp in the low half of the dword, 2 vp + 1 in the high half
+                vdst[(2 * j) * (VT_STRIDE / 2)] = (a[j] & 0xFFFFu) | (b[j] << 16);
+                vdst[(2 * j + 1) * (VT_STRIDE / 2)] = (a[j] >> 16) | (b[j] & 0xFFFF0000u);
+            }
+        }
+        if (t + ATT_SPLITS < ntiles) load_kv(key0 + ATT_SPLITS * ATT_TILE);       // the split's next tile: in flight across this tile's arithmetic
+        __syncthreads();                                   // Ks, Vt staged
+        if (!any) continue;                                // (wave-uniform; both barriers above are passed by every wave)
+        // ---- S = Q K^T: B = Ks[key 16 st + lr][d = 32 kk + 8 lg .. + 8], read once for all heads of the wave
+        uint4 kf[4][2];
+#pragma unroll
+        for (int st = 0; st < 4; st++)
+#pragma unroll
+            for (int kk = 0; kk < 2; kk++) kf[st][kk] = *reinterpret_cast<const uint4 *>(&Ks[(16 * st + lr) * K64_STRIDE + 32 * kk + 8 * lg]);
+#pragma unroll
+        for (int j = 0; j < HPW; j++) {
+            if (!act[j]) continue;
+            floatx4 s[4];
+#pragma unroll
+            for (int st = 0; st < 4; st++) {
+                floatx4 acc = (floatx4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kk = 0; kk < 2; kk++) acc = Mfma<TT>::run(qa[j][kk], __builtin_bit_cast(V8, kf[st][kk]), acc);
+                s[st] = acc;
+            }
+            // ---- mask, online softmax (exp2 domain); lane holds rows 4 lg + r, key 16 st + lr
+            float tmax[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) tmax[r] = -INFINITY;
+#pragma unroll
+            for (int st = 0; st < 4; st++) {
+                const int key = key0 + 16 * st + lr;
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int rel = key - L;                                   // index of a NEW key among the draft's nodes
+                    bool ok;
+                    if constexpr (WIDE) {
+                        const unsigned long long word = rel < 64 ? mrow[r] : mrow_hi[r];
+                        ok = (key < L) | ((key < total) & (bool)((word >> (rel & 63)) & 1ull));
+                    } else ok = (key < L) | ((key < total) & (bool)((mrow[r] >> (rel & 63)) & 1ull));
+                    const float v = ok ? s[st][r] * scale_log2 : -INFINITY;
+                    s[st][r] = v;
+                    tmax[r] = fmaxf(tmax[r], v);
+                }
+            }
+            E *Pmine = Pw + (w * HPW + j) * 16 * P_STRIDE;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float v = row16_max(tmax[r]);
+                const float m_new = fmaxf(m_run[j][r], v);
+                const float m_use = m_new == -INFINITY ? 0.f : m_new;
+                const float alpha = __builtin_amdgcn_exp2f(m_run[j][r] - m_use);       // m_run = -inf -> 0
+                float psum = 0.f;
+#pragma unroll
+                for (int st = 0; st < 4; st++) {
+                    const float p = __builtin_amdgcn_exp2f(s[st][r] - m_use);
+                    psum += p;
+                    Pmine[(4 * lg + r) * P_STRIDE + 16 * st + lr] = (E)p;
+                }
+                psum = row16_sum(psum);
+                l_run[j][r] = l_run[j][r] * alpha + psum;
+                m_run[j][r] = m_new;
+#pragma unroll
+                for (int dt = 0; dt < 4; dt++) o[j][dt][r] *= alpha;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();       // the wave's own P tiles are written
+        // ---- O += P V: A = P[row = lr][keys 32 kcx + 8 lg .. + 8], B = Vt[d = 16 dt + lr][same keys], read once for all heads of the wave
+        uint4 vf[4][2];
+#pragma unroll
+        for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+            for (int kcx = 0; kcx < 2; kcx++) vf[dt][kcx] = *reinterpret_cast<const uint4 *>(&Vt[(16 * dt + lr) * VT_STRIDE + 32 * kcx + 8 * lg]);
+#pragma unroll
+        for (int j = 0; j < HPW; j++) {
+            if (!act[j]) continue;
+            const E *Pmine = Pw + (w * HPW + j) * 16 * P_STRIDE;
+            V8 pa[2];
+#pragma unroll
+            for (int kcx = 0; kcx < 2; kcx++) pa[kcx] = __builtin_bit_cast(V8, *reinterpret_cast<const uint4 *>(&Pmine[lr * P_STRIDE + 32 * kcx + 8 * lg]));
+#pragma unroll
+            for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+                for (int kcx = 0; kcx < 2; kcx++) o[j][dt] = Mfma<TT>::run(pa[kcx], __builtin_bit_cast(V8, vf[dt][kcx]), o[j][dt]);
+        }
+    }
+    // ---- partial result: ws[split][row][h][0..63] = O, [64] = m, [65] = l
+#pragma unroll
+    for (int j = 0; j < HPW; j++) {
+        if (!act[j]) continue;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int row = row_base + 4 * lg + r;
+            if (row >= n_q_pad) continue;
+            float *dst = ws + (((size_t)split * n_q_pad + row) * n_heads + head[j]) * (A64_D + 2);
+#pragma unroll
+            for (int dt = 0; dt < 4; dt++) dst[16 * dt + lr] = o[j][dt][r];
+            if (lr == 0) { dst[A64_D] = m_run[j][r]; dst[A64_D + 1] = l_run[j][r]; }
+        }
+    }
 }
 
 // ================================================================================================
@@ -1303,15 +1522,35 @@ static int tree_attention_impl(const void *d_q, const void *d_k_cache, const voi
     const int warm_rows = (warm_blocks(wa) + n_heads - 1) / n_heads;                         // extra blockIdx.y rows of the merge launch
     const int warm_splits = (warm_blocks(wa_split) + n_heads - 1) / n_heads;                 // extra blockIdx.y rows of the split launch
     if (!d_q || !d_k_cache || !d_v_cache || !d_out || !d_mask || !d_cache_length || !d_n || !d_workspace) { samd_set_error("samd_tree_attention: null pointer"); return SAMD_E_INVALID; }
-    if (head_dim != ATT_D || n_q_pad < 1 || n_q_pad > SAMD_MAX_DRAFT || n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0 ||
-        (dtype != SAMD_F16 && dtype != SAMD_BF16) || workspace_bytes < samd_tree_attention_workspace(n_q_pad, n_heads, head_dim)) {
-        samd_set_error("samd_tree_attention: unsupported shape (head_dim must be 128, n_q_pad <= 128, f16/bf16) or workspace too small");
+    if ((head_dim != ATT_D && head_dim != A64_D) || n_q_pad < 1 || n_q_pad > SAMD_MAX_DRAFT || n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0 ||
+        max_len < 1 || (dtype != SAMD_F16 && dtype != SAMD_BF16) || workspace_bytes < samd_tree_attention_workspace(n_q_pad, n_heads, head_dim)) {
+        samd_set_error("samd_tree_attention: unsupported shape (head_dim must be 64 or 128, n_q_pad <= 128, f16/bf16) or workspace too small");
         return SAMD_E_INVALID;
     }
+    if (head_dim == A64_D && (v_transposed || d_arrive)) { samd_set_error("samd_tree_attention: head_dim 64 reads a row-major V cache only (no _vt, no _signal form)"); return SAMD_E_INVALID; }
     const int row_tiles = (n_q_pad + 63) / 64;                 // > 64 rows: d_mask holds [2][SAMD_MAX_DRAFT] words (low, high)
     hipStream_t st = (hipStream_t)stream;
     const float scale_log2 = scale * 1.4426950408889634f;
     float *ws = (float *)d_workspace;
+    if (head_dim == A64_D) {
+        // k_tree_attention_gqa64: grid = (KV head x chunk of <= 8 query heads, KV split, ceil(16-row tiles / tpb)); the L2-warm hint is ignored
+        const int G = n_heads / n_kv_heads, chunks = (G + 7) / 8, tpb = G == 1 ? 4 : (G == 2 ? 2 : 1), tiles16 = (n_q_pad + 15) / 16;
+        const dim3 grid(n_kv_heads * chunks, ATT_SPLITS, (tiles16 + tpb - 1) / tpb);
+#define A64_GO(TT, ET, W, HPW) hipLaunchKernelGGL((k_tree_attention_gqa64<TT, W, HPW>), grid, dim3(256), 0, st, (const ET *)d_q, (const ET *)d_k_cache, \
+                           (const ET *)d_v_cache, ws, n_q_pad, n_heads, n_kv_heads, (long long)max_len, (const unsigned long long *)d_mask, \
+                           d_cache_length, d_n, scale_log2, tpb)
+#define A64_ALL(TT, ET) do { \
+            if (row_tiles > 1) { if (G > 4) A64_GO(TT, ET, true, 2); else A64_GO(TT, ET, true, 1); } \
+            else { if (G > 4) A64_GO(TT, ET, false, 2); else A64_GO(TT, ET, false, 1); } \
+            if (d_inv) hipLaunchKernelGGL((k_attn_combine_perm<ET, A64_D>), dim3(n_heads, n_q_pad), dim3(A64_D), 0, st, ws, (ET *)d_out, n_q_pad, n_heads, d_cache_length, d_n, d_inv); \
+            else hipLaunchKernelGGL((k_attn_combine<ET, A64_D>), dim3(n_heads, n_q_pad), dim3(A64_D), 0, st, ws, (ET *)d_out, n_q_pad, n_heads, d_cache_length, d_n, none, (int *)nullptr); \
+        } while (0)
+        if (dtype == SAMD_F16) A64_ALL(F16, _Float16); else A64_ALL(BF16, __bf16);
+#undef A64_ALL
+#undef A64_GO
+        LAUNCHCHK();
+        return SAMD_OK;
+    }
 #define ATT_GO(TT, ET, W) if (v_transposed && n_q_pad <= att_direct_rows()) \
                           hipLaunchKernelGGL((k_tree_attention_direct<TT>), dim3(n_heads, ATT_SPLITS + warm_splits, (n_q_pad + 15) / 16), dim3(64), 0, st, (const ET *)d_q, \
                            (const ET *)d_k_cache, (const ET *)d_v_cache, ws, n_q_pad, n_heads, n_kv_heads, (long long)max_len, \

@@ -77,7 +77,8 @@ class LlamaShape:
 
     qkv_bias: q|k|v carry a bias (Qwen2 / Qwen2.5); qk_norm: q and k go through a per-head RMSNorm before the RoPE (Qwen3).  Both default to
     what the config's model_type implies; from_hf passes what the module actually holds.  Raises SamdError for what the runner does not run:
-    sliding-window layers, an o_proj bias, MLP biases, head_dim != 128.
+    sliding-window layers, an o_proj bias, MLP biases, a head_dim other than 64 or 128, and at head_dim 64 anything but the Llama family
+    (no q|k|v bias, no q / k norm, no experts).
     model_type "qwen3_moe" (which implies qk_norm): n_experts, top_k, moe_inter, norm_topk and `sparse`, the per-layer map of which MLPs are
     sparse blocks, decided from mlp_only_layers / decoder_sparse_step exactly as Qwen3MoeDecoderLayer.__init__ decides it; `moe` = any."""
 
@@ -99,8 +100,9 @@ class LlamaShape:
             theta = rp.get("rope_theta")
         self.rope_theta = float(theta if theta is not None else 10000.0)
         self.rope_scaling = dict(rp) if isinstance(rp, dict) else {}
-        if self.head_dim != 128:
-            raise SamdError("the gfx950 tree-attention kernel is specialised for head_dim 128 (Vicuna-7B / Llama-3-8B)")
+        if self.head_dim not in (64, 128):
+            raise SamdError(f"head_dim {self.head_dim}: the gfx950 tree-attention kernels exist for head_dim 128 (Vicuna-7B / Llama-3-8B) and "
+                            f"head_dim 64 (Llama-3.2-1B / TinyLlama / SmolLM2)")
         self.model_type = str(_cfg_get(cfg, "model_type", None) or "llama")
         layer_types = _cfg_get(cfg, "layer_types", None) or ()
         if _cfg_get(cfg, "use_sliding_window", False) or any(t != "full_attention" for t in layer_types):
@@ -122,6 +124,10 @@ class LlamaShape:
             self.norm_topk = bool(_cfg_get(cfg, "norm_topk_prob", False))
             self.sparse = MOE.sparse_layer_map(self.layers, self.n_experts, _cfg_get(cfg, "mlp_only_layers"), _cfg_get(cfg, "decoder_sparse_step", 1))
         self.moe = any(self.sparse)
+        if self.head_dim == 64 and (self.qkv_bias or self.qk_norm or self.model_type == "qwen3_moe"):
+            # the q|k|v epilogue (samd_rope_kv_write_epi) and the expert path are 128-wide only: the 64-wide path is the Llama family's
+            raise SamdError("head_dim 64 runs Llama-family models only: q|k|v bias (Qwen2), q / k RMSNorm (Qwen3) and mixture-of-experts "
+                            "models need head_dim 128")
         if self.moe:
             MOE.check_shape(self.hidden, self.moe_inter, self.n_experts, self.top_k)
 
@@ -221,6 +227,14 @@ class LlamaRunner:
         self.attention = attention or os.environ.get("SAMD_ATTENTION", "split")
         if self.attention not in ("split", "split2", "split3", "block"):
             raise SamdError(f"unknown attention mode '{self.attention}'")
+        # head_dim 64 (csrc/verify_kernels.hip: k_tree_attention_gqa64): the split attention over a row-major cache, RoPE + K/V row write from the
+        # position tables (samd_rope_kv_write takes any even width; the per-row cos | sin form is 128-wide), the eight-launch forward at
+        # every bucket -- pack_qkv64 declines the width, so there is no fused q|k|v tile and no norm-fold form.  The one-launch kernels
+        # ("split2", "block", and with "block" the EAGLE draft heads) stay 128-wide.
+        self.rope_tables = self.attention == "split3" or s.head_dim == 64
+        if s.head_dim == 64 and (self.attention not in ("split", "split3") or self.draft_head):
+            raise SamdError(f"head_dim 64 runs attention mode 'split' (or 'split3') of a base model only: mode '{self.attention}' and EAGLE "
+                            f"draft heads need head_dim 128")
         # Qwen2 q|k|v bias / Qwen3 q / k norm: applied by samd_rope_kv_write_epi between the q|k|v product and the RoPE, so only the forms whose
         # RoPE runs there exist: "split" / "split3", the split-K (or library) q|k|v projection -- no fused q|k|v tiles, no norm-fold forward
         self.qkv_epilogue = bool(s.qkv_bias or s.qk_norm)
@@ -722,7 +736,7 @@ class LlamaRunner:
         log_routes = s.moe and self.route_log is not None and not torch.cuda.is_current_stream_capturing()
         block = self.attention == "block"
         vt = self.v_transposed and not block          # the split launches over a transposed V cache (round 6)
-        if self.attention != "split3" and not resumed:
+        if not self.rope_tables and not resumed:
             # cos / sin of every row's position (visible length + relative position), once per forward: the attention launches of all
             # layers read them without first having to wait for L
             check(L.samd_rope_rows(_ptr(d_relpos), _ptr(d_vis if d_vis is not None else d_L), _ptr(self.cos), _ptr(self.sin), _ptr(b["cs"]), R,
@@ -773,7 +787,7 @@ class LlamaRunner:
                         _ptr(src), _ptr(d_relpos), _ptr(d_L), _ptr(d_n), None if cs_form else _ptr(self.cos), None if cs_form else _ptr(self.sin),
                         _ptr(b["cs"]) if cs_form else None, _ptr(b["q"]), _ptr(self.kv[li, 0]), _ptr(self.kv[li, 1]), int(vt), R, s.heads,
                         s.kv_heads, s.head_dim, self.max_len, self.rope_rows, dt, n_p, stride, C.byref(self.epi[li]), st))
-                elif self.attention == "split":
+                elif not self.rope_tables:
                     check((L.samd_rope_kv_write_cs_vt if vt else L.samd_rope_kv_write_cs)(
                         _ptr(src), _ptr(d_relpos), _ptr(d_L), _ptr(d_n), _ptr(b["cs"]), _ptr(b["q"]), _ptr(self.kv[li, 0]),
                         _ptr(self.kv[li, 1]), R, s.heads, s.kv_heads, s.head_dim, self.max_len, dt, n_p, stride, st))
